@@ -14,12 +14,17 @@ synthetic weights / synthetic prompts (no checkpoints offline), n_steps_text_enc
         `scaling` is "strong"; `value` = audio seconds of all 64 prompts / MAX-over-ranks time.
 
   python bench.py [--gpus N --steps K --warmup W]     (N > 1: one rank per GPU; under torch.distributed.run as the driver launches it, or
-                                                       plain - the process then re-executes itself under that launcher, launch_ranks();
+                                                       plain - the process then starts that launcher as its child, launch_ranks();
                                                        --gpus that disagrees with WORLD_SIZE or with the node's GPU count exits 2)
+                  [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel against HBM) and, at N = 1, `cpu_baseline` (the CPU oracle timed on
-this host, 4 pinned threads, on the headline workload itself - about 20 s; test infrastructure used as the measured-beside baseline
-only, never on the product path).
+Prints ONE JSON line on rank 0.  At N = 1 a plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+stage times); `--full` adds the legs measured beside it: `roofline` (dominant kernel against HBM), the 64-prompt lock-step job, the other
+fine order, the tolerance route, the 768-step cap, bark-large, q4_0, the few-slot jobs and `cpu_baseline` (the CPU oracle timed on this host,
+4 pinned threads, on the headline workload itself - about 20 s; test infrastructure used as the measured-beside baseline only, never on
+the product path).  The N > 1 line always carries its `roofline` and weak-scaling leg.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32 PCM, token ids as float64; at most 64 MB, a fixed
+seeded sample beyond that): the inputs are the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -103,6 +108,20 @@ def gather_batch_results(pcms, idx, n_total: int, rank: int, world: int, device=
                 if i >= 0:
                     out[int(i)] = host[k, :n].copy()
     return counts, out
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = 64 << 20):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32 (float arrays) or float64 (integer ids, exact), together at most `limit`
+    bytes; beyond that each array is cut to its share of the limit by a fixed seeded sample of its flattened elements (same sizes, same sample)."""
+    import numpy as np
+    arrays = {k: np.asarray(v, np.float32 if np.asarray(v).dtype.kind == "f" else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        if total > limit:
+            v = v.ravel()
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, int(v.size * limit // total), replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def n1_reference(a, n_prompts: int):
@@ -255,11 +274,13 @@ def few_slot_jobs_leg(path: str, prompts, n_semantic: int, deadline: float = flo
 
 
 def launch_ranks(n: int, all_on_device0: bool = False):
-    """`python bench.py --gpus N` without a launcher: this process replaces itself by the driver's own N > 1 form,
+    """`python bench.py --gpus N` without a launcher: this process runs the driver's own N > 1 form as its child and exits with its status,
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same arguments>`
-    (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the launcher).  Refuses (exit 2, nothing on stdout) when the node
-    shows fewer than N GPUs - an N-GPU request must never turn into a line that says n_gpus = 1."""
+    (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the launcher).  A child, not an exec: counting the GPUs may already
+    have opened the device in this process.  Refuses (exit 2, nothing on stdout) when the node shows fewer than N GPUs - an N-GPU request
+    must never turn into a line that says n_gpus = 1."""
     import socket
+    import subprocess
     if not all_on_device0:
         import torch
         have = torch.cuda.device_count()
@@ -272,7 +293,7 @@ def launch_ranks(n: int, all_on_device0: bool = False):
     argv = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
             "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, argv)
+    sys.exit(subprocess.call(argv))
 
 
 def main():
@@ -294,6 +315,9 @@ def main():
                     help="N > 1: strong = the --n-prompts job split over the ranks (BASELINE config 5); weak = --n-prompts per rank")
     ap.add_argument("--no-weak-leg", action="store_true", help="N > 1, strong scaling: skip the weak-scaling leg (a 64-prompt job per rank) reported beside it")
     ap.add_argument("--ragged", action="store_true", help="N > 1: the ragged job (bench.ragged_caps: step caps 64..256 by prompt length) instead of equal caps")
+    ap.add_argument("--full", action="store_true", help="N = 1: also run the legs measured beside the headline (roofline, batched jobs, fine order, tolerance "
+                                                         "route, 768-step cap, bark-large, q4_0, few-slot jobs, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--dump-pcm", default=None, help="rank 0 writes the gathered PCM of the last step here (.npz; tests)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for the 1-GPU dry run)")
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="dry run of the N > 1 path on a single GPU (with --backend gloo)")
@@ -393,6 +417,9 @@ def main():
             assert len(gathered) == len(prompts) and int(counts.sum()) == sum(len(v) for v in gathered.values())
             if a.dump_pcm:
                 np.savez(a.dump_pcm, **{"p%03d" % i: v for i, v in gathered.items()})
+            if a.dump_outputs:
+                order = sorted(gathered)
+                dump_outputs(a.dump_outputs, {"pcm": np.concatenate([gathered[i] for i in order]), "sample_counts": counts})
             out = {
                 "metric": "audio-sec/sec (RTF), bark-small f16 greedy", "value": audio_total / dt, "unit": "audio-s/s",
                 "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1000.0 * dt / max(1, a.steps),
@@ -455,6 +482,14 @@ def main():
         "samples_settled_by_exact_path": agg["n_near_tie"],
         "prompts_per_s": world * a.steps / dt,
     }
+    if a.dump_outputs:
+        # what bark_generate_audio returned in the last timed step (the context keeps it until its next call)
+        dump_outputs(a.dump_outputs, {"pcm": ctx.audio_data(), "semantic_tokens": ctx.semantic_tokens(), "coarse_tokens": ctx.coarse_tokens(),
+                                      "fine_tokens": ctx.fine_tokens()})
+    if not a.full:
+        print(json.dumps(out))
+        ctx.free()
+        return
     # roofline.  Dominant kernel by time: gemv_ln_wg_kernel (LayerNorm-fused decode GEMV: QKV, FC and LM head = 25 of the 62 launches
     # of a step, ~37 % of it; profiles/).  Its largest per-layer instance is the FC product (4 E^2 f16 weights = 4.72 MB per launch).
     # `achieved` = algorithmic bytes / average launch duration, measured here with HIP events on the engine's stream over a graph of

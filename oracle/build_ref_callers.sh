@@ -15,15 +15,19 @@ OUT="$HERE/_ref"
 mkdir -p "$OUT"
 CXX="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="-std=c++17 -O1 -w -I$ROOT/include -I$REF/examples -L$ROOT/bark.cpp_amd/lib -lbark -lpthread -Wl,-rpath,\$ORIGIN/../../bark.cpp_amd/lib"
+pids=()
 newer() { [ ! -f "$1" ] || [ "$2" -nt "$1" ] || [ "$ROOT/include/bark.h" -nt "$1" ]; }
 if newer "$OUT/bark_main" "$REF/examples/main/main.cpp"; then
     $CXX "$REF/examples/main/main.cpp" "$REF/examples/common.cpp" $FLAGS -o "$OUT/bark_main" &
+    pids+=($!)
 fi
 if newer "$OUT/bark_quantize" "$REF/examples/quantize/main.cpp"; then
     $CXX "$REF/examples/quantize/main.cpp" $FLAGS -o "$OUT/bark_quantize" &
+    pids+=($!)
 fi
 if newer "$OUT/bark_server" "$REF/examples/server/server.cpp"; then
     $CXX "$REF/examples/server/server.cpp" "$REF/examples/common.cpp" -I"$REF/examples/server" $FLAGS -o "$OUT/bark_server" &
+    pids+=($!)
 fi
-wait
+for p in "${pids[@]}"; do wait "$p"; done      # a caller that fails to compile fails the build
 ls -la "$OUT"

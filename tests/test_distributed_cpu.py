@@ -99,8 +99,8 @@ def test_cpu_baseline_leg_reports_the_contract_keys(toy_model):
 
 
 def test_gpus_flag_starts_its_own_ranks_or_refuses(monkeypatch, capsys):
-    """`python bench.py --gpus N` is the N-rank job: without a launcher the process re-executes itself under torch.distributed.run with
-    --nproc-per-node N on 127.0.0.1; when --gpus disagrees with WORLD_SIZE, or the node shows fewer GPUs than N, it exits 2 and prints NO line
+    """`python bench.py --gpus N` is the N-rank job: without a launcher the process runs itself under torch.distributed.run with
+    --nproc-per-node N on 127.0.0.1 as its child and exits with the child's status; when --gpus disagrees with WORLD_SIZE, or the node shows fewer GPUs than N, it exits 2 and prints NO line
     (an N-GPU request must never produce an n_gpus = 1 record).  The plain two-rank command itself runs in the GPU suite
     (tests/test_gpu_parity.py::test_two_ranks_gather_the_single_process_pcm)."""
     import pytest
@@ -108,10 +108,10 @@ def test_gpus_flag_starts_its_own_ranks_or_refuses(monkeypatch, capsys):
     import bench
     seen = {}
 
-    def fake_execv(exe, argv):
-        seen["exe"], seen["argv"] = exe, list(argv)
-        raise SystemExit(0)
-    monkeypatch.setattr(os, "execv", fake_execv)
+    def fake_call(argv):
+        seen["argv"] = list(argv)
+        return 0
+    monkeypatch.setattr(subprocess, "call", fake_call)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4", "--steps", "2", "--backend", "gloo", "--all-ranks-on-device0"])
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)

@@ -8,7 +8,10 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 N=${1:-r06}
 mkdir -p $R/gpurun_out
 cd $R
-timeout 900 python bench.py --steps 3 --warmup 1 > gpurun_out/${N}_bench_small_n1.json 2> gpurun_out/${N}_bench.err
+# the bench line with every leg beside the headline (roofline, cpu_baseline, ...: what profiles/rNN_bench_small_n1.json holds) -> $OUT
+OUT=${OUT:-$R/profile_out}
+mkdir -p $OUT
+timeout 900 python bench.py --full --steps 3 --warmup 1 > $OUT/${N}_bench_small_n1.json 2> $OUT/${N}_bench.err
 timeout 300 python tools/lock_step_timeline.py small 640 > gpurun_out/${N}_lock_step_timeline.txt 2>&1; cp gpurun_out/lock_step_timeline.json gpurun_out/${N}_lock_step_timeline.json
 timeout 600 python tools/batch_throughput.py 256 small > gpurun_out/${N}_batch_throughput.txt 2>&1
 timeout 120 python tools/profile_codec.py > gpurun_out/${N}_codec_time.txt 2>&1
