@@ -37,6 +37,11 @@ class BarkHipRequestParams(C.Structure):
     _fields_ = [("temp", C.c_float), ("fine_temp", C.c_float), ("min_eos_p", C.c_float), ("n_steps_text_encoder", C.c_int32), ("seed", C.c_uint32)]
 
 
+class BarkHipSamplingFilter(C.Structure):
+    """struct bark_hip_sampling_filter (bark_mi355x.h): top-k / nucleus filter of the semantic and coarse samples (rule C8n); {0, 1.0}: off."""
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 class BarkHipStats(C.Structure):
     _fields_ = [
         ("t_load_us", C.c_int64), ("t_eval_us", C.c_int64), ("t_semantic_us", C.c_int64), ("t_coarse_us", C.c_int64),
@@ -76,6 +81,7 @@ EXPORTS = [
     "bark_hip_clone_context", "bark_hip_generate_audio_batch", "bark_hip_generate_batch", "bark_hip_generate_batch_seeded", "bark_hip_generate_batch_ex", "bark_hip_reserve_batch", "bark_hip_profile_lock_step", "bark_hip_batch_audio", "bark_hip_batch_tokens", "bark_hip_get_semantic_tokens", "bark_hip_get_coarse_tokens", "bark_hip_get_fine_tokens", "bark_hip_get_stats",
     "bark_hip_time_decode_step", "bark_hip_time_gemv", "bark_hip_time_slots", "bark_hip_time_fine_pass", "bark_hip_time_fine_passes", "bark_hip_describe", "bark_hip_set_fine_order", "bark_hip_load_model_on_device", "bark_hip_batcher_create_multi",
     "bark_hip_batcher_create", "bark_hip_batcher_create_ex", "bark_hip_batcher_submit", "bark_hip_batcher_submit_ex", "bark_hip_batcher_wait", "bark_hip_batcher_stats", "bark_hip_batcher_admitted", "bark_hip_batcher_free",
+    "bark_hip_set_sampling_filter", "bark_hip_generate_batch_filtered", "bark_hip_batcher_submit_filtered", "bark_hip_sample_rows_filtered", "bark_hip_time_sample_filter",
 ]
 
 
@@ -154,6 +160,13 @@ def load_library() -> C.CDLL:
     lib.bark_hip_batcher_submit.argtypes = [vp, C.c_char_p, C.c_uint32]
     lib.bark_hip_batcher_submit_ex.restype = C.c_int64
     lib.bark_hip_batcher_submit_ex.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams)]
+    lib.bark_hip_batcher_submit_filtered.restype = C.c_int64
+    lib.bark_hip_batcher_submit_filtered.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter)]
+    lib.bark_hip_set_sampling_filter.argtypes = [vp, C.c_int32, C.c_float]
+    lib.bark_hip_generate_batch_filtered.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter)]
+    lib.bark_hip_sample_rows_filtered.argtypes = [vp, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]
+    lib.bark_hip_time_sample_filter.restype = C.c_double
+    lib.bark_hip_time_sample_filter.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_float, C.c_int, C.c_int]
     lib.bark_hip_batcher_wait.argtypes = [vp, C.c_int64, fp, C.c_int]
     lib.bark_hip_batcher_stats.restype = None
     lib.bark_hip_batcher_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -357,12 +370,18 @@ class BarkContext:
         if self._lib.bark_hip_reserve_batch(self._h, slots) != 0:
             raise RuntimeError("bark_hip_reserve_batch failed")
 
-    def generate_batch(self, texts, seeds=None, params=None) -> list:
-        """In-engine batching (bark_hip_generate_batch[_seeded|_ex]): returns one dict per utterance (or None if it failed).
-        params: one BarkHipRequestParams per utterance (request_params(...))."""
+    def generate_batch(self, texts, seeds=None, params=None, filters=None) -> list:
+        """In-engine batching (bark_hip_generate_batch[_seeded|_ex|_filtered]): returns one dict per utterance (or None if it failed).
+        params: one BarkHipRequestParams per utterance (request_params(...)); filters: one (top_k, top_p) pair or BarkHipSamplingFilter per
+        utterance (bark_hip_generate_batch_filtered; None: the context's filter)."""
         n = len(texts)
         ts = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
-        if params is not None:
+        if filters is not None:
+            assert len(filters) == n and seeds is None
+            fl = (BarkHipSamplingFilter * n)(*[f if isinstance(f, BarkHipSamplingFilter) else BarkHipSamplingFilter(int(f[0]), float(f[1])) for f in filters])
+            ps = (BarkHipRequestParams * n)(*params) if params is not None else None
+            good = self._lib.bark_hip_generate_batch_filtered(self._h, ts, n, ps, fl)
+        elif params is not None:
             assert len(params) == n and seeds is None
             good = self._lib.bark_hip_generate_batch_ex(self._h, ts, n, (BarkHipRequestParams * n)(*params))
         elif seeds is None:
@@ -424,6 +443,33 @@ class BarkContext:
         s = BarkHipStats()
         self._lib.bark_hip_get_stats(self._h, C.byref(s))
         return s.as_dict()
+
+    def set_sampling_filter(self, top_k: int = 0, top_p: float = 1.0):
+        """Top-k / nucleus filter of the semantic and coarse samples (rule C8n; top_k 0 and top_p 1.0: off).  Greedy stages are not filtered."""
+        if self._lib.bark_hip_set_sampling_filter(self._h, int(top_k), float(top_p)) != 0:
+            raise ValueError(f"bark_hip_set_sampling_filter rejected top_k={top_k}, top_p={top_p} (top_k >= 0, 0 < top_p <= 1)")
+
+    def sample_rows_filtered(self, logits, temp, top_k, top_p, u):
+        """Kernel-level hook (bark_hip_sample_rows_filtered): rows of logits [n_rows, n] through the decode loop's filter + sampler launches;
+        per-row temp / top_k / top_p / uniform draw u.  Returns (ids int32 [n_rows], eos_p float32 [n_rows])."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        nr, n = lg.shape
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(temp, np.float32), (nr,)))
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, np.int32), (nr,)))
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(top_p, np.float32), (nr,)))
+        uu = np.ascontiguousarray(np.broadcast_to(np.asarray(u, np.float64), (nr,)))
+        ids = np.zeros(nr, np.int32)
+        eos = np.zeros(nr, np.float32)
+        if self._lib.bark_hip_sample_rows_filtered(self._h, lg.ctypes.data, nr, n, t.ctypes.data, k.ctypes.data, p.ctypes.data, uu.ctypes.data,
+                                                   ids.ctypes.data, eos.ctypes.data) != 0:
+            raise RuntimeError("bark_hip_sample_rows_filtered failed")
+        return ids, eos
+
+    def time_sample_filter(self, n: int, n_slots: int, top_k: int, top_p: float, peaked: bool, iters: int) -> float:
+        us = self._lib.bark_hip_time_sample_filter(self._h, n, n_slots, int(top_k), float(top_p), 1 if peaked else 0, iters)
+        if us < 0:
+            raise RuntimeError("bark_hip_time_sample_filter failed")
+        return us
 
     def set_fine_order(self, order: int):
         """0: default policy (C1 for generate_audio / stage calls, C1m inside lock-step jobs and fine_many); 1: C1 everywhere; 2: C1m everywhere."""
@@ -501,8 +547,15 @@ class Batcher:
         except Exception:
             pass
 
-    def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None) -> int:
-        if params is not None:
+    def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None) -> int:
+        """top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
+        neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does."""
+        if top_k is not None or top_p is not None:
+            flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
+            if params is None:
+                params = self._ctx[0].request_params(seed=int(seed))
+            t = self._lib.bark_hip_batcher_submit_filtered(self._b, text.encode("utf-8"), C.byref(params), C.byref(flt))
+        elif params is not None:
             t = self._lib.bark_hip_batcher_submit_ex(self._b, text.encode("utf-8"), C.byref(params))
         else:
             t = self._lib.bark_hip_batcher_submit(self._b, text.encode("utf-8"), seed)

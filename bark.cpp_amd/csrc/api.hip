@@ -284,6 +284,31 @@ int bark_hip_generate_batch_ex(struct bark_context * bctx, const char * const * 
     for (int i = 0; i < n; i++) if (!texts[i]) return -1;
     return guarded("bark_hip_generate_batch_ex", -1, [&] { return engine_generate_batch(bctx, texts, n, nullptr, per_utterance); });
 }
+int bark_hip_generate_batch_filtered(struct bark_context * bctx, const char * const * texts, int n, const struct bark_hip_request_params * per_utterance,
+                                     const struct bark_hip_sampling_filter * filters) {
+    if (!bctx || !texts || n <= 0) return -1;
+    for (int i = 0; i < n; i++) if (!texts[i]) return -1;
+    if (filters) for (int i = 0; i < n; i++) if (!filter_valid(filters[i])) return -1;
+    return guarded("bark_hip_generate_batch_filtered", -1, [&] { return engine_generate_batch(bctx, texts, n, nullptr, per_utterance, nullptr, filters); });
+}
+int bark_hip_set_sampling_filter(struct bark_context * bctx, int32_t top_k, float top_p) {
+    const bark_hip_sampling_filter f{top_k, top_p};
+    if (!bctx || !filter_valid(f)) return -1;
+    return guarded("bark_hip_set_sampling_filter", -1, [&] {
+        if (filter_on(f) != filter_on(bctx->filter)) engine_invalidate_graphs(bctx);       // the decode graphs hold the filter launch or not
+        bctx->filter = f;
+        return 0;
+    });
+}
+int bark_hip_sample_rows_filtered(struct bark_context * bctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k,
+                                  const float * top_p, const double * u, int32_t * out_ids, float * out_eos_p) {
+    if (!bctx || !logits || !temp || !top_k || !top_p || !u || !out_ids || n_rows <= 0) return -1;
+    return guarded("bark_hip_sample_rows_filtered", -1, [&] { engine_sample_rows_filtered(bctx, logits, n_rows, n, temp, top_k, top_p, u, out_ids, out_eos_p); return 0; });
+}
+double bark_hip_time_sample_filter(struct bark_context * bctx, int n, int n_slots, int32_t top_k, float top_p, int peaked, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_sample_filter", -1.0, [&] { return engine_time_sample_filtered(bctx, n, n_slots, top_k, top_p, peaked, iters); });
+}
 int bark_hip_profile_lock_step(struct bark_context * bctx, int which, int n_slots, int ctx, int reps, char * json_out, int capacity) {
     if (!bctx || !json_out || capacity < 2) return -1;
     return guarded("bark_hip_profile_lock_step", -1, [&] {

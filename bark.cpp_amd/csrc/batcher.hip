@@ -25,10 +25,13 @@
 using namespace barkhip;
 
 struct bark_hip_batcher {
-    struct Req { std::string text; bark_hip_request_params rp{}; std::vector<float> pcm; bool done = false, ok = false; };
+    struct Req { std::string text; bark_hip_request_params rp{}; bark_hip_sampling_filter flt{0, 1.0f}; std::vector<float> pcm; bool done = false, ok = false; };
     bark_context * ctx = nullptr;                          // worker 0's context (the caller's); request defaults are read from it
     std::vector<bark_context *> ctxs;                      // one per worker; ctxs[1 ..] are clones owned by the batcher ...
     bool owns_workers = true;                              // ... unless the caller brought every context itself (bark_hip_batcher_create_multi: one per GPU)
+    // the context's top-k / nucleus filter, copied when the collector is made (the workers own the contexts from then on): what a request without a
+    // filter of its own gets, read under `mu` at submit time - nothing is ever written into a running worker's context
+    bark_hip_sampling_filter default_filter{0, 1.0f};
     int max_batch = 32;
     std::chrono::microseconds max_wait{2000};
     std::mutex mu;
@@ -56,21 +59,21 @@ struct bark_hip_batcher {
             while (!queue.empty() && (int) batch.size() < job_cap) { batch.push_back(queue.front().second); queue.pop_front(); }
             if (batch.empty()) continue;                         // another worker took what was there
             lk.unlock();
-            std::vector<const char *> texts; std::vector<bark_hip_request_params> rps;
-            for (auto & r : batch) { texts.push_back(r->text.c_str()); rps.push_back(r->rp); }
+            std::vector<const char *> texts; std::vector<bark_hip_request_params> rps; std::vector<bark_hip_sampling_filter> flts;
+            for (auto & r : batch) { texts.push_back(r->text.c_str()); rps.push_back(r->rp); flts.push_back(r->flt); }
             // continuous admission: requests that arrive while the job's semantic stage has free slots join it (engine_generate_batch asks here)
             BatchAdmit admit;
             admit.max_job = job_cap;
-            admit.next = [&](std::string & text, bark_hip_request_params & rp) {
+            admit.next = [&](std::string & text, bark_hip_request_params & rp, bark_hip_sampling_filter & flt) {
                 std::lock_guard<std::mutex> g(mu);
                 if (queue.empty() || (int) batch.size() >= job_cap) return false;
                 batch.push_back(queue.front().second); queue.pop_front();
-                text = batch.back()->text; rp = batch.back()->rp;
+                text = batch.back()->text; rp = batch.back()->rp; flt = batch.back()->flt;
                 n_admitted++;
                 return true;
             };
             bool failed = false;
-            try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit); }
+            try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit, flts.data()); }
             catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: batch failed: %s\n", e.what()); failed = true; }
             lk.lock();
             for (size_t i = 0; i < batch.size(); i++) {
@@ -91,6 +94,7 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create_ex(struct bark_contex
     std::unique_ptr<bark_hip_batcher> b(new bark_hip_batcher());
     try {
         b->ctx = bctx; b->max_batch = max_batch; b->max_wait = std::chrono::microseconds((int64_t) max_wait_ms * 1000);
+        b->default_filter = bctx->filter;
         b->ctxs.push_back(bctx);
         for (int i = 1; i < n_streams; i++) {
             b->ctxs.push_back(engine_clone(bctx, (uint32_t) i));
@@ -124,6 +128,7 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create_multi(struct bark_con
     std::unique_ptr<bark_hip_batcher> b(new bark_hip_batcher());
     try {
         b->ctx = ctxs[0]; b->max_batch = max_batch; b->max_wait = std::chrono::microseconds((int64_t) max_wait_ms * 1000);
+        b->default_filter = ctxs[0]->filter;
         b->owns_workers = false;
         for (int i = 0; i < n_ctx; i++) b->ctxs.push_back(ctxs[i]);
         for (bark_context * c : b->ctxs) engine_reserve_batch(c, std::min(max_batch, 64));
@@ -141,11 +146,12 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create(struct bark_context *
     return bark_hip_batcher_create_ex(bctx, max_batch, max_wait_ms, 1);
 }
 
-static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp) {
+static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp, const bark_hip_sampling_filter * flt = nullptr) {
     auto r = std::make_shared<bark_hip_batcher::Req>();
     r->text = text; r->rp = rp;
     std::lock_guard<std::mutex> lk(b->mu);
     if (b->stop) return -1;
+    r->flt = flt ? *flt : b->default_filter;
     const int64_t t = b->next_ticket++;
     b->tickets[t] = r;
     b->queue.emplace_back(t, r);
@@ -164,6 +170,11 @@ BARK_API int64_t bark_hip_batcher_submit(struct bark_hip_batcher * b, const char
 BARK_API int64_t bark_hip_batcher_submit_ex(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params) {
     if (!b || !text) return -1;
     return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0));
+}
+BARK_API int64_t bark_hip_batcher_submit_filtered(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                                  const struct bark_hip_sampling_filter * filter) {
+    if (!b || !text || (filter && !filter_valid(*filter))) return -1;
+    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter);
 }
 
 BARK_API int bark_hip_batcher_wait(struct bark_hip_batcher * b, int64_t ticket, float * pcm, int capacity) {

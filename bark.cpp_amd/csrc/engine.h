@@ -105,6 +105,10 @@ struct bark_context {
     barkhip::StepState * d_state = nullptr;
     double * d_u = nullptr;                             // uniform draws for on-device multinomial sampling (8192)
     bool host_sampling = false;                         // BARK_HIP_HOST_SAMPLING=1: sample temp > 0 on the host (A/B path)
+    // top-k / nucleus filter of the semantic and coarse samples (C8n, bark_hip_set_sampling_filter); {0, 1}: off.  The decode graphs read the
+    // settings from d_filter (uploaded at the start of a stage), so only switching the filter on or off needs fresh graphs.
+    bark_hip_sampling_filter filter{0, 1.0f};
+    int32_t * d_filter = nullptr;                       // [0]: top_k, [1]: top_p (float bits)
     uint16_t * d_gelu_lut = nullptr;
     int max_E = 0, max_H = 0, P = 1024;
     // codec scratch (grown on demand)
@@ -130,7 +134,8 @@ struct bark_context {
         float * ps = nullptr;                            // [cap][max_H][4][P] partial scores per slot (few-slot lock steps: QKV kernel -> attn_fused_ps_kernel)
         double * u = nullptr;                            // [cap][8192] uniform draws of the slots' own generators (temp > 0)
         size_t ld_logits = 0;
-        float * slot_par = nullptr;                      // the slots' own temperatures [cap] and min_eos_p [cap] (bark_hip_request_params)
+        float * slot_par = nullptr;                      // the slots' own temperatures [cap], min_eos_p [cap] (bark_hip_request_params) and top_p [cap]
+        int32_t * slot_top_k = nullptr;                  // the slots' own top_k [cap] (bark_hip_sampling_filter)
         // pinned host memory (hipHostMalloc, freed by the context): where the sampled ids [cap][2048] and the states [cap] of the live slots land at
         // a poll / window end, and the staging rows of the states uploaded at a window start
         int32_t * h_ids = nullptr; barkhip::StepState * h_state = nullptr, * h_state_in = nullptr;
@@ -139,6 +144,7 @@ struct bark_context {
         int32_t * pf_tokens = nullptr; barkhip::SeqTab * pf_tab = nullptr;
     } batch;
     std::vector<float> h_slot_par;                      // host mirror of batch.slot_par
+    std::vector<int32_t> h_slot_top_k;                  // host mirror of batch.slot_top_k
     std::vector<std::pair<std::string, hipEvent_t>> * step_marks = nullptr;      // engine_profile_lock_step: events behind the launch sites of a lock step
     std::map<int, hipGraphExec_t> batch_graphs;         // captured lock steps by (model, active slots, kinds of sampling among them)
     // fine windows of several utterances in one forward pass (engine_fine_many): rows = cap * 1024
@@ -191,10 +197,18 @@ bool engine_generate(bark_context * ctx, const char * text);
 // seeds: one std::mt19937 seed per utterance (temp > 0); nullptr: drawn from the context's generator, in order.  Returns #ok
 // Continuous admission: while the semantic stage of a job has free slots and nobody of the job waits for them, next() may hand over further
 // requests (false: none pending); they join the job - results are appended behind the n given ones - up to max_job utterances in total.
-struct BatchAdmit { std::function<bool(std::string & text, bark_hip_request_params & rp)> next; int max_job = 0; };
-// rps: per-utterance parameters (nullptr: the context's for everyone); seeds override rps[i].seed when both are given
+struct BatchAdmit { std::function<bool(std::string & text, bark_hip_request_params & rp, bark_hip_sampling_filter & flt)> next; int max_job = 0; };
+// rps: per-utterance parameters (nullptr: the context's for everyone); seeds override rps[i].seed when both are given;
+// flts: per-utterance top-k / nucleus filters (nullptr: the context's for everyone)
 int  engine_generate_batch(bark_context * ctx, const char * const * texts, int n, const uint32_t * seeds, const bark_hip_request_params * rps = nullptr,
-                           const BatchAdmit * admit = nullptr);
+                           const BatchAdmit * admit = nullptr, const bark_hip_sampling_filter * flts = nullptr);
+// checks a filter (top_k >= 0, 0 < top_p <= 1); false on a bad one
+bool filter_valid(const bark_hip_sampling_filter & f);
+inline bool filter_on(const bark_hip_sampling_filter & f) { return f.top_k > 0 || f.top_p < 1.0f; }
+// the decode loop's filter + sampler launches on n_rows caller rows of n logits (bark_hip_sample_rows_filtered): ids, eos_p = p_{n-1}
+void engine_sample_rows_filtered(bark_context * ctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k, const float * top_p,
+                                 const double * u, int32_t * out_ids, float * out_eos_p);
+double engine_time_sample_filtered(bark_context * ctx, int n, int n_rows, int top_k, float top_p, int peaked, int iters);
 void engine_reserve_batch(bark_context * ctx, int slots);          // fixes the lock-step capacity (otherwise the first batch call does)
 
 double engine_time_decode_step(bark_context * ctx, int which, int ctxlen, int iters, double * bytes_per_step);

@@ -227,7 +227,9 @@ void run_sample(bark_context * c, const StageCfg & s, int n_past_add, bool presc
     const GptModel & m = c->gpt[s.which];
     a.wte = m.wte[0]; a.wte_q = m.wte_q[0]; a.wpe = m.wpe; a.E = m.hp.n_embd; a.n_in = m.hp.n_in_vocab; a.P = c->P; a.x = c->x;
     BARK_TRACE_SET(c, a, 16);
-    launch_sample_greedy(c->stream, a);
+    // top-k / nucleus filter (C8n): on the raw logits, in front of the multinomial sampler; its settings come from d_filter (upload_filter)
+    if (!prescaled && s.temp > 0.0f && filter_on(c->filter)) launch_sample_filtered(c->stream, a, c->d_filter, reinterpret_cast<const float *>(c->d_filter + 1));
+    else launch_sample_greedy(c->stream, a);
 }
 
 // [embed(state) ->] layers -> LM head [-> greedy sample + embedding of the sampled token]
@@ -286,6 +288,42 @@ void decode_steps_greedy(bark_context * c, const StageCfg & s, int n, int n_past
 }
 
 // ---- host-side sampling (temp > 0, or settling a near tie): bark.cpp:184-270 -------------------------
+// C8n, restated with a sort: the ids the top-k / nucleus filter removes become -inf (probability exactly 0)
+void filter_host(std::vector<float> & l, int32_t top_k, float top_p) {
+    const int n = (int) l.size();
+    if (n == 0 || (top_k <= 0 && !(top_p < 1.0f))) return;
+    std::vector<int> ord((size_t) n);
+    for (int i = 0; i < n; i++) ord[(size_t) i] = i;
+    std::sort(ord.begin(), ord.end(), [&](int a, int b) { return l[(size_t) a] > l[(size_t) b] || (l[(size_t) a] == l[(size_t) b] && a < b); });
+    int J = n;
+    if (top_p < 1.0f) {
+        float mx = -INFINITY;
+        for (float v : l) mx = std::max(mx, v);
+        std::vector<uint64_t> w((size_t) n);
+        uint64_t S = 0;
+        for (int i = 0; i < n; i++) { const float e = (float) exp((double) (l[(size_t) i] - mx)); w[(size_t) i] = (uint64_t) std::floor((double) e * 1099511627776.0); S += w[(size_t) i]; }
+        // W <= top_p * S, exactly: top_p = fm 2^-sh, so W <= floor(fm S / 2^sh)
+        int ex = 0; const double fr = std::frexp((double) top_p, &ex);             // top_p = fr 2^ex, fr in [0.5, 1)
+        const unsigned __int128 fm = (unsigned __int128) std::ldexp(fr, 24);         // 24 significant bits (exact for every float)
+        const int sh = 24 - ex;
+        const unsigned __int128 prod = fm * (unsigned __int128) S;
+        const uint64_t T = sh >= 128 ? 0 : (uint64_t) (prod >> sh);
+        uint64_t W = 0;
+        J = 0;
+        for (int j = 0; j < n; j++) {
+            if (j > 0 && W > T) break;
+            J = j + 1;
+            W += w[(size_t) ord[(size_t) j]];
+        }
+    }
+    int F = J;
+    if (top_k > 0 && top_k < J) {
+        const float v = l[(size_t) ord[(size_t) top_k - 1]];
+        F = top_k;
+        while (F < J && l[(size_t) ord[(size_t) F]] >= v) F++;                   // ties with the top_k-th logit stay
+    }
+    for (int j = F; j < n; j++) l[(size_t) ord[(size_t) j]] = -INFINITY;
+}
 void softmax_host(std::vector<float> & l) {
     float mx = -INFINITY;
     for (float v : l) mx = std::max(mx, v);
@@ -293,7 +331,7 @@ void softmax_host(std::vector<float> & l) {
     for (float & v : l) { v = (float) exp((double) (v - mx)); sum += v; }
     for (float & v : l) v /= sum;
 }
-int sample_host(std::vector<float> & l, std::mt19937 & rng, float temp, float * eos_p) {
+int sample_host(std::vector<float> & l, std::mt19937 & rng, float temp, float * eos_p, const bark_hip_sampling_filter * flt) {
     if (temp == 0.0f) {                                  // gpt_argmax_sample
         for (float & v : l) v /= 0.7f;
         softmax_host(l);
@@ -302,6 +340,7 @@ int sample_host(std::vector<float> & l, std::mt19937 & rng, float temp, float * 
         for (int i = 0; i < (int) l.size(); i++) if (l[(size_t) i] > mx) { mx = l[(size_t) i]; best = i; }
         return best;
     }
+    if (flt) filter_host(l, flt->top_k, flt->top_p);     // C8n: on the untempered logits
     for (float & v : l) v /= temp;                       // gpt_multinomial_sample
     softmax_host(l);
     std::discrete_distribution<int32_t> dist(l.begin(), l.end());
@@ -330,6 +369,13 @@ void upload_uniforms(bark_context * c, int n) {
     HIP_OK(hipStreamSynchronize(c->stream));
 }
 void consume_uniforms(bark_context * c, int n_used) { c->rng.discard(2ull * (unsigned long long) n_used); }
+// the context's top-k / nucleus settings -> d_filter, read by the filter launches of run_sample (also from the captured decode graphs)
+void upload_filter(bark_context * c) {
+    int32_t v[2] = {c->filter.top_k, 0};
+    memcpy(&v[1], &c->filter.top_p, 4);
+    HIP_OK(hipMemcpyAsync(c->d_filter, v, sizeof(v), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+}
 
 void progress(bark_context * c, bark_encoding_step step, int pct) {
     if (c->params.progress_callback) c->params.progress_callback(c, step, pct, c->params.progress_callback_user_data);
@@ -373,6 +419,50 @@ int engine_gpt_eval(bark_context * c, int which, const int32_t * tokens, int n_t
     HIP_OK(hipMemcpyAsync(logits, c->logits, (size_t) n_out * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return n_past + N;
+}
+
+bool filter_valid(const bark_hip_sampling_filter & f) { return f.top_k >= 0 && f.top_p > 0.0f && f.top_p <= 1.0f; }      // NaN fails both
+
+// kernel-level hook: the decode loop's filter + sampler launches (launch_sample_filtered, as in a lock step with per-slot settings) on caller rows,
+// in chunks of up to 4096 rows; row r is slot r of the chunk with a fresh state (step 0 reads u[r])
+void engine_sample_rows_filtered(bark_context * c, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k, const float * top_p,
+                                 const double * u, int32_t * out_ids, float * out_eos_p) {
+    if (n_rows <= 0 || n < 1 || n > 12288) throw std::runtime_error("sample_rows_filtered: n must be in 1..12288");
+    for (int r = 0; r < n_rows; r++)
+        if (!(temp[r] >= 0.0f) || !filter_valid(bark_hip_sampling_filter{top_k[r], top_p[r]})) throw std::runtime_error("sample_rows_filtered: bad settings");
+    HIP_OK(hipSetDevice(c->device));
+    const int chunk = std::min(n_rows, 4096);
+    struct Buf { void * p = nullptr; ~Buf() { if (p) (void) hipFree(p); } };
+    Buf b_l, b_t, b_k, b_p, b_u, b_st, b_ids, b_eos;
+    HIP_OK(hipMalloc(&b_l.p, (size_t) chunk * n * 4)); HIP_OK(hipMalloc(&b_t.p, (size_t) chunk * 4)); HIP_OK(hipMalloc(&b_k.p, (size_t) chunk * 4));
+    HIP_OK(hipMalloc(&b_p.p, (size_t) chunk * 4)); HIP_OK(hipMalloc(&b_u.p, (size_t) chunk * 8)); HIP_OK(hipMalloc(&b_st.p, (size_t) chunk * sizeof(StepState)));
+    HIP_OK(hipMalloc(&b_ids.p, (size_t) chunk * 4)); HIP_OK(hipMalloc(&b_eos.p, (size_t) chunk * 4));
+    std::vector<StepState> sts((size_t) chunk, fresh_state());
+    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int nb = std::min(chunk, n_rows - r0);
+        hipStream_t st = c->stream;
+        HIP_OK(hipMemcpyAsync(b_l.p, logits + (size_t) r0 * n, (size_t) nb * n * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_t.p, temp + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_k.p, top_k + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_p.p, top_p + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_u.p, u + r0, (size_t) nb * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_st.p, sts.data(), (size_t) nb * sizeof(StepState), hipMemcpyHostToDevice, st));
+        SampleArgs a;
+        { static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0; a.force_exact = force_exact; }
+        a.logits = (const float *) b_l.p; a.n = n; a.mode = 0; a.eos_token = -1; a.min_eos_p = 2.0f; a.token_base = 0; a.n_past_add = 0;
+        a.out_tokens = (int32_t *) b_ids.p; a.eos_trace = (float *) b_eos.p; a.st = (StepState *) b_st.p;
+        a.nbatch = nb; a.ld_logits = n; a.out_stride = 1; a.u = (const double *) b_u.p; a.u_stride = 1;
+        a.slot_temp = (const float *) b_t.p; a.x = nullptr;
+        a.kinds = 0;
+        for (int r = r0; r < r0 + nb; r++) {
+            a.kinds |= temp[r] > 0.0f ? 2 : 1;
+            if (temp[r] > 0.0f && filter_on(bark_hip_sampling_filter{top_k[r], top_p[r]})) a.kinds |= 4;
+        }
+        launch_sample_filtered(st, a, (const int32_t *) b_k.p, (const float *) b_p.p);
+        HIP_OK(hipMemcpyAsync(out_ids + r0, b_ids.p, (size_t) nb * 4, hipMemcpyDeviceToHost, st));
+        if (out_eos_p) HIP_OK(hipMemcpyAsync(out_eos_p + r0, b_eos.p, (size_t) nb * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
 }
 
 namespace detail {
@@ -426,6 +516,7 @@ std::vector<int32_t> engine_semantic(bark_context * c, const std::vector<int32_t
     set_state(c, st);
     const bool greedy = p.temp == 0.0f || !c->host_sampling;      // "greedy" == sampled on the device (argmax or multinomial)
     if (p.temp != 0.0f && greedy) upload_uniforms(c, n_steps);
+    if (p.temp != 0.0f && greedy && filter_on(c->filter)) upload_filter(c);
     const int N = run_prefill(c, m, 513, true);
     run_lm_head(c, m, c->x + (size_t) (N - 1) * m.hp.n_embd, s.lm_row0, s.lm_rows, 0);
     if (greedy) {
@@ -463,7 +554,7 @@ std::vector<int32_t> engine_semantic(bark_context * c, const std::vector<int32_t
             }
             std::vector<float> l = fetch_logits(c, (size_t) s.lm_rows);
             float eos_p = 0.f;
-            const int next = sample_host(l, c->rng, p.temp, &eos_p);
+            const int next = sample_host(l, c->rng, p.temp, &eos_p, filter_on(c->filter) ? &c->filter : nullptr);
             c->stats.n_sample_semantic++;
             if (eos_trace) eos_trace->push_back(eos_p);
             progress(c, SEMANTIC, 100 * (i + 1) / std::max(1, p.n_steps_text_encoder));
@@ -493,6 +584,7 @@ std::vector<int32_t> engine_coarse(bark_context * c, const std::vector<int32_t> 
     const int n_windows = (int) ceilf((float) n_steps / p.sliding_window_size);
     const bool greedy = p.temp == 0.0f || !c->host_sampling;
     if (p.temp != 0.0f && greedy) upload_uniforms(c, n_steps);
+    if (p.temp != 0.0f && greedy && filter_on(c->filter)) upload_filter(c);
     std::vector<int32_t> out;            // offset ids, as fed back into the model
     std::vector<int32_t> cached;         // token ids whose K/V rows are valid in the cache (prefix reuse)
     const bool reuse_prefix = !(crosscheck_mask() & 8);
@@ -566,7 +658,7 @@ std::vector<int32_t> engine_coarse(bark_context * c, const std::vector<int32_t> 
                     n_past += 1;
                 }
                 std::vector<float> l = fetch_logits(c, (size_t) s.lm_rows);
-                int next = sample_host(l, c->rng, p.temp, nullptr);
+                int next = sample_host(l, c->rng, p.temp, nullptr, filter_on(c->filter) ? &c->filter : nullptr);
                 next += s.lm_row0 + parity * s.lm_rows;
                 out.push_back(next);
                 step_idx += 1;

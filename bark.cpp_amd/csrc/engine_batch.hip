@@ -79,8 +79,11 @@ void ensure_batch(bark_context * c, int B) {
     bb.sc = dev_alloc<float>(c, (size_t) B * c->max_H * c->P);
     if (few_slots_max(1) > 0) bb.ps = dev_alloc<float>(c, (size_t) std::min(B, few_slots_max(1)) * c->max_H * 4 * c->P);
     if (c->any_q4) { bb.att32 = dev_alloc<float>(c, (size_t) B * E); bb.h32 = dev_alloc<float>(c, (size_t) B * 4 * E); }
-    bb.slot_par = dev_alloc<float>(c, (size_t) 2 * B);               // [0, B): temperatures, [B, 2 B): min_eos_p
-    c->h_slot_par.assign((size_t) 2 * B, 0.0f);
+    bb.slot_par = dev_alloc<float>(c, (size_t) 3 * B);               // [0, B): temperatures, [B, 2 B): min_eos_p, [2 B, 3 B): top_p
+    c->h_slot_par.assign((size_t) 3 * B, 0.0f);
+    for (int b = 0; b < B; b++) c->h_slot_par[(size_t) 2 * B + b] = 1.0f;
+    bb.slot_top_k = dev_alloc<int32_t>(c, (size_t) B);
+    c->h_slot_top_k.assign((size_t) B, 0);
     // pinned landing zone of the per-window / per-poll read-back (ids of all slots + their states): read_back() below
     HIP_OK(hipHostMalloc((void **) &bb.h_ids, (size_t) B * 2048 * sizeof(int32_t), hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **) &bb.h_state, (size_t) B * sizeof(StepState), hipHostMallocDefault));
@@ -108,12 +111,18 @@ void read_back(bark_context * c, int B, std::vector<int32_t> * ids, std::vector<
 void upload_slot_params(bark_context * c) {
     bark_context::Batch & bb = c->batch;
     HIP_OK(hipMemcpyAsync(bb.slot_par, c->h_slot_par.data(), c->h_slot_par.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(bb.slot_top_k, c->h_slot_top_k.data(), c->h_slot_top_k.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
 }
-// 1: greedy slots among [slot0, slot0 + n), 2: sampled slots among them
+// 1: greedy slots among [slot0, slot0 + n), 2: sampled slots among them, 4: sampled slots with a top-k / nucleus filter among them
 int slot_kinds(const bark_context * c, int slot0, int n) {
     int k = 0;
-    for (int b = slot0; b < slot0 + n; b++) k |= c->h_slot_par[(size_t) b] > 0.0f ? 2 : 1;
+    const size_t cap = (size_t) c->batch.cap;
+    for (int b = slot0; b < slot0 + n; b++) {
+        const bool sampled = c->h_slot_par[(size_t) b] > 0.0f;
+        k |= sampled ? 2 : 1;
+        if (sampled && (c->h_slot_top_k[(size_t) b] > 0 || c->h_slot_par[2 * cap + (size_t) b] < 1.0f)) k |= 4;
+    }
     return k;
 }
 // the sampler's arguments for slots [slot0, slot0 + nb) of the batch
@@ -132,6 +141,12 @@ SampleArgs slot_sample_args(bark_context * c, const StageCfg & s, const bark_con
     sa.kinds = slot_kinds(c, first, nb);
     sa.wte = m.wte[0]; sa.wte_q = m.wte_q[0]; sa.wpe = m.wpe; sa.E = m.hp.n_embd; sa.n_in = m.hp.n_in_vocab; sa.P = c->P; sa.x = bb.x + (size_t) slot0 * m.hp.n_embd;
     return sa;
+}
+
+// the sampler launches of slots sa.st[0 .. nbatch): kinds & 4 puts the filter (C8n) in front, with the slots' own top_k / top_p
+void launch_slot_sampler(bark_context * c, hipStream_t st, const SampleArgs & sa) {
+    const int first = (int) (sa.st - c->batch.state);
+    launch_sample_filtered(st, sa, c->batch.slot_top_k + first, c->batch.slot_par + 2 * (size_t) c->batch.cap + first);
 }
 
 void set_slot_state(bark_context * c, int slot, const StepState & st) {
@@ -223,7 +238,7 @@ void enqueue_batch_step(bark_context * c, const StageCfg & s, int B, const bark_
     h.epi = EPI_LOGITS; h.out = bb.logits; h.ld_out = (int) bb.ld_logits; h.parity_rows = s.parity_rows; h.st = bb.state;
     product(h, m.lnf_g, m.lnf_b);
     mark("lnf+lm_head");
-    launch_sample_greedy(st, slot_sample_args(c, s, bb, 0, B, 1));
+    launch_slot_sampler(c, st, slot_sample_args(c, s, bb, 0, B, 1));
     mark("sample+embed");
 }
 
@@ -295,7 +310,7 @@ void batch_prefill_and_sample(bark_context * c, const StageCfg & s, int slot, co
     h.x_f32 = c->x + (size_t) (N - 1) * m.hp.n_embd; h.ln_g = m.lnf_g; h.ln_b = m.lnf_b; h.epi = EPI_LOGITS;
     h.out = bb.logits + bb.ld_logits * (size_t) slot; h.ld_out = (int) bb.ld_logits; h.parity_rows = s.parity_rows; h.st = bb.state + slot;
     launch_linear(c->stream, h);
-    launch_sample_greedy(c->stream, slot_sample_args(c, s, bb, slot, 1, N));
+    launch_slot_sampler(c, c->stream, slot_sample_args(c, s, bb, slot, 1, N));
 }
 
 
@@ -353,7 +368,7 @@ void batch_prefill_many(bark_context * c, const StageCfg & s, const std::vector<
         h.x_f32 = bb.pf_x + ((size_t) z * seq + (size_t) (N - 1)) * E; h.ln_g = m.lnf_g; h.ln_b = m.lnf_b; h.epi = EPI_LOGITS;
         h.out = bb.logits + bb.ld_logits * (size_t) slot; h.ld_out = (int) bb.ld_logits; h.parity_rows = s.parity_rows; h.st = bb.state + slot;
         launch_linear(st, h);
-        launch_sample_greedy(st, slot_sample_args(c, s, bb, slot, 1, N));
+        launch_slot_sampler(c, st, slot_sample_args(c, s, bb, slot, 1, N));
     }
     HIP_OK(hipStreamSynchronize(st));                           // tok / tab / sts are stack objects
 }
@@ -463,7 +478,7 @@ void engine_profile_lock_step(bark_context * c, int which, int B, int ctxlen, in
     HIP_OK(hipMemsetAsync(bb.x, 0, (size_t) B * m.hp.n_embd * 4, c->stream));
     HIP_OK(hipMemsetAsync(bb.kc[which], 0, bb.slot_stride[which] * (size_t) B * 4, c->stream));
     HIP_OK(hipMemsetAsync(bb.vc[which], 0, bb.slot_stride[which] * (size_t) B * 4, c->stream));
-    for (int b = 0; b < B; b++) { c->h_slot_par[(size_t) b] = 0.0f; c->h_slot_par[(size_t) bb.cap + b] = 0.2f; }
+    for (int b = 0; b < B; b++) { c->h_slot_par[(size_t) b] = 0.0f; c->h_slot_par[(size_t) bb.cap + b] = 0.2f; c->h_slot_par[2 * (size_t) bb.cap + b] = 1.0f; c->h_slot_top_k[(size_t) b] = 0; }
     upload_slot_params(c);
     reset();
     enqueue_batch_step(c, s, B, bb);                               // warm-up (first-use costs)
@@ -522,6 +537,7 @@ namespace {
 struct Utt {
     std::string text;
     bark_hip_request_params rp{};
+    bark_hip_sampling_filter flt{0, 1.0f};               // top-k / nucleus filter of its semantic and coarse samples
     std::mt19937 rng;
     std::vector<int32_t> coarse_out;                     // raw coarse ids of the windows done so far
     std::vector<int32_t> cached;                         // coarse: ids whose K / V rows sit in the utterance's slot cache
@@ -545,11 +561,15 @@ void move_slot(bark_context * c, int g, int from, int to) {
     HIP_OK(hipMemcpyAsync(bb.u + (size_t) to * 8192, bb.u + (size_t) from * 8192, 8192 * sizeof(double), hipMemcpyDeviceToDevice, st));
     c->h_slot_par[(size_t) to] = c->h_slot_par[(size_t) from];
     c->h_slot_par[(size_t) bb.cap + to] = c->h_slot_par[(size_t) bb.cap + from];
+    c->h_slot_par[2 * (size_t) bb.cap + to] = c->h_slot_par[2 * (size_t) bb.cap + from];
+    c->h_slot_top_k[(size_t) to] = c->h_slot_top_k[(size_t) from];
 }
 
 void set_slot_params(bark_context * c, int slot, const Utt & u) {
     c->h_slot_par[(size_t) slot] = u.rp.temp;
     c->h_slot_par[(size_t) c->batch.cap + slot] = u.rp.min_eos_p;
+    c->h_slot_par[2 * (size_t) c->batch.cap + slot] = u.flt.top_p;
+    c->h_slot_top_k[(size_t) slot] = u.flt.top_k;
 }
 
 
@@ -737,7 +757,8 @@ struct JobTail {
 // whole job; inside the semantic and the coarse stage the utterances travel through S = capacity slots: a slot whose utterance has
 // finished (its own step cap / stop rule, its own number of coarse windows) is handed to the next waiting utterance, and once nobody
 // waits the batch is compacted (the last slot moves into the hole), so every lock step runs over live utterances only.
-int engine_generate_batch(bark_context * c, const char * const * texts, int n, const uint32_t * seeds, const bark_hip_request_params * rps, const BatchAdmit * admit) {
+int engine_generate_batch(bark_context * c, const char * const * texts, int n, const uint32_t * seeds, const bark_hip_request_params * rps, const BatchAdmit * admit,
+                          const bark_hip_sampling_filter * flts) {
     HIP_OK(hipSetDevice(c->device));
     const JobScope job(c);
     const bark_context_params & p = c->params;
@@ -754,25 +775,32 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
         else { u.rp.temp = p.temp; u.rp.fine_temp = p.fine_temp; u.rp.min_eos_p = p.min_eos_p; u.rp.n_steps_text_encoder = p.n_steps_text_encoder; u.rp.seed = seeds ? seeds[i] : (uint32_t) c->rng(); }
         if (rps && seeds) u.rp.seed = seeds[i];
         if (!(u.rp.temp >= 0.0f) || !(u.rp.fine_temp >= 0.0f)) throw std::runtime_error("generate_batch: temperatures must be >= 0");
+        u.flt = flts ? flts[i] : c->filter;
+        if (!filter_valid(u.flt)) throw std::runtime_error("generate_batch: top_k must be >= 0 and top_p in (0, 1]");
         u.rng = std::mt19937(u.rp.seed);
     }
     if (c->host_sampling || c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd || c->any_w32) {
         // host-side sampling and f32 model files keep one utterance in flight: fall back to the sequential loop
         int good = 0;
         const bark_context_params saved = c->params;
+        const bark_hip_sampling_filter saved_flt = c->filter;
         for (int i = 0; i < n; i++) {
             bark_context::BatchResult & r = c->batch_results[(size_t) i];
             Utt & u = us[(size_t) i];
             // the captured graphs bake the sampling constants: an utterance with other parameters than its predecessor needs fresh ones (as bark_hip_set_params)
-            if (c->params.temp != u.rp.temp || c->params.fine_temp != u.rp.fine_temp || c->params.min_eos_p != u.rp.min_eos_p) engine_invalidate_graphs(c);
+            if (c->params.temp != u.rp.temp || c->params.fine_temp != u.rp.fine_temp || c->params.min_eos_p != u.rp.min_eos_p || filter_on(c->filter) != filter_on(u.flt))
+                engine_invalidate_graphs(c);
+            c->filter = u.flt;
             c->params.temp = u.rp.temp; c->params.fine_temp = u.rp.fine_temp; c->params.min_eos_p = u.rp.min_eos_p; c->params.n_steps_text_encoder = u.rp.n_steps_text_encoder;
             std::swap(c->rng, u.rng);
-            try { r.ok = engine_generate(c, u.text.c_str()); } catch (...) { std::swap(c->rng, u.rng); c->params = saved; engine_invalidate_graphs(c); throw; }
+            try { r.ok = engine_generate(c, u.text.c_str()); } catch (...) { std::swap(c->rng, u.rng); c->params = saved; c->filter = saved_flt; engine_invalidate_graphs(c); throw; }
             std::swap(c->rng, u.rng);
             if (r.ok) { r.semantic = c->semantic_tokens; r.coarse = c->coarse_tokens; r.fine = c->fine_tokens; r.audio = c->audio; good++; }
         }
-        if (c->params.temp != saved.temp || c->params.fine_temp != saved.fine_temp || c->params.min_eos_p != saved.min_eos_p) engine_invalidate_graphs(c);
+        if (c->params.temp != saved.temp || c->params.fine_temp != saved.fine_temp || c->params.min_eos_p != saved.min_eos_p || filter_on(c->filter) != filter_on(saved_flt))
+            engine_invalidate_graphs(c);
         c->params = saved;
+        c->filter = saved_flt;
         return good;
     }
     const int64_t t0 = now_us();
@@ -819,11 +847,11 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             // that arrived in the meantime join the job - they ride along through the remaining stages
             while (admit && queue.empty() && (int) slot_utt.size() < S && n < admit->max_job) {
                 Utt u;
-                if (!admit->next(u.text, u.rp)) break;
+                if (!admit->next(u.text, u.rp, u.flt)) break;
                 u.rng = std::mt19937(u.rp.seed);
                 u.cap = std::max(0, std::min(u.rp.n_steps_text_encoder, cap_max));
                 us.push_back(std::move(u)); c->batch_results.emplace_back(); prompts.emplace_back();
-                if (us.back().cap > 0 && us.back().rp.temp >= 0.0f && us.back().rp.fine_temp >= 0.0f) { queue.push_back(n); total_steps += us.back().cap; }
+                if (us.back().cap > 0 && us.back().rp.temp >= 0.0f && us.back().rp.fine_temp >= 0.0f && filter_valid(us.back().flt)) { queue.push_back(n); total_steps += us.back().cap; }
                 n++;
             }
             // hand free slots to waiting utterances: their prompts go through the model in one pass, which also takes their first sample

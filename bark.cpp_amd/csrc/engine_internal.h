@@ -121,9 +121,11 @@ void run_sample(bark_context * c, const StageCfg & s, int n_past_add, bool presc
 void enqueue_decode_step(bark_context * c, const StageCfg & s, bool sample, int n_past_add, bool embed = true);
 hipGraphExec_t capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps = 1, int ng = 4);
 void decode_steps_greedy(bark_context * c, const StageCfg & s, int n, int n_past);
-int sample_host(std::vector<float> & l, std::mt19937 & rng, float temp, float * eos_p);
+int sample_host(std::vector<float> & l, std::mt19937 & rng, float temp, float * eos_p, const bark_hip_sampling_filter * flt = nullptr);
+void filter_host(std::vector<float> & l, int32_t top_k, float top_p);      // C8n's cut, restated with a sort (removed ids -> -inf)
 std::vector<float> fetch_logits(bark_context * c, size_t n);
 void upload_uniforms(bark_context * c, int n);
+void upload_filter(bark_context * c);
 void consume_uniforms(bark_context * c, int n_used);
 void progress(bark_context * c, bark_encoding_step step, int pct);
 void run_fine_forward(bark_context * c, int nn, int n_rows, const RowBufs * rb = nullptr, int Z = 1);

@@ -19,6 +19,43 @@ namespace barkhip {
 // ---------------------------------------------------------------------------------------------------
 // timing hooks for bench.py (hipEvents on the engine's own stream)
 // ---------------------------------------------------------------------------------------------------
+// ONE top-k / nucleus filter launch over n_slots rows of n logits (C8n's kernel alone).  The filter masks its rows in place, so every launch gets the
+// original rows back first (a device copy outside the timed interval).  peaked: N(0, 1) logits times 4 (a nucleus of a few hundred ids at n = 10 048);
+// flat: N(0, 1) logits times 0.01 (nucleus ~ n).
+double engine_time_sample_filtered(bark_context * c, int n, int n_slots, int top_k, float top_p, int peaked, int iters) {
+    if (n < 1 || n > 12288 || n_slots < 1 || n_slots > 256 || !filter_valid(bark_hip_sampling_filter{top_k, top_p})) throw std::runtime_error("time_sample_filter: bad arguments");
+    HIP_OK(hipSetDevice(c->device));
+    std::mt19937 g(1234);
+    std::normal_distribution<float> nd(0.0f, 1.0f);
+    std::vector<float> rows((size_t) n_slots * n);
+    for (auto & v : rows) v = nd(g) * (peaked ? 4.0f : 0.01f);
+    struct Buf { void * p = nullptr; ~Buf() { if (p) (void) hipFree(p); } } orig, work, par;
+    HIP_OK(hipMalloc(&orig.p, rows.size() * 4)); HIP_OK(hipMalloc(&work.p, rows.size() * 4)); HIP_OK(hipMalloc(&par.p, (size_t) n_slots * 8));
+    std::vector<int32_t> pk((size_t) n_slots, top_k); std::vector<float> pp((size_t) n_slots, top_p);
+    HIP_OK(hipMemcpyAsync(orig.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(par.p, pk.data(), (size_t) n_slots * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync((char *) par.p + (size_t) n_slots * 4, pp.data(), (size_t) n_slots * 4, hipMemcpyHostToDevice, c->stream));
+    FilterArgs f;
+    f.logits = (float *) work.p; f.n = n; f.ld_logits = n; f.nbatch = n_slots; f.temp = 1.0f;
+    f.top_k = (const int32_t *) par.p; f.top_p = (const float *) ((char *) par.p + (size_t) n_slots * 4);
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+    double total_ms = 0.0;
+    iters = std::max(1, iters);
+    for (int i = -2; i < iters; i++) {                                    // two warm-up launches
+        HIP_OK(hipMemcpyAsync(work.p, orig.p, rows.size() * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_OK(hipEventRecord(e0, c->stream));
+        launch_sample_filter(c->stream, f);
+        HIP_OK(hipEventRecord(e1, c->stream));
+        HIP_OK(hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+        if (i >= 0) total_ms += ms;
+    }
+    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
+    return total_ms * 1000.0 / iters;
+}
+
 double engine_time_decode_step(bark_context * c, int which, int ctxlen, int iters, double * bytes_per_step) {
     if (which < 0 || which > 1) throw std::runtime_error("time_decode_step: which must be 0 or 1");
     HIP_OK(hipSetDevice(c->device));
@@ -34,6 +71,7 @@ double engine_time_decode_step(bark_context * c, int which, int ctxlen, int iter
     if (m.vtcache) HIP_OK(hipMemsetAsync(m.vtcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
     // the graph the stage loops replay: eight steps per launch; n_past does not advance here
     const int per_graph = 8;
+    upload_filter(c);                                                     // the step samples with the context's top-k / nucleus filter, if any
     if (m.bench_graph) { (void) hipGraphExecDestroy(m.bench_graph); m.bench_graph = nullptr; }     // the variant depends on the context length
     m.bench_graph = capture_decode(c, s, 0, per_graph, (ctxlen + 255) / 256);
     for (int i = 0; i < 3; i++) HIP_OK(hipGraphLaunch(m.bench_graph, c->stream));

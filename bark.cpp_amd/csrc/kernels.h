@@ -196,7 +196,7 @@ struct SampleArgs {
     int nbatch = 1; int ld_logits = 0; int out_stride = 0;   // batched decode: slot b reads logits + b*ld_logits, writes out_tokens + b*out_stride, x + b*E
     // lock-step batches whose utterances carry their own parameters: slot b samples with slot_temp[b] (0: greedy) and stops on slot_min_eos_p[b].
     // With slot_temp set the launch runs the greedy kernel for the slots with temperature 0 and / or the multinomial kernel for the others
-    // (`kinds`: 1 greedy slots present, 2 sampled slots present); a kernel leaves the other kind's slots untouched.
+    // (`kinds`: 1 greedy slots present, 2 sampled slots present, 4 sampled slots with a top-k / nucleus filter present); a kernel leaves the other kind's slots untouched.
     const float * slot_temp = nullptr; const float * slot_min_eos_p = nullptr; int kinds = 0;
     // embedding of the sampled token for the NEXT decode step, written by the same kernel (x == nullptr: skip)
     const half_t * wte = nullptr; const float * wpe = nullptr; int E = 0, n_in = 0, P = 1024; float * x = nullptr;
@@ -204,6 +204,18 @@ struct SampleArgs {
     BARK_TRACE_FIELD
 };
 void launch_sample_greedy(hipStream_t s, const SampleArgs & a);
+// top-k / nucleus filter (C8n) in front of the multinomial sampler: row b = logits + b * ld_logits holds the raw logits of
+// slot b; the ids the filter removes are set to -inf in place.  Per-slot settings in device memory (a captured graph serves refilled slots):
+// top_k[b] (0: off), top_p[b] (1: off).  Slots with temperature 0 (slot_temp[b], or temp without per-slot temperatures) are left alone.
+struct FilterArgs {
+    float * logits = nullptr; int n = 0; int ld_logits = 0; int nbatch = 1;
+    float temp = 0.0f; const float * slot_temp = nullptr;
+    const int32_t * top_k = nullptr; const float * top_p = nullptr;
+};
+void launch_sample_filter(hipStream_t s, const FilterArgs & f);
+// the decode loop's sampler launch with the filter: SampleArgs::kinds bit 4 (per-slot temperatures: filtered sampled slots present) or temp > 0
+// alone (top_k / top_p non-null) launches the filter first, then launch_sample_greedy(a).  top_k / top_p index like slot_temp.
+void launch_sample_filtered(hipStream_t s, const SampleArgs & a, const int32_t * top_k, const float * top_p);
 // fine: per-row greedy pick over the first n_cols of each row -> out[i*out_stride]
 // fine stage, fine_temp > 0: row r picks with the uniform draw u[r]
 // st (optional): near_tie counts the picks settled by the exact path (u within 1e-6 of a bin boundary)

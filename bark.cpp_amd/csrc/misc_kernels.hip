@@ -1,5 +1,5 @@
 // misc_kernels.hip - embeddings, LayerNorm over rows, and the sampling kernels (greedy rule C8, multinomial picks aligned
-// with std::discrete_distribution, per-row picks of the fine stage).
+// with std::discrete_distribution, the top-k / nucleus filter of rule C8n in front of them, per-row picks of the fine stage).
 #include "device_utils.h"
 
 #include <cfloat>
@@ -576,6 +576,211 @@ void launch_sample_greedy(hipStream_t s, const SampleArgs & a) {
     }
     if (a.temp > 0.0f) hipLaunchKernelGGL(sample_multinomial_kernel, dim3(a.nbatch), dim3(1024), 0, s, a);
     else hipLaunchKernelGGL(sample_greedy_kernel, dim3(a.nbatch), dim3(1024), 0, s, a.logits, a.st, a.n, a.ld_logits, a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// top-k / nucleus filter (C8n; semantics of generate_text_semantic / generate_coarse in suno-ai/bark generation.py):
+// top-p on the untempered logits, then top-k, then C8's multinomial over what is left.  pi orders the ids by l descending, ties by ascending
+// id.  Nucleus: w_i = floor(e_i 2^40) with e_i = (float) exp((double) (l_i - max)); pi(j) stays iff j == 0 or sum_{t<j} w_pi(t) <= top_p * S,
+// S = sum w (exact integers: S < 2^54, the comparison against the float top_p is exact).  Top-k: survivors whose logit is below the top_k-th
+// largest surviving logit go (ties at it stay).  The survivors are always a prefix of pi, so the filter is one cut in pi, found by radix
+// selection over an order-preserving 32-bit key of l (8-bit digits, counts and weight sums per digit in LDS; weights in three 18-bit limbs
+// so that 32-bit atomics hold every bucket sum); a tie group the cut straddles is split by ascending id (a 16-bit selection over the ids).
+// The removed ids are set to -inf IN PLACE: the decode loop's logits row is read by nothing but the sampler behind this kernel, and
+// sample_multinomial_kernel then runs unchanged (exp(-inf) = 0: probability exactly 0, eos_p 0 when the last id went).  One workgroup per
+// slot; slots whose temperature is 0 (greedy ignores the filter) or whose filter is off are left alone.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kFiltPer = 12;                                   // ids per thread: up to 12288 logits
+struct FiltLds {
+    unsigned hist[4][256];                                     // per digit: count, weight limbs [0, 18), [18, 36), [36, 41)
+    unsigned scan_c[4]; unsigned long long scan_w[4]; int cand[4];
+    unsigned r_digit, r_cnt, r_above_c; unsigned long long r_w, r_above_w;
+    float red_f[16]; unsigned long long red_w[16];
+};
+struct SelRes { unsigned key; unsigned cnt; unsigned above_c; unsigned long long w, above_w; };
+
+DEVINL unsigned filter_key(float l) { return f32_ordered(l == 0.0f ? 0.0f : l); }      // -0 and +0 are one logit value
+DEVINL unsigned long long shfl_up_u64(unsigned long long v, unsigned d) {
+    const unsigned lo = (unsigned) __shfl_up((int) (unsigned) v, d, 64), hi = (unsigned) __shfl_up((int) (unsigned) (v >> 32), d, 64);
+    return ((unsigned long long) hi << 32) | lo;
+}
+DEVINL unsigned long long shfl_xor_u64(unsigned long long v, int m) {
+    const unsigned lo = (unsigned) __shfl_xor((int) (unsigned) v, m, 64), hi = (unsigned) __shfl_xor((int) (unsigned) (v >> 32), m, 64);
+    return ((unsigned long long) hi << 32) | lo;
+}
+// floor(top_p * S) exactly, 0 < top_p < 1 a float (= fm 2^-sh), S < 2^54: then W <= top_p * S  <=>  W <= floor(top_p * S) for an integer W
+DEVINL unsigned long long nucleus_threshold(float top_p, unsigned long long S) {
+    const unsigned b = __builtin_bit_cast(unsigned, top_p);
+    const int E = (int) ((b >> 23) & 255u);
+    const unsigned long long fm = E ? ((b & 0x7FFFFFu) | 0x800000u) : (b & 0x7FFFFFu);
+    const int sh = E ? 150 - E : 149;
+    const unsigned long long lo = (S & 0xFFFFFFFFull) * fm, hi = (S >> 32) * fm;          // fm * S = hi 2^32 + lo < 2^78
+    const unsigned long long plo = lo + (hi << 32), phi = (hi >> 32) + (plo < lo ? 1ull : 0ull);
+    if (sh >= 128) return 0;
+    if (sh >= 64) return phi >> (sh - 64);
+    if (sh == 0) return plo;
+    return (plo >> sh) | (phi << (64 - sh));
+}
+
+// Among the active elements (act: bit j for element j of the thread), the LOWEST key K (nbits wide) such that the sum of `weighted ? w : 1`
+// over the active elements with key > K is <= T (the element at rank T when counting).  Every thread calls it; 8 bits per pass, from the top.
+// Returns K, the count and weight of its tie group and of everything above it.  A candidate always exists: the highest key has nothing above.
+DEVINL SelRes radix_select(FiltLds & L, const unsigned (&key)[kFiltPer], const unsigned long long (&w)[kFiltPer], unsigned act, bool weighted,
+                           unsigned long long T, int nbits) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned prefix = 0, pmask = 0;
+    SelRes r{0u, 0u, 0u, 0ull, 0ull};
+    for (int sh = nbits - 8; sh >= 0; sh -= 8) {
+        __syncthreads();                                       // the previous pass's readers are done with the histogram
+        (&L.hist[0][0])[tid] = 0u;
+        __syncthreads();
+        #pragma unroll
+        for (int j = 0; j < kFiltPer; j++) {
+            if (((act >> j) & 1u) && (key[j] & pmask) == prefix) {
+                const unsigned d = (key[j] >> sh) & 255u;
+                atomicAdd(&L.hist[0][d], 1u);
+                if (weighted && w[j]) {
+                    const unsigned l0 = (unsigned) (w[j] & 0x3FFFFull), l1 = (unsigned) ((w[j] >> 18) & 0x3FFFFull), l2 = (unsigned) (w[j] >> 36);
+                    if (l0) atomicAdd(&L.hist[1][d], l0);
+                    if (l1) atomicAdd(&L.hist[2][d], l1);
+                    if (l2) atomicAdd(&L.hist[3][d], l2);
+                }
+            }
+        }
+        __syncthreads();
+        // threads 0..255 take the digits in DESCENDING order (thread t: digit 255 - t) and scan counts and weights
+        unsigned c = 0, ic = 0; unsigned long long ww = 0, iw = 0;
+        if (tid < 256) {
+            const int d = 255 - tid;
+            c = L.hist[0][d];
+            ww = (unsigned long long) L.hist[1][d] + ((unsigned long long) L.hist[2][d] << 18) + ((unsigned long long) L.hist[3][d] << 36);
+            ic = c; iw = ww;
+            for (unsigned o = 1; o < 64; o <<= 1) {
+                const unsigned oc = (unsigned) __shfl_up((int) ic, o, 64); const unsigned long long ow = shfl_up_u64(iw, o);
+                if (lane >= (int) o) { ic += oc; iw += ow; }
+            }
+            if (lane == 63) { L.scan_c[wave] = ic; L.scan_w[wave] = iw; }
+        }
+        __syncthreads();
+        unsigned exc = 0; unsigned long long exw = 0;
+        if (tid < 256) {
+            unsigned oc = 0; unsigned long long ow = 0;
+            for (int v = 0; v < wave; v++) { oc += L.scan_c[v]; ow += L.scan_w[v]; }
+            exc = oc + ic - c; exw = ow + iw - ww;
+            const unsigned long long val = weighted ? r.above_w + exw : (unsigned long long) (r.above_c + exc);
+            int best = (c > 0 && val <= T) ? tid : -1;
+            for (int m = 1; m < 64; m <<= 1) best = max(best, __shfl_xor(best, m, 64));
+            if (lane == 0) L.cand[wave] = best;
+        }
+        __syncthreads();
+        if (tid < 256) {
+            const int best = max(max(L.cand[0], L.cand[1]), max(L.cand[2], L.cand[3]));
+            if (tid == best) { L.r_digit = 255u - (unsigned) tid; L.r_cnt = c; L.r_w = ww; L.r_above_c = exc; L.r_above_w = exw; }
+        }
+        __syncthreads();
+        prefix |= L.r_digit << sh; pmask |= 255u << sh;
+        r.above_c += L.r_above_c; r.above_w += L.r_above_w; r.cnt = L.r_cnt; r.w = L.r_w;
+    }
+    r.key = prefix;
+    return r;
+}
+}  // namespace
+
+__global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a) {
+    __shared__ FiltLds L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slot = blockIdx.x;
+    const float temp = a.slot_temp ? a.slot_temp[slot] : a.temp;
+    if (!(temp > 0.0f)) return;                                // greedy slot: C8's argmax, the filter does not apply
+    const int n = a.n;
+    const float top_p = a.top_p[slot];
+    int top_k = a.top_k[slot];
+    if (top_k >= n) top_k = 0;                                 // keeps everything
+    const bool nucleus = top_p < 1.0f;
+    if (!nucleus && top_k <= 0) return;                        // uniform over the workgroup
+    float * row = a.logits + (size_t) slot * a.ld_logits;
+    float lv[kFiltPer]; unsigned key[kFiltPer]; unsigned long long w[kFiltPer];
+    unsigned act = 0;
+    #pragma unroll
+    for (int j = 0; j < kFiltPer; j++) {
+        const int i = tid + 1024 * j;
+        lv[j] = i < n ? row[i] : -INFINITY;
+        key[j] = i < n ? filter_key(lv[j]) : 0u;
+        w[j] = 0;
+        if (i < n) act |= 1u << j;
+    }
+    // the cut: keep key > ck, and of the ids with key == ck those <= ci
+    unsigned ck = 0u; int ci = INT32_MAX;
+    unsigned J = (unsigned) n;                                 // survivors of the nucleus: the first J of pi
+    unsigned tie_keep = 0, tie_cnt = 0;                        // of the cut's tie group: how many stay / how many there are
+    if (nucleus) {
+        float mx = -INFINITY;
+        #pragma unroll
+        for (int j = 0; j < kFiltPer; j++) mx = fmaxf(mx, lv[j]);
+        mx = wave_max(mx);
+        if (lane == 0) L.red_f[wave] = mx;
+        __syncthreads();
+        mx = L.red_f[0];
+        for (int v = 1; v < 16; v++) mx = fmaxf(mx, L.red_f[v]);
+        unsigned long long s = 0;
+        #pragma unroll
+        for (int j = 0; j < kFiltPer; j++) {
+            if ((act >> j) & 1u) {
+                const float e = (float) exp((double) (lv[j] - mx));        // C8's exponential
+                w[j] = (unsigned long long) (e * 1099511627776.0f);        // floor(e 2^40): the scaling is exact, e <= 1
+                s += w[j];
+            }
+        }
+        for (int m = 1; m < 64; m <<= 1) s += shfl_xor_u64(s, m);
+        if (lane == 0) L.red_w[wave] = s;
+        __syncthreads();
+        unsigned long long S = 0;
+        for (int v = 0; v < 16; v++) S += L.red_w[v];
+        const unsigned long long T = nucleus_threshold(top_p, S);
+        const SelRes r = radix_select(L, key, w, act, true, T, 32);
+        const unsigned long long wv = r.cnt ? r.w / r.cnt : 0;   // equal logits, equal weights
+        tie_cnt = r.cnt;
+        const unsigned long long fit = wv == 0 ? r.cnt : (T - r.above_w) / wv + 1;          // ids of the group whose prefix stays <= T
+        tie_keep = fit < r.cnt ? (unsigned) fit : r.cnt;
+        ck = r.key;
+        J = r.above_c + tie_keep;
+    }
+    if (top_k > 0 && (unsigned) top_k < J) {
+        const SelRes q = radix_select(L, key, w, act, false, (unsigned long long) (top_k - 1), 32);     // the top_k-th largest logit
+        if (q.above_c + q.cnt < J) { ck = q.key; tie_cnt = q.cnt; tie_keep = q.cnt; }                  // else the nucleus cut stands
+    }
+    if (tie_keep < tie_cnt) {                                  // the cut splits a tie group: its tie_keep smallest ids stay
+        unsigned key2[kFiltPer]; unsigned act2 = 0;
+        #pragma unroll
+        for (int j = 0; j < kFiltPer; j++) {
+            key2[j] = 0xFFFFu - (unsigned) (tid + 1024 * j);   // descending key2 = ascending id
+            if (((act >> j) & 1u) && key[j] == ck) act2 |= 1u << j;
+        }
+        const SelRes z = radix_select(L, key2, w, act2, false, (unsigned long long) (tie_keep - 1), 16);
+        ci = (int) (0xFFFFu - z.key);
+    }
+    #pragma unroll
+    for (int j = 0; j < kFiltPer; j++) {
+        const int i = tid + 1024 * j;
+        if (((act >> j) & 1u) && !(key[j] > ck || (key[j] == ck && i <= ci))) row[i] = -INFINITY;
+    }
+}
+
+void launch_sample_filter(hipStream_t s, const FilterArgs & f) {
+    if (f.n > 1024 * kFiltPer) kernel_fail("bark-hip: the sampling filter takes at most %d logits per row", 1024 * kFiltPer);
+    hipLaunchKernelGGL(sample_filter_kernel, dim3(f.nbatch), dim3(1024), 0, s, f);
+}
+
+// kinds & 4 (or, without per-slot temperatures, temp > 0 and a filter): the filter runs on the rows first, then the samplers as above
+void launch_sample_filtered(hipStream_t s, const SampleArgs & a, const int32_t * top_k, const float * top_p) {
+    if (top_k && top_p && (a.slot_temp ? (a.kinds & 4) != 0 : a.temp > 0.0f)) {
+        FilterArgs f;
+        f.logits = const_cast<float *>(a.logits); f.n = a.n; f.ld_logits = a.ld_logits; f.nbatch = a.nbatch;
+        f.temp = a.temp; f.slot_temp = a.slot_temp; f.top_k = top_k; f.top_p = top_p;
+        launch_sample_filter(s, f);
+    }
+    launch_sample_greedy(s, a);
 }
 
 // fine stage, greedy: per-row pick of gpt_argmax_sample (bark.cpp:223-247) over the first n_cols logits.  Fast path as in sample_greedy_kernel: the

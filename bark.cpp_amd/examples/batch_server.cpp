@@ -5,9 +5,11 @@
 // bark_generate_audio; here every connection is a thread that hands its text to the request collector of bark_mi355x.h
 // (bark_hip_batcher_*): whatever is pending travels through the engine as ONE lock-step batch.  A request may carry "seed": n (default:
 // a counter starting at the server's --seed); its audio is what a fresh context loaded with that seed generates, whatever batch it joined.
+// "top_k": k (integer >= 0, 0 off) and "top_p": p (0 < p <= 1, 1 off) filter the request's semantic and coarse samples (bark_hip_sampling_filter);
+// a field left out takes the server's --top-k / --top-p, an invalid one is answered 400.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -28,7 +30,7 @@
 
 namespace {
 
-using barkhttp::json_string; using barkhttp::json_uint; using barkhttp::wav_f32;
+using barkhttp::json_string; using barkhttp::json_uint; using barkhttp::json_int; using barkhttp::json_float; using barkhttp::wav_f32;
 
 struct Options {
     std::string model, host = "127.0.0.1";
@@ -36,6 +38,7 @@ struct Options {
     std::vector<int> devices;                      // --devices 0,1,...: one context (own copy of the weights) and one worker per listed GPU, one queue
     uint32_t seed = 0;
     float temp = -1.0f, fine_temp = -1.0f;
+    int32_t top_k = 0; float top_p = 1.0f;         // --top-k / --top-p: the filter of requests that carry no "top_k" / "top_p" of their own
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -54,6 +57,8 @@ void respond(int fd, int status, const char * reason, const char * type, const s
 }
 
 std::atomic<uint32_t> next_seed{0};
+bark_hip_request_params request_defaults{};            // the context's sampling parameters (a request with its own filter carries them explicitly)
+bark_hip_sampling_filter filter_defaults{0, 1.0f};
 std::atomic<int> open_connections{0};
 constexpr int kMaxConnections = 512;                     // beyond that a connection is answered 503 at once
 
@@ -93,9 +98,25 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
         if (!json_string(body, "text", text)) {
             respond(fd, 400, "Bad Request", "text/plain", "expected a JSON body with a \"text\" string");
         } else {
+            // "top_k" (integer >= 0) / "top_p" (0 < p <= 1): the request's own filter, the other field from the server's defaults.  Checked
+            // before a default seed is drawn: a refused request does not shift the seeds of the requests behind it
+            bark_hip_sampling_filter flt = filter_defaults;
+            const int hk = json_int(body, "top_k", flt.top_k), hp = json_float(body, "top_p", flt.top_p);
+            int64_t ticket = -1;
+            if (hk < 0 || hp < 0 || flt.top_k < 0 || !(flt.top_p > 0.0f && flt.top_p <= 1.0f)) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"top_k\" must be an integer >= 0 and \"top_p\" a number in (0, 1]");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
             uint32_t seed = 0;
             if (!json_uint(body, "seed", seed)) seed = next_seed.fetch_add(1);
-            const int64_t ticket = bark_hip_batcher_submit(batcher, text.c_str(), seed);
+            if (hk || hp) {
+                bark_hip_request_params rp = request_defaults; rp.seed = seed;
+                ticket = bark_hip_batcher_submit_filtered(batcher, text.c_str(), &rp, &flt);
+            } else {
+                ticket = bark_hip_batcher_submit(batcher, text.c_str(), seed);
+            }
             int n = ticket > 0 ? bark_hip_batcher_wait(batcher, ticket, nullptr, 0) : -1;     // probe: -(2 + samples)
             if (n <= -2) {
                 std::vector<float> pcm((size_t) (-n - 2));
@@ -112,7 +133,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)]\n", argv0);
 }
 
 }  // namespace
@@ -132,6 +153,8 @@ int main(int argc, char ** argv) {
         else if (a == "--devices") { for (const char * p = next("--devices"); *p;) { char * e = nullptr; o.devices.push_back((int) strtol(p, &e, 10)); if (e == p) { usage(argv[0]); return 1; } p = *e == ',' ? e + 1 : e; } }
         else if (a == "--temp") o.temp = (float) atof(next("--temp"));
         else if (a == "--fine-temp") o.fine_temp = (float) atof(next("--fine-temp"));
+        else if (a == "--top-k") o.top_k = (int32_t) atoi(next("--top-k"));
+        else if (a == "--top-p") o.top_p = (float) atof(next("--top-p"));
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
@@ -144,6 +167,11 @@ int main(int argc, char ** argv) {
     if (o.devices.empty()) ctxs.push_back(bark_load_model(o.model.c_str(), params, o.seed));
     else for (int d : o.devices) ctxs.push_back(bark_hip_load_model_on_device(o.model.c_str(), params, o.seed, d));
     for (bark_context * c : ctxs) if (!c) { fprintf(stderr, "%s: could not load the model\n", argv[0]); for (bark_context * x : ctxs) if (x) bark_free(x); return 1; }
+    for (bark_context * c : ctxs)
+        if (bark_hip_set_sampling_filter(c, o.top_k, o.top_p) != 0) { fprintf(stderr, "%s: --top-k must be >= 0 and --top-p in (0, 1]\n", argv[0]); for (bark_context * x : ctxs) bark_free(x); return 1; }
+    filter_defaults = bark_hip_sampling_filter{o.top_k, o.top_p};
+    request_defaults.temp = params.temp; request_defaults.fine_temp = params.fine_temp; request_defaults.min_eos_p = params.min_eos_p;
+    request_defaults.n_steps_text_encoder = params.n_steps_text_encoder;
     bark_context * ctx = ctxs[0];
     bark_hip_batcher * batcher = ctxs.size() > 1 ? bark_hip_batcher_create_multi(ctxs.data(), (int) ctxs.size(), o.max_batch, o.max_wait_ms)
                                                  : bark_hip_batcher_create_ex(ctx, o.max_batch, o.max_wait_ms, o.streams);

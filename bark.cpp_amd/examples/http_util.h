@@ -64,6 +64,40 @@ inline bool json_uint(const std::string & js, const char * key, uint32_t & out) 
     return true;
 }
 
+// the value of `key` as a number: 0 the key is absent, 1 *out holds it, -1 the key is there but its value is not a number (a server answers 400)
+inline int json_number(const std::string & js, const char * key, double & out) {
+    const std::string pat = std::string("\"") + key + "\"";
+    size_t p = js.find(pat);
+    if (p == std::string::npos) return 0;
+    p = js.find(':', p + pat.size());
+    if (p == std::string::npos) return -1;
+    p++;
+    while (p < js.size() && (js[p] == ' ' || js[p] == '\t')) p++;
+    if (p >= js.size() || !((js[p] >= '0' && js[p] <= '9') || js[p] == '-' || js[p] == '+' || js[p] == '.')) return -1;
+    char * end = nullptr;
+    out = strtod(js.c_str() + p, &end);
+    if (end == js.c_str() + p) return -1;
+    return 1;
+}
+// an integer value (no fraction, within int32): 0 absent, 1 ok, -1 malformed
+inline int json_int(const std::string & js, const char * key, int32_t & out) {
+    double v = 0.0;
+    const int r = json_number(js, key, v);
+    if (r <= 0) return r;
+    if (!(v >= -2147483648.0 && v <= 2147483647.0) || v != (double) (int64_t) v) return -1;
+    out = (int32_t) v;
+    return 1;
+}
+// a float value: 0 absent, 1 ok, -1 malformed (NaN and infinities included)
+inline int json_float(const std::string & js, const char * key, float & out) {
+    double v = 0.0;
+    const int r = json_number(js, key, v);
+    if (r <= 0) return r;
+    if (!(v >= -3.4e38 && v <= 3.4e38)) return -1;
+    out = (float) v;
+    return 1;
+}
+
 inline std::string wav_f32(const float * pcm, int n, int rate) {
     auto u32 = [](std::string & s, uint32_t v) { s.append(reinterpret_cast<const char *>(&v), 4); };
     auto u16 = [](std::string & s, uint16_t v) { s.append(reinterpret_cast<const char *>(&v), 2); };

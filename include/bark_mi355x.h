@@ -115,6 +115,23 @@ struct bark_hip_request_params {
     uint32_t seed;                  /* seed of the utterance's own std::mt19937 (temp > 0 / fine_temp > 0)             */
 };
 BARK_API int bark_hip_generate_batch_ex(struct bark_context * bctx, const char * const * texts, int n, const struct bark_hip_request_params * per_utterance);
+
+/* Top-k and nucleus (top-p) filtering of the semantic and coarse samples (rule C8n; the semantics of generate_text_semantic /
+ * generate_coarse in suno-ai/bark generation.py): top-p on the UNtempered logits first - the ids in descending logit order (ties: ascending id) stay
+ * while the weight in front of them is <= top_p of the total (the id that crosses top_p stays, and so does the first); then top-k - survivors below
+ * the top_k-th largest surviving logit go (ties with it stay); then temperature and the multinomial draw as before, one uniform draw per sample.
+ * Greedy stages (temp 0) and the fine stage are not filtered.  {0, 1.0f} is off: the same kernels, graphs and bits as without a filter. */
+struct bark_hip_sampling_filter {
+    int32_t top_k;                  /* keep the top_k largest logits, 0 = off            */
+    float   top_p;                  /* nucleus mass in (0, 1], 1 = off                   */
+};
+/* The context's filter for bark_generate_audio, bark_hip_semantic / bark_hip_coarse and the jobs that carry no filters of their own.  Returns 0, or -1
+ * for top_k < 0 or top_p outside (0, 1] (NaN included).  bark_hip_clone_context copies it. */
+BARK_API int bark_hip_set_sampling_filter(struct bark_context * bctx, int32_t top_k, float top_p);
+/* bark_hip_generate_batch_ex with a filter per utterance (filters == NULL: the context's filter for everyone; per_utterance == NULL: the context's
+ * parameters).  Every utterance is bit-identical to a fresh context with its parameters, seed and filter. */
+BARK_API int bark_hip_generate_batch_filtered(struct bark_context * bctx, const char * const * texts, int n, const struct bark_hip_request_params * per_utterance,
+                                              const struct bark_hip_sampling_filter * filters);
 /* Fixes the number of lock-step slots (1..64; at least 8 are allocated) before the first job; returns 0 or -1. */
 BARK_API int bark_hip_reserve_batch(struct bark_context * bctx, int slots);
 /* audio of utterance i of the last batch: returns the sample count (-1 on error), *data points into the context */
@@ -148,6 +165,11 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create_multi(struct bark_con
 BARK_API int64_t bark_hip_batcher_submit(struct bark_hip_batcher * b, const char * text, uint32_t seed);
 /* a request with its own parameters (nullptr: the context's) */
 BARK_API int64_t bark_hip_batcher_submit_ex(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params);
+/* ... and its own top-k / nucleus filter; -1 for an invalid filter.  filter == nullptr: the context's filter as it was when the collector was
+ * created (bark_hip_batcher_create* copy it once; a later bark_hip_set_sampling_filter on that context does not reach the collector).
+ * params == nullptr: the context's parameters with seed 0, as bark_hip_batcher_submit_ex. */
+BARK_API int64_t bark_hip_batcher_submit_filtered(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                                  const struct bark_hip_sampling_filter * filter);
 BARK_API int bark_hip_batcher_wait(struct bark_hip_batcher * b, int64_t ticket, float * pcm, int capacity);
 BARK_API void bark_hip_batcher_stats(struct bark_hip_batcher * b, int * n_batches, int * n_requests, int * largest_batch);
 /* requests that joined a job that was already running (continuous admission: while the semantic stage of a job has free slots, requests
@@ -196,6 +218,15 @@ BARK_API double bark_hip_time_slots(struct bark_context * bctx, int which, int o
  * launch order (kernel time + the gap in front of it), closed by {"site": "step (graph replay)", "us": the same step replayed from its
  * hipGraph}.  Returns the length written, or -1 (error / capacity too small). */
 BARK_API int bark_hip_profile_lock_step(struct bark_context * bctx, int which, int n_slots, int ctx, int reps, char * json_out, int capacity);
+
+/* Kernel-level hook of the semantic / coarse sampler with the top-k / nucleus filter (tests): n_rows rows of n logits (n <= 12288), row r sampled with
+ * temp[r] (> 0), top_k[r], top_p[r] and the uniform draw u[r] by the decode loop's launches (filter, then the multinomial sampler of C8) on the
+ * context's stream.  out_ids[r]: the pick, out_eos_p[r]: the probability of the last id (0 if the filter removed it).  Returns 0, or -1. */
+BARK_API int bark_hip_sample_rows_filtered(struct bark_context * bctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k,
+                                           const float * top_p, const double * u, int32_t * out_ids, float * out_eos_p);
+/* Device time (us) of ONE filter launch over n_slots rows of n logits (the filter kernel alone, averaged over `iters` launches on rows that are
+ * restored in between); peaked != 0: logits with a nucleus of a few hundred ids, 0: nearly flat logits.  Returns < 0 on error. */
+BARK_API double bark_hip_time_sample_filter(struct bark_context * bctx, int n, int n_slots, int32_t top_k, float top_p, int peaked, int iters);
 
 /* Device time (us) of one fine forward pass (N = 1024), averaged over iters. */
 BARK_API double bark_hip_time_fine_pass(struct bark_context * bctx, int iters, double * flops_per_pass);
