@@ -49,6 +49,20 @@ RowBufs own_rows(bark_context * c) {
     return r;
 }
 
+LinArgs layer_product(const bark_context * c, const GptModel & m, int l, int op) {
+    const GptModel::Layer & L = m.layers[(size_t) l];
+    const int E = m.hp.n_embd;
+    LinArgs a;
+    switch (op) {
+        case OP_QKV:  a.W = L.attn_w; a.wq = L.attn_q; a.M = 3 * E; a.K = E; a.bias = L.attn_b; a.epi = EPI_QKV; a.ln_g = L.ln1_g; a.ln_b = L.ln1_b; a.E = E; a.P = c->P; break;
+        case OP_PROJ: a.W = L.proj_w; a.wq = L.proj_q; a.M = E; a.K = E; a.bias = L.proj_b; a.epi = EPI_RESID; break;
+        case OP_FC:   a.W = L.fc_w; a.wq = L.fc_q; a.M = 4 * E; a.K = E; a.bias = L.fc_b; a.epi = EPI_GELU; a.ln_g = L.ln2_g; a.ln_b = L.ln2_b; a.lut = c->d_gelu_lut; break;
+        case OP_MPROJ: a.W = L.mproj_w; a.wq = L.mproj_q; a.M = E; a.K = 4 * E; a.bias = L.mproj_b; a.epi = EPI_RESID; break;
+        default: throw std::runtime_error("layer_product: bad product index");
+    }
+    return a;
+}
+
 // N > 1 rows through all layers (bark.cpp:1261-1389 causal, :1474-1562 fine); x holds the embeddings.
 void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float * kbase, float * vbase, int pos0, const RowBufs * rbp, int seq, size_t kv_seq_stride,
                      const SeqTab * seqtab) {
@@ -65,18 +79,26 @@ void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float *
     // kbase / vbase: another utterance slot's cache (batched decode) or the fine batch's; default: the context's own cache
     auto layer_k = [&](const GptModel & mm, int l) { return (kbase ? kbase : mm.kcache) + mm.kv_layer_stride * (size_t) l; };
     auto layer_v = [&](const GptModel & mm, int l) { return (vbase ? vbase : mm.vcache) + mm.kv_layer_stride * (size_t) l; };
+    // the LayerNorm in front of a product is a launch of its own here.  f16 weights: activations are rounded to f16 rows (xn / att / hbuf); q4_0
+    // weights: f32 rows quantised to q8_0 (xq8 / xd8)
+    auto ln_rows = [&](LinArgs & a) {
+        if (m.w32)     launch_ln_rows_f32(s, rb.x, N, E, a.ln_g, a.ln_b, c->xn32);
+        else if (m.q4) launch_q8_rows(s, rb.x, N, E, a.ln_g, a.ln_b, c->xq);
+        else           launch_ln_rows(s, rb.x, N, E, a.ln_g, a.ln_b, rb.xn);
+        a.ln_g = a.ln_b = nullptr;
+    };
+    // the N input rows of a product: f16, their q8 image (block formats) or f32 (f32 files)
+    auto rows_in = [&](LinArgs & a, const half_t * x16, const float * x32) {
+        a.N = N; a.x_f16 = x16; a.xq = c->xq; if (m.w32) a.x_f32 = x32;
+        a.fast = fast;
+    };
     for (int l = 0; l < m.hp.n_layer; l++) {
-        const GptModel::Layer & L = m.layers[(size_t) l];
-        // f16 weights: activations are rounded to f16 rows (xn / att / hbuf); q4_0 weights: f32 rows quantised to q8_0 (xq8 / xd8)
-        if (m.w32)     launch_ln_rows_f32(s, rb.x, N, E, L.ln1_g, L.ln1_b, c->xn32);
-        else if (m.q4) launch_q8_rows(s, rb.x, N, E, L.ln1_g, L.ln1_b, c->xq);
-        else           launch_ln_rows(s, rb.x, N, E, L.ln1_g, L.ln1_b, rb.xn);
-        LinArgs a;
-        a.W = L.attn_w; a.wq = L.attn_q; a.M = 3 * E; a.K = E; a.N = N; a.x_f16 = rb.xn; a.xq = c->xq; if (m.w32) a.x_f32 = c->xn32; a.bias = L.attn_b; a.epi = EPI_QKV;
-        a.q = rb.q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.E = E; a.P = P; a.pos0 = pos0;
+        LinArgs a = layer_product(c, m, l, OP_QKV);
+        ln_rows(a);
+        rows_in(a, rb.xn, c->xn32);
+        a.q = rb.q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.pos0 = pos0;
         if (!kbase && !vbase) a.vt = detail::layer_vt(m, l);      // the context's own cache keeps the K-layout copy of V too
         a.seq = seq; a.kv_slot_stride = kv_seq_stride; a.seqtab = seqtab;
-        a.fast = fast;
         if (flash) {
             // tolerance route of the fine model: q / k / v leave the product as the f16 operands of the flash attention (no KV cache)
             a.epi = EPI_QKV16; a.q16 = rb.q16; a.k16 = rb.k16; a.vt16 = rb.vt16; a.seq = 1024;
@@ -93,22 +115,19 @@ void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float *
             launch_attn_prefill(s, at);
         }
         if (m.q4 && !m.w32) launch_q8_rows(s, c->att32, N, E, nullptr, nullptr, c->xq);
-        LinArgs p;
-        p.W = L.proj_w; p.wq = L.proj_q; p.M = E; p.K = E; p.N = N; p.x_f16 = rb.att; p.xq = c->xq; if (m.w32) p.x_f32 = c->att32; p.bias = L.proj_b; p.epi = EPI_RESID; p.res = rb.x;
-        p.fast = fast;
+        LinArgs p = layer_product(c, m, l, OP_PROJ);
+        rows_in(p, rb.att, c->att32);
+        p.res = rb.x;
         launch_linear(s, p);
-        if (m.w32)     launch_ln_rows_f32(s, rb.x, N, E, L.ln2_g, L.ln2_b, c->xn32);
-        else if (m.q4) launch_q8_rows(s, rb.x, N, E, L.ln2_g, L.ln2_b, c->xq);
-        else           launch_ln_rows(s, rb.x, N, E, L.ln2_g, L.ln2_b, rb.xn);
-        LinArgs f;
-        f.W = L.fc_w; f.wq = L.fc_q; f.M = 4 * E; f.K = E; f.N = N; f.x_f16 = rb.xn; f.xq = c->xq; if (m.w32) f.x_f32 = c->xn32; f.bias = L.fc_b; f.epi = EPI_GELU;
-        f.out_h = rb.hbuf; f.out_h32 = m.q4 ? c->h32 : nullptr; f.lut = c->d_gelu_lut;
-        f.fast = fast;
+        LinArgs f = layer_product(c, m, l, OP_FC);
+        ln_rows(f);
+        rows_in(f, rb.xn, c->xn32);
+        f.out_h = rb.hbuf; f.out_h32 = m.q4 ? c->h32 : nullptr;
         launch_linear(s, f);
         if (m.q4 && !m.w32) launch_q8_rows(s, c->h32, N, 4 * E, nullptr, nullptr, c->xq);
-        LinArgs o;
-        o.W = L.mproj_w; o.wq = L.mproj_q; o.M = E; o.K = 4 * E; o.N = N; o.x_f16 = rb.hbuf; o.xq = c->xq; if (m.w32) o.x_f32 = c->h32; o.bias = L.mproj_b; o.epi = EPI_RESID; o.res = rb.x;
-        o.fast = fast;
+        LinArgs o = layer_product(c, m, l, OP_MPROJ);
+        rows_in(o, rb.hbuf, c->h32);
+        o.res = rb.x;
         launch_linear(s, o);
     }
 }
@@ -118,11 +137,9 @@ void run_layers_decode(bark_context * c, GptModel & m) {
     const int E = m.hp.n_embd, H = m.hp.n_head, P = c->P;
     hipStream_t s = c->stream;
     for (int l = 0; l < m.hp.n_layer; l++) {
-        const GptModel::Layer & L = m.layers[(size_t) l];
         const bool ps = !(crosscheck_mask() & 4) && !m.w32 && P == 1024 && m.vtcache && E <= 1024;
-        LinArgs a;
-        a.W = L.attn_w; a.wq = L.attn_q; a.M = 3 * E; a.K = E; a.N = 1; a.x_f32 = c->x; a.ln_g = L.ln1_g; a.ln_b = L.ln1_b; a.bias = L.attn_b;
-        a.epi = EPI_QKV; a.q = c->q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.vt = layer_vt(m, l); a.E = E; a.P = P; a.pos0 = 0; a.st = c->d_state;
+        LinArgs a = layer_product(c, m, l, OP_QKV);
+        a.x_f32 = c->x; a.q = c->q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.vt = layer_vt(m, l); a.st = c->d_state;
         // f16 weights: the QKV kernel also forms the partial scores of the cached keys (C2 blocks), attn_ps_kernel finishes them
         if (ps) { a.ps = c->ps; a.knew = c->knew; a.ng = c->decode_ng; }
         BARK_TRACE_SET(c, a, (a.M + 3) / 4 + 4 * (E / 4));        // room for all four copies of the q workgroups
@@ -133,30 +150,35 @@ void run_layers_decode(bark_context * c, GptModel & m) {
         if (ps) { at.ps = c->ps; at.knew = c->knew; at.ng = c->decode_ng; at.vt = layer_vt(m, l); }
         BARK_TRACE_SET(c, at, 8 * 16 * ((H + 7) / 8) * 16);      // up to 16 slices per head, 16 waves per workgroup
         launch_attn_decode(s, at);
-        LinArgs p;
-        p.W = L.proj_w; p.wq = L.proj_q; p.M = E; p.K = E; p.N = 1; if (m.q4) p.x_f32 = c->att32; else p.x_f16 = c->att; p.bias = L.proj_b; p.epi = EPI_RESID; p.res = c->x;
+        LinArgs p = layer_product(c, m, l, OP_PROJ);
+        if (m.q4) p.x_f32 = c->att32; else p.x_f16 = c->att;
+        p.res = c->x;
         BARK_TRACE_SET(c, p, (p.M + 3) / 4);
         launch_linear(s, p);
-        LinArgs f;
-        f.W = L.fc_w; f.wq = L.fc_q; f.M = 4 * E; f.K = E; f.N = 1; f.x_f32 = c->x; f.ln_g = L.ln2_g; f.ln_b = L.ln2_b; f.bias = L.fc_b;
-        f.epi = EPI_GELU; f.out_h = c->hbuf; f.out_h32 = m.q4 ? c->h32 : nullptr; f.lut = c->d_gelu_lut;
+        LinArgs f = layer_product(c, m, l, OP_FC);
+        f.x_f32 = c->x; f.out_h = c->hbuf; f.out_h32 = m.q4 ? c->h32 : nullptr;
         BARK_TRACE_SET(c, f, (f.M + 3) / 4);
         launch_linear(s, f);
-        LinArgs o;
-        o.W = L.mproj_w; o.wq = L.mproj_q; o.M = E; o.K = 4 * E; o.N = 1; if (m.q4) o.x_f32 = c->h32; else o.x_f16 = c->hbuf; o.bias = L.mproj_b; o.epi = EPI_RESID; o.res = c->x;
+        LinArgs o = layer_product(c, m, l, OP_MPROJ);
+        if (m.q4) o.x_f32 = c->h32; else o.x_f16 = c->hbuf;
+        o.res = c->x;
         BARK_TRACE_SET(c, o, (o.M + 3) / 4);
         launch_linear(s, o);
     }
 }
 
-// final LayerNorm + LM head on ONE row (bark.cpp:1391-1405): rows [row0, row0 + n_rows) of the head,
-// or the parity-selected codebook window of the coarse model.
-void run_lm_head(bark_context * c, GptModel & m, const float * xrow, int row0, int n_rows, int parity_rows, float out_div) {
+LinArgs lm_head_args(const GptModel & m, int row0, int n_rows, int parity_rows, const float * xrow, float * out, int ld_out, const StepState * st) {
+    const int E = m.hp.n_embd;
     LinArgs a;
-    if (m.q4) a.wq = q4_rows(m.lm_head_q[0], (size_t) row0, m.hp.n_embd); else a.W = m.lm_head[0] + (size_t) row0 * m.hp.n_embd;
-    a.M = n_rows; a.K = m.hp.n_embd; a.N = 1;
-    a.x_f32 = xrow; a.ln_g = m.lnf_g; a.ln_b = m.lnf_b; a.epi = EPI_LOGITS; a.out = c->logits; a.ld_out = n_rows;
-    a.parity_rows = parity_rows; a.st = c->d_state; a.out_div = out_div;
+    if (m.q4) a.wq = q4_rows(m.lm_head_q[0], (size_t) row0, E); else a.W = m.lm_head[0] + (size_t) row0 * E;
+    a.M = n_rows; a.K = E; a.N = 1;
+    a.x_f32 = xrow; a.ln_g = m.lnf_g; a.ln_b = m.lnf_b; a.epi = EPI_LOGITS; a.out = out; a.ld_out = ld_out;
+    a.parity_rows = parity_rows; a.st = st;
+    return a;
+}
+void run_lm_head(bark_context * c, GptModel & m, const float * xrow, int row0, int n_rows, int parity_rows, float out_div) {
+    LinArgs a = lm_head_args(m, row0, n_rows, parity_rows, xrow, c->logits, n_rows, c->d_state);
+    a.out_div = out_div;
     BARK_TRACE_SET(c, a, (a.M + 3) / 4);
     launch_linear(c->stream, a);
 }
@@ -193,7 +215,8 @@ void check_ids(const int32_t * tok, size_t n, int n_in, const char * what) {
 int run_prefill(bark_context * c, GptModel & m, int n_tokens, bool merge, float * kbase, float * vbase, int pos0) {
     const int N = merge ? n_tokens - 256 : n_tokens;
     EmbedArgs e;
-    e.wte = m.wte[0]; e.wte_q = m.wte_q[0]; e.wpe = m.wpe; e.E = m.hp.n_embd; e.n_in = m.hp.n_in_vocab; e.P = c->P; e.tokens = c->d_tokens; e.n_rows = N; e.merge = merge ? 1 : 0; e.pos0 = pos0; e.x = c->x;
+    set_token_embedding(e, c, m);
+    e.tokens = c->d_tokens; e.n_rows = N; e.merge = merge ? 1 : 0; e.pos0 = pos0; e.x = c->x;
     launch_embed_causal(c->stream, e);
     run_layers_rows(c, m, N, true, kbase, vbase, pos0);
     return N;
@@ -216,6 +239,13 @@ StageCfg stage_cfg(bark_context * c, int which) {
     return s;
 }
 
+void embed_state_row(bark_context * c, const GptModel & m, const StepState * st, float * x) {
+    EmbedArgs e;
+    set_token_embedding(e, c, m);
+    e.n_rows = 1; e.st = st; e.x = x;
+    launch_embed_causal(c->stream, e);
+}
+
 void run_sample(bark_context * c, const StageCfg & s, int n_past_add, bool prescaled) {
     SampleArgs a;
     a.prescaled = prescaled ? 1 : 0;
@@ -223,9 +253,9 @@ void run_sample(bark_context * c, const StageCfg & s, int n_past_add, bool presc
     a.token_base = s.token_base; a.n_past_add = n_past_add; a.out_tokens = c->d_out_tokens;
     a.eos_trace = s.mode == 0 ? c->d_eos_trace : nullptr; a.st = c->d_state;
     a.temp = s.temp; a.u = c->d_u;
-    { static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0; a.force_exact = force_exact; }
-    const GptModel & m = c->gpt[s.which];
-    a.wte = m.wte[0]; a.wte_q = m.wte_q[0]; a.wpe = m.wpe; a.E = m.hp.n_embd; a.n_in = m.hp.n_in_vocab; a.P = c->P; a.x = c->x;
+    a.force_exact = exact_sampling();
+    set_token_embedding(a, c, c->gpt[s.which]);
+    a.x = c->x;
     BARK_TRACE_SET(c, a, 16);
     // top-k / nucleus filter (C8n): on the raw logits, in front of the multinomial sampler; its settings come from d_filter (upload_filter)
     if (!prescaled && s.temp > 0.0f && filter_on(c->filter)) launch_sample_filtered(c->stream, a, c->d_filter, reinterpret_cast<const float *>(c->d_filter + 1));
@@ -236,11 +266,7 @@ void run_sample(bark_context * c, const StageCfg & s, int n_past_add, bool presc
 // In the greedy loop the previous sample kernel has already written x, so the step starts at the layers.
 void enqueue_decode_step(bark_context * c, const StageCfg & s, bool sample, int n_past_add, bool embed) {
     GptModel & m = c->gpt[s.which];
-    if (embed) {
-        EmbedArgs e;
-        e.wte = m.wte[0]; e.wte_q = m.wte_q[0]; e.wpe = m.wpe; e.E = m.hp.n_embd; e.n_in = m.hp.n_in_vocab; e.P = c->P; e.n_rows = 1; e.st = c->d_state; e.x = c->x;
-        launch_embed_causal(c->stream, e);
-    }
+    if (embed) embed_state_row(c, m, c->d_state, c->x);
     run_layers_decode(c, m);
     // greedy decode step: the LM head divides by 0.7 itself (2512 waves instead of one workgroup doing 10 048 divisions)
     const bool prescale = sample && s.temp == 0.0f;
@@ -248,19 +274,34 @@ void enqueue_decode_step(bark_context * c, const StageCfg & s, bool sample, int 
     if (sample) run_sample(c, s, n_past_add, prescale);
 }
 
-hipGraphExec_t capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps, int ng) {
+hipGraphExec_t capture_graph(hipStream_t s, const std::function<void()> & body) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    const int ng_saved = c->decode_ng;
-    c->decode_ng = std::max(1, std::min(ng, 4));
-    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    try { for (int i = 0; i < n_steps; i++) enqueue_decode_step(c, s, true, n_past_add, false); }
-    catch (...) { c->decode_ng = ng_saved; hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(c->stream, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
-    c->decode_ng = ng_saved;
-    HIP_OK(hipStreamEndCapture(c->stream, &graph));
+    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    try { body(); }
+    catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(s, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
+    HIP_OK(hipStreamEndCapture(s, &graph));
     HIP_OK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     (void) hipGraphDestroy(graph);
     return exec;
+}
+
+double time_on_stream_us(bark_context * c, const std::function<void()> & body) {
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void) hipEventDestroy(e); } } e0, e1;
+    HIP_OK(hipEventCreate(&e0.e)); HIP_OK(hipEventCreate(&e1.e));
+    HIP_OK(hipEventRecord(e0.e, c->stream));
+    body();
+    HIP_OK(hipEventRecord(e1.e, c->stream));
+    HIP_OK(hipEventSynchronize(e1.e));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0.e, e1.e));
+    return (double) ms * 1000.0;
+}
+
+hipGraphExec_t capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps, int ng) {
+    struct Restore { bark_context * c; int ng; ~Restore() { c->decode_ng = ng; } } restore{c, c->decode_ng};      // also when a launch throws
+    c->decode_ng = std::max(1, std::min(ng, 4));
+    return capture_graph(c->stream, [&] { for (int i = 0; i < n_steps; i++) enqueue_decode_step(c, s, true, n_past_add, false); });
 }
 
 // n consecutive decode steps; the cache holds n_past rows before the first of them (step k then attends over n_past + k + 1 keys).
@@ -448,7 +489,7 @@ void engine_sample_rows_filtered(bark_context * c, const float * logits, int n_r
         HIP_OK(hipMemcpyAsync(b_u.p, u + r0, (size_t) nb * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(b_st.p, sts.data(), (size_t) nb * sizeof(StepState), hipMemcpyHostToDevice, st));
         SampleArgs a;
-        { static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0; a.force_exact = force_exact; }
+        a.force_exact = exact_sampling();
         a.logits = (const float *) b_l.p; a.n = n; a.mode = 0; a.eos_token = -1; a.min_eos_p = 2.0f; a.token_base = 0; a.n_past_add = 0;
         a.out_tokens = (int32_t *) b_ids.p; a.eos_trace = (float *) b_eos.p; a.st = (StepState *) b_st.p;
         a.nbatch = nb; a.ld_logits = n; a.out_stride = 1; a.u = (const double *) b_u.p; a.u_stride = 1;
@@ -483,6 +524,38 @@ void run_fine_forward(bark_context * c, int nn, int n_rows, const RowBufs * rbp,
     a.W = m.lm_head[nn - 1]; a.wq = m.lm_head_q[nn - 1]; a.xq = c->xq; if (m.w32) a.x_f32 = c->xn32; a.M = n_rows; a.K = E; a.N = N; a.x_f16 = rb.xn; a.epi = EPI_LOGITS; a.out = rb.logits; a.ld_out = n_rows;
     a.fast = fine_products_on_f16_mfma(c, m, false) ? 1 : (!m.q4 && !m.w32) ? c->fast_gemm : 0;
     launch_linear(c->stream, a);                           // lm_heads[codebook_idx - n_codes_given], bark.cpp:1573
+}
+
+FinePlan fine_plan(const bark_context_params & p, const std::vector<int32_t> & coarse) {
+    const int nc = p.n_coarse_codebooks, cs = p.codebook_size;
+    FinePlan f;
+    f.T = (int) coarse.size() / nc;
+    if (f.T <= 0 || f.T > 8192) throw std::runtime_error("fine: number of frames must be in 1..8192");
+    for (int32_t v : coarse) if (v < 0 || v >= cs) throw std::runtime_error("fine: coarse code out of range");
+    // in_arr [L][8]: coarse rows, channels 2..7 and the time padding filled with `cs` (bark.cpp:1983-1996)
+    f.L = std::max(f.T, 1024);
+    f.in_arr.assign((size_t) f.L * 8, cs);
+    for (int t = 0; t < f.T; t++) for (int ch = 0; ch < nc; ch++) f.in_arr[(size_t) t * 8 + ch] = coarse[(size_t) t * nc + ch];
+    f.n_loops = std::max(0, (int) ceilf((float) (f.L - 1024) / 512.f)) + 1;          // bark.cpp:1998
+    return f;
+}
+// window n (bark.cpp:2002-2013).  T <= 1024: one window, start_idx == 0, rel == 0.  For longer inputs the reference
+// stores its samples at [rel + i] and runs out of the buffer (undefined behaviour); this engine and
+// the oracle implement the algorithm it was ported from (suno-ai/bark generate_fine): all 1024 positions are sampled
+// (the random stream advances as in the reference) and positions >= rel keep their sample.
+FineWindow fine_window(const FinePlan & f, int n) {
+    FineWindow w;
+    w.start_idx = std::min(n * 512, f.L - 1024);
+    w.start_fill_idx = std::min(n * 512, f.L - 512);
+    w.rel = w.start_fill_idx - w.start_idx;
+    return w;
+}
+void fine_window_tokens(const FinePlan & f, const FineWindow & w, int32_t * tok, size_t plane) {
+    for (int ch = 0; ch < 8; ch++) for (int j = 0; j < 1024; j++) tok[(size_t) ch * plane + j] = f.in_arr[(size_t) (w.start_idx + j) * 8 + ch];
+}
+void fine_write_back(FinePlan & f, const FineWindow & w, const bark_context_params & p, const int32_t * tok, size_t plane) {
+    for (int nn = p.n_coarse_codebooks; nn < p.n_fine_codebooks; nn++)                       // bark.cpp:2041-2046
+        for (int j = 0; j < p.codebook_size - w.rel; j++) f.in_arr[(size_t) (w.start_fill_idx + j) * 8 + nn] = tok[(size_t) nn * plane + w.rel + j];
 }
 }  // namespace detail
 
@@ -617,9 +690,7 @@ std::vector<int32_t> engine_coarse(bark_context * c, const std::vector<int32_t> 
         StepState st = fresh_state(); st.step = step_idx; st.n_past = L; st.cur_token = in[(size_t) L];
         set_state(c, st);
         if (greedy && rows == 1) {
-            EmbedArgs e;
-            e.wte = m.wte[0]; e.wte_q = m.wte_q[0]; e.wpe = m.wpe; e.E = m.hp.n_embd; e.n_in = m.hp.n_in_vocab; e.P = c->P; e.n_rows = 1; e.st = c->d_state; e.x = c->x;
-            launch_embed_causal(c->stream, e);
+            embed_state_row(c, m, c->d_state, c->x);
             decode_steps_greedy(c, s, 1, L);
             c->stats.n_prefix_rows_reused += L;
         } else {
@@ -687,28 +758,17 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
     GptModel & m = c->gpt[2];
     const int nc = p.n_coarse_codebooks, nf = p.n_fine_codebooks, cs = p.codebook_size;
     if (nc != 2 || nf != 8 || cs != 1024) throw std::runtime_error("fine: only 2 -> 8 codebooks of 1024 entries are supported");
-    const int T = (int) coarse.size() / nc;
-    if (T <= 0 || T > 8192) throw std::runtime_error("fine: number of frames must be in 1..8192");
-    for (int32_t v : coarse) if (v < 0 || v >= cs) throw std::runtime_error("fine: coarse code out of range");
-    // in_arr [L][8]: coarse rows, channels 2..7 and the time padding filled with `cs` (bark.cpp:1983-1996)
-    const int L = std::max(T, 1024);
-    std::vector<int32_t> in_arr((size_t) L * 8, cs);
-    for (int t = 0; t < T; t++) for (int ch = 0; ch < nc; ch++) in_arr[(size_t) t * 8 + ch] = coarse[(size_t) t * nc + ch];
-    const int n_loops = std::max(0, (int) ceilf((float) (L - 1024) / 512.f)) + 1;          // bark.cpp:1998
+    FinePlan plan = fine_plan(p, coarse);
+    const int n_loops = plan.n_loops;
     const bool greedy = p.fine_temp == 0.0f;
     const bool device_multinomial = !greedy && !c->host_sampling;
     StepState st = fresh_state();
     set_state(c, st);
     std::vector<int32_t> buf((size_t) 8 * 1024);
     for (int n = 0; n < n_loops; n++) {
-        // window n (bark.cpp:2002-2013).  T <= 1024: one window, start_idx == 0, rel == 0.  For longer inputs the reference
-        // stores its samples at [rel + i] and runs out of the buffer (undefined behaviour); this engine and
-        // the oracle implement the algorithm it was ported from (suno-ai/bark generate_fine): all 1024 positions are sampled
-        // (the random stream advances as in the reference) and positions >= rel keep their sample.
-        const int start_idx = std::min(n * 512, L - 1024);
-        const int start_fill_idx = std::min(n * 512, L - 512);
-        const int rel = start_fill_idx - start_idx;
-        for (int ch = 0; ch < 8; ch++) for (int j = 0; j < 1024; j++) buf[(size_t) ch * 1024 + j] = in_arr[(size_t) (start_idx + j) * 8 + ch];
+        const FineWindow w = fine_window(plan, n);
+        const int rel = w.rel;
+        fine_window_tokens(plan, w, buf.data(), 1024);
         upload_tokens(c, buf.data(), buf.size());
         if (device_multinomial) upload_uniforms(c, (nf - nc) * 1024);
         for (int nn = nc; nn < nf; nn++) {
@@ -724,15 +784,7 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
                 };
                 if (c->use_graph && rel == 0) {
                     hipGraphExec_t & g = c->fine_graphs[nn + (fine_products_on_f16_mfma(c, m, false) ? 8 : 0)];
-                    if (!g) {
-                        hipGraph_t graph = nullptr;
-                        HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                        try { enqueue(); }
-                        catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(c->stream, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
-                        HIP_OK(hipStreamEndCapture(c->stream, &graph));
-                        HIP_OK(hipGraphInstantiate(&g, graph, nullptr, nullptr, 0));
-                        (void) hipGraphDestroy(graph);
-                    }
+                    if (!g) g = capture_graph(c->stream, enqueue);
                     HIP_OK(hipGraphLaunch(g, c->stream));
                     c->stats.graph_replays++;
                 } else {
@@ -757,13 +809,12 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
         if (device_multinomial) consume_uniforms(c, (nf - nc) * 1024);
         HIP_OK(hipMemcpyAsync(buf.data(), c->d_tokens, buf.size() * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
-        for (int nn = nc; nn < nf; nn++)                                                     // bark.cpp:2041-2046
-            for (int j = 0; j < cs - rel; j++) in_arr[(size_t) (start_fill_idx + j) * 8 + nn] = buf[(size_t) nn * 1024 + rel + j];
+        fine_write_back(plan, w, p, buf.data(), 1024);
     }
     const StepState cur = get_state(c);
     c->stats.n_near_tie += cur.near_tie;
-    in_arr.resize((size_t) T * 8);                                                           // strip the time padding
-    return in_arr;
+    plan.in_arr.resize((size_t) plan.T * 8);                                                 // strip the time padding
+    return std::move(plan.in_arr);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -805,20 +856,11 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
     const int U = (int) coarse.size();
     const bool greedy = p.fine_temp == 0.0f;
     if (!greedy && (!rngs || (int) rngs->size() != U)) throw std::runtime_error("fine_many: one generator per utterance is needed for fine_temp > 0");
-    struct Utt { int T, L, n_loops; std::vector<int32_t> in_arr; };
-    std::vector<Utt> us((size_t) U);
+    std::vector<FinePlan> us((size_t) U);
     int max_loops = 0;
     for (int u = 0; u < U; u++) {
-        const std::vector<int32_t> & co = *coarse[(size_t) u];
-        Utt & t = us[(size_t) u];
-        t.T = (int) co.size() / nc;
-        if (t.T <= 0 || t.T > 8192) throw std::runtime_error("fine: number of frames must be in 1..8192");
-        for (int32_t v : co) if (v < 0 || v >= cs) throw std::runtime_error("fine: coarse code out of range");
-        t.L = std::max(t.T, 1024);
-        t.in_arr.assign((size_t) t.L * 8, cs);                                              // bark.cpp:1983-1996
-        for (int i = 0; i < t.T; i++) for (int ch = 0; ch < nc; ch++) t.in_arr[(size_t) i * 8 + ch] = co[(size_t) i * nc + ch];
-        t.n_loops = std::max(0, (int) ceilf((float) (t.L - 1024) / 512.f)) + 1;             // bark.cpp:1998
-        max_loops = std::max(max_loops, t.n_loops);
+        us[(size_t) u] = fine_plan(p, *coarse[(size_t) u]);
+        max_loops = std::max(max_loops, us[(size_t) u].n_loops);
     }
     ensure_fine_batch(c, U);
     bark_context::FineBatch & fb = c->fine_batch;
@@ -827,17 +869,17 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
     std::vector<int32_t> buf;
     std::vector<double> ubuf;
     for (int n = 0; n < max_loops; n++) {
-        std::vector<int> act, rels, fills;
+        std::vector<int> act;
+        std::vector<FineWindow> win;
         for (int u = 0; u < U; u++) if (n < us[(size_t) u].n_loops) act.push_back(u);
         const int Z = (int) act.size(), R = Z * 1024;
         buf.assign((size_t) 8 * R, cs);
         bool any_rel = false;
         for (int z = 0; z < Z; z++) {
-            const Utt & t = us[(size_t) act[(size_t) z]];
-            const int start_idx = std::min(n * 512, t.L - 1024), start_fill_idx = std::min(n * 512, t.L - 512);      // bark.cpp:2002-2013
-            rels.push_back(start_fill_idx - start_idx); fills.push_back(start_fill_idx);
-            any_rel = any_rel || rels.back() > 0;
-            for (int ch = 0; ch < 8; ch++) for (int j = 0; j < 1024; j++) buf[(size_t) ch * R + (size_t) z * 1024 + j] = t.in_arr[(size_t) (start_idx + j) * 8 + ch];
+            const FinePlan & t = us[(size_t) act[(size_t) z]];
+            win.push_back(fine_window(t, n));
+            any_rel = any_rel || win.back().rel > 0;
+            fine_window_tokens(t, win.back(), buf.data() + (size_t) z * 1024, (size_t) R);
         }
         HIP_OK(hipMemcpyAsync(fb.tokens, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, c->stream));
         if (!greedy) {
@@ -859,19 +901,17 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
             if (greedy) launch_argmax_rows(c->stream, fb.logits, cs, R, cs, pick_dst, 1, c->d_state);
             else launch_sample_rows_multinomial(c->stream, fb.logits, cs, R, cs, p.fine_temp, fb.u + (size_t) (nn - nc) * R, pick_dst, 1, c->d_state);
             if (any_rel)
-                for (int z = 0; z < Z; z++)
-                    HIP_OK(hipMemcpyAsync(fb.tokens + (size_t) nn * R + (size_t) z * 1024 + rels[(size_t) z], fb.picks + (size_t) z * 1024 + rels[(size_t) z],
-                                          (size_t) (1024 - rels[(size_t) z]) * 4, hipMemcpyDeviceToDevice, c->stream));
+                for (int z = 0; z < Z; z++) {
+                    const size_t at = (size_t) z * 1024 + (size_t) win[(size_t) z].rel;
+                    HIP_OK(hipMemcpyAsync(fb.tokens + (size_t) nn * R + at, fb.picks + at, (size_t) (1024 - win[(size_t) z].rel) * 4, hipMemcpyDeviceToDevice, c->stream));
+                }
             c->stats.n_sample_fine += R;
         }
         HIP_OK(hipMemcpyAsync(buf.data(), fb.tokens, buf.size() * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
         for (int z = 0; z < Z; z++) {
-            Utt & t = us[(size_t) act[(size_t) z]];
-            const int rel = rels[(size_t) z];
             if (!greedy) (*rngs)[(size_t) act[(size_t) z]].discard(2ull * (unsigned long long) ((nf - nc) * 1024));
-            for (int nn = nc; nn < nf; nn++)                                                 // bark.cpp:2041-2046
-                for (int j = 0; j < cs - rel; j++) t.in_arr[(size_t) (fills[(size_t) z] + j) * 8 + nn] = buf[(size_t) nn * R + (size_t) z * 1024 + rel + j];
+            fine_write_back(us[(size_t) act[(size_t) z]], win[(size_t) z], p, buf.data() + (size_t) z * 1024, (size_t) R);
         }
     }
     const StepState cur = get_state(c);

@@ -129,7 +129,7 @@ int slot_kinds(const bark_context * c, int slot0, int n) {
 SampleArgs slot_sample_args(bark_context * c, const StageCfg & s, const bark_context::Batch & bb, int slot0, int nb, int n_past_add) {
     const GptModel & m = c->gpt[s.which];
     SampleArgs sa;
-    { static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0; sa.force_exact = force_exact; }
+    sa.force_exact = exact_sampling();
     sa.logits = bb.logits + bb.ld_logits * (size_t) slot0; sa.n = s.lm_rows; sa.mode = s.mode; sa.min_eos_p = s.min_eos_p; sa.eos_token = s.eos_token;
     sa.token_base = s.token_base; sa.n_past_add = n_past_add; sa.out_tokens = bb.out_tokens + (size_t) slot0 * 2048;
     sa.eos_trace = s.mode == 0 ? bb.eos_trace + (size_t) slot0 * 2048 : nullptr;
@@ -139,7 +139,8 @@ SampleArgs slot_sample_args(bark_context * c, const StageCfg & s, const bark_con
     const int first = (int) (bb.state - c->batch.state) + slot0;
     sa.slot_temp = c->batch.slot_par + first; sa.slot_min_eos_p = s.mode == 0 ? c->batch.slot_par + c->batch.cap + first : nullptr;
     sa.kinds = slot_kinds(c, first, nb);
-    sa.wte = m.wte[0]; sa.wte_q = m.wte_q[0]; sa.wpe = m.wpe; sa.E = m.hp.n_embd; sa.n_in = m.hp.n_in_vocab; sa.P = c->P; sa.x = bb.x + (size_t) slot0 * m.hp.n_embd;
+    set_token_embedding(sa, c, m);
+    sa.x = bb.x + (size_t) slot0 * m.hp.n_embd;
     return sa;
 }
 
@@ -175,17 +176,18 @@ void enqueue_batch_step(bark_context * c, const StageCfg & s, int B, const bark_
     // (tools/check_routes.py, test_cross_check_routes_give_the_same_bits).  BARK_HIP_CROSSCHECK bit 1 forces the VALU
     // GEMV per pair of slots everywhere (the cross-check route, and the only one for fewer than 8 slots and for quantised files).
     const bool mfma = !(crosscheck_mask() & 2) && B >= 8 && !m.q4;
-    auto product = [&](LinArgs & a, const float * ln_g, const float * ln_b) {
-        if (!mfma) { a.ln_g = ln_g; a.ln_b = ln_b; launch_linear(st, a); return; }
+    // a.ln_g / a.ln_b: the LayerNorm in front of the product (layer_product, lm_head_args)
+    auto product = [&](LinArgs & a) {
+        if (!mfma) { launch_linear(st, a); return; }
         // the two out-projections (input rows f16 already, 768 output rows): the VALU GEMV per pair of slots stays ahead for few slots
         // (tools/time_slots.py, us per launch VALU / matrix cores: proj 2.9 / 3.5 at 8 slots, 3.3 / 3.7 at 16, 4.4 / 3.7 at 32; MLP proj 5.1 / 8.0
         // at 8, 9.0 / 8.8 at 16, 12.7 / 8.9 at 32)
-        if (!ln_g && (a.K == a.M ? B < 24 : B < 16)) { launch_linear(st, a); return; }
+        if (!a.ln_g && (a.K == a.M ? B < 24 : B < 16)) { launch_linear(st, a); return; }
         // LayerNorm of the slot rows: inside the product kernel (BARK_HIP_CROSSCHECK bit 7 keeps the launch of its own, the cross-check route)
         // - measured per launch (QKV, small): 8 slots 5.7 us fused against 4.0 + 1.9 separate, 32 slots 8.7 against 5.7 + 2.0 (two slot tiles: twice
         // the workgroups repeat the LayerNorm), whole batches +2 % at 8 slots, -1 % at 32 (profiles/r03_ln_fused_slots.txt): fused for one slot tile
-        if (ln_g && linear_slots_fuses_ln(a.K) && B <= 16 && !(crosscheck_mask() & 128)) { a.ln_g = ln_g; a.ln_b = ln_b; }
-        else if (ln_g) { launch_ln_rows(st, a.x_f32, B, a.K, ln_g, ln_b, c->xn); a.x_f16 = c->xn; a.x_f32 = nullptr; }
+        const bool fused = linear_slots_fuses_ln(a.K) && B <= 16 && !(crosscheck_mask() & 128);
+        if (a.ln_g && !fused) { launch_ln_rows(st, a.x_f32, B, a.K, a.ln_g, a.ln_b, c->xn); a.x_f16 = c->xn; a.x_f32 = nullptr; a.ln_g = a.ln_b = nullptr; }
         a.ln_stats = nullptr;
         launch_linear_slots(st, a);
     };
@@ -193,16 +195,16 @@ void enqueue_batch_step(bark_context * c, const StageCfg & s, int B, const bark_
     const bool few_ok = !m.q4 && !m.w32 && P == 1024 && E <= 1024 && (E & 127) == 0 && B >= 2 && !(crosscheck_mask() & 2);
     const bool few = few_ok && B <= few_slots_max(0);
     const bool slot_ps = few_ok && bb.ps && B <= few_slots_max(1);
+    // all slots as one launch: row b of every input / output is slot b; the hoisted statistics go to the products with a LayerNorm in front
+    auto slots = [&](LinArgs & a) { a.batched = 1; a.nbatch = B; a.N = 1; a.ln_stats = hoist && a.ln_g ? bb.ln_stats : nullptr; };
     for (int l = 0; l < m.hp.n_layer; l++) {
-        const GptModel::Layer & L = m.layers[(size_t) l];
         float * kl = kc0 + m.kv_layer_stride * (size_t) l, * vl = vc0 + m.kv_layer_stride * (size_t) l;
         if (hoist && !mfma) launch_ln_stats(st, bb.x, B, E, bb.ln_stats);
-        LinArgs a;
-        a.batched = 1; a.nbatch = B; a.kv_slot_stride = slot; a.ln_stats = hoist ? bb.ln_stats : nullptr;
-        a.W = L.attn_w; a.wq = L.attn_q; a.M = 3 * E; a.K = E; a.N = 1; a.x_f32 = bb.x; a.bias = L.attn_b;
-        a.epi = EPI_QKV; a.q = bb.q; a.kc = kl; a.vc = vl; a.E = E; a.P = P; a.pos0 = 0; a.st = bb.state;
-        if (slot_ps) { a.ln_g = L.ln1_g; a.ln_b = L.ln1_b; a.ln_stats = nullptr; a.ps = bb.ps; launch_linear_slots_ps(st, a); }
-        else product(a, L.ln1_g, L.ln1_b);
+        LinArgs a = layer_product(c, m, l, OP_QKV);
+        slots(a);
+        a.kv_slot_stride = slot; a.x_f32 = bb.x; a.q = bb.q; a.kc = kl; a.vc = vl; a.st = bb.state;
+        if (slot_ps) { a.ln_stats = nullptr; a.ps = bb.ps; launch_linear_slots_ps(st, a); }
+        else product(a);
         mark("ln1+qkv");
         AttnDecodeArgs at;
         at.q = bb.q; at.kc = kl; at.vc = vl; at.H = H; at.P = P; at.st = bb.state; at.att = bb.att;
@@ -211,32 +213,30 @@ void enqueue_batch_step(bark_context * c, const StageCfg & s, int B, const bark_
         if (slot_ps) at.ps = bb.ps;
         launch_attn_decode(st, at);
         mark("attention");
-        LinArgs p;
-        p.batched = 1; p.nbatch = B;
-        p.W = L.proj_w; p.wq = L.proj_q; p.M = E; p.K = E; p.N = 1; if (m.q4) p.x_f32 = bb.att32; else p.x_f16 = bb.att; p.bias = L.proj_b; p.epi = EPI_RESID; p.res = bb.x;
-        if (few) launch_linear_slots_gemv(st, p); else product(p, nullptr, nullptr);
+        LinArgs p = layer_product(c, m, l, OP_PROJ);
+        slots(p);
+        if (m.q4) p.x_f32 = bb.att32; else p.x_f16 = bb.att;
+        p.res = bb.x;
+        if (few) launch_linear_slots_gemv(st, p); else product(p);
         mark("proj");
         if (hoist && !mfma) launch_ln_stats(st, bb.x, B, E, bb.ln_stats);
-        LinArgs f;
-        f.batched = 1; f.nbatch = B; f.ln_stats = hoist ? bb.ln_stats : nullptr;
-        f.W = L.fc_w; f.wq = L.fc_q; f.M = 4 * E; f.K = E; f.N = 1; f.x_f32 = bb.x; f.bias = L.fc_b;
-        f.epi = EPI_GELU; f.out_h = bb.h; f.out_h32 = m.q4 ? bb.h32 : nullptr; f.lut = c->d_gelu_lut;
-        if (few) { f.ln_g = L.ln2_g; f.ln_b = L.ln2_b; f.ln_stats = nullptr; f.E = E; launch_linear_slots_ps(st, f); }
-        else product(f, L.ln2_g, L.ln2_b);
+        LinArgs f = layer_product(c, m, l, OP_FC);
+        slots(f);
+        f.x_f32 = bb.x; f.out_h = bb.h; f.out_h32 = m.q4 ? bb.h32 : nullptr;
+        if (few) { f.ln_stats = nullptr; f.E = E; launch_linear_slots_ps(st, f); }
+        else product(f);
         mark("ln2+fc+gelu");
-        LinArgs o;
-        o.batched = 1; o.nbatch = B;
-        o.W = L.mproj_w; o.wq = L.mproj_q; o.M = E; o.K = 4 * E; o.N = 1; if (m.q4) o.x_f32 = bb.h32; else o.x_f16 = bb.h; o.bias = L.mproj_b; o.epi = EPI_RESID; o.res = bb.x;
-        if (few) launch_linear_slots_gemv(st, o); else product(o, nullptr, nullptr);
+        LinArgs o = layer_product(c, m, l, OP_MPROJ);
+        slots(o);
+        if (m.q4) o.x_f32 = bb.h32; else o.x_f16 = bb.h;
+        o.res = bb.x;
+        if (few) launch_linear_slots_gemv(st, o); else product(o);
         mark("mlp_proj");
     }
     if (hoist && !mfma) launch_ln_stats(st, bb.x, B, E, bb.ln_stats);
-    LinArgs h;
-    h.batched = 1; h.nbatch = B; h.ln_stats = hoist ? bb.ln_stats : nullptr;
-    if (m.q4) h.wq = q4_rows(m.lm_head_q[0], (size_t) s.lm_row0, E); else h.W = m.lm_head[0] + (size_t) s.lm_row0 * E;
-    h.M = s.lm_rows; h.K = E; h.N = 1; h.x_f32 = bb.x;
-    h.epi = EPI_LOGITS; h.out = bb.logits; h.ld_out = (int) bb.ld_logits; h.parity_rows = s.parity_rows; h.st = bb.state;
-    product(h, m.lnf_g, m.lnf_b);
+    LinArgs h = lm_head_args(m, s.lm_row0, s.lm_rows, s.parity_rows, bb.x, bb.logits, (int) bb.ld_logits, bb.state);
+    slots(h);
+    product(h);
     mark("lnf+lm_head");
     launch_slot_sampler(c, st, slot_sample_args(c, s, bb, 0, B, 1));
     mark("sample+embed");
@@ -249,15 +249,7 @@ void batch_step(bark_context * c, const StageCfg & s, int B) {
         // size once per context (the executables are kept)
         const int key = s.which | (B << 1) | (slot_kinds(c, 0, B) << 12);
         hipGraphExec_t & exec = c->batch_graphs[key];
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            try { enqueue_batch_step(c, s, B, bb); }
-            catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(c->stream, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
-            HIP_OK(hipStreamEndCapture(c->stream, &graph));
-            HIP_OK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void) hipGraphDestroy(graph);
-        }
+        if (!exec) exec = capture_graph(c->stream, [&] { enqueue_batch_step(c, s, B, bb); });
         HIP_OK(hipGraphLaunch(exec, c->stream));
         c->stats.graph_replays++;
     } else {
@@ -276,11 +268,8 @@ bark_context::Batch slot_view(const bark_context * c, const StageCfg & s, int b)
     return v;
 }
 void embed_slot(bark_context * c, const StageCfg & s, int b) {
-    GptModel & m = c->gpt[s.which];
-    EmbedArgs e;
-    e.wte = m.wte[0]; e.wte_q = m.wte_q[0]; e.wpe = m.wpe; e.E = m.hp.n_embd; e.n_in = m.hp.n_in_vocab; e.P = c->P; e.n_rows = 1;
-    e.st = c->batch.state + b; e.x = c->batch.x + (size_t) b * m.hp.n_embd;
-    launch_embed_causal(c->stream, e);
+    const GptModel & m = c->gpt[s.which];
+    embed_state_row(c, m, c->batch.state + b, c->batch.x + (size_t) b * m.hp.n_embd);
 }
 
 // temp > 0: the next `n` uniform draws of a slot's own generator, taken from a COPY as in upload_uniforms()
@@ -304,12 +293,8 @@ void batch_prefill_and_sample(bark_context * c, const StageCfg & s, int slot, co
     set_slot_state(c, slot, st);
     float * kb = bb.kc[s.which] + bb.slot_stride[s.which] * (size_t) slot, * vb = bb.vc[s.which] + bb.slot_stride[s.which] * (size_t) slot;
     const int N = run_prefill(c, m, (int) ids.size() - L, merge, kb, vb, L);
-    LinArgs h;
-    if (m.q4) h.wq = q4_rows(m.lm_head_q[0], (size_t) s.lm_row0, m.hp.n_embd); else h.W = m.lm_head[0] + (size_t) s.lm_row0 * m.hp.n_embd;
-    h.M = s.lm_rows; h.K = m.hp.n_embd; h.N = 1;
-    h.x_f32 = c->x + (size_t) (N - 1) * m.hp.n_embd; h.ln_g = m.lnf_g; h.ln_b = m.lnf_b; h.epi = EPI_LOGITS;
-    h.out = bb.logits + bb.ld_logits * (size_t) slot; h.ld_out = (int) bb.ld_logits; h.parity_rows = s.parity_rows; h.st = bb.state + slot;
-    launch_linear(c->stream, h);
+    launch_linear(c->stream, lm_head_args(m, s.lm_row0, s.lm_rows, s.parity_rows, c->x + (size_t) (N - 1) * m.hp.n_embd,
+                                          bb.logits + bb.ld_logits * (size_t) slot, (int) bb.ld_logits, bb.state + slot));
     launch_slot_sampler(c, c->stream, slot_sample_args(c, s, bb, slot, 1, N));
 }
 
@@ -354,7 +339,8 @@ void batch_prefill_many(bark_context * c, const StageCfg & s, const std::vector<
     HIP_OK(hipMemsetAsync(bb.pf_x, 0, (size_t) Z * seq * E * sizeof(float), st));          // padding rows: zeros (their results are never read)
     for (int z = 0; z < Z; z++) {
         EmbedArgs e;
-        e.wte = m.wte[0]; e.wte_q = m.wte_q[0]; e.wpe = m.wpe; e.E = E; e.n_in = m.hp.n_in_vocab; e.P = P; e.tokens = bb.pf_tokens + (size_t) z * tok_stride;
+        set_token_embedding(e, c, m);
+        e.tokens = bb.pf_tokens + (size_t) z * tok_stride;
         e.n_rows = tab[(size_t) z].len; e.merge = merge ? 1 : 0; e.pos0 = Ls[(size_t) z]; e.x = bb.pf_x + (size_t) z * seq * E;
         launch_embed_causal(st, e);
     }
@@ -363,11 +349,8 @@ void batch_prefill_many(bark_context * c, const StageCfg & s, const std::vector<
     run_layers_rows(c, m, Z * seq, true, bb.kc[s.which], bb.vc[s.which], 0, &rb, seq, bb.slot_stride[s.which], bb.pf_tab);
     for (int z = 0; z < Z; z++) {
         const int slot = slots[(size_t) z], N = tab[(size_t) z].len;
-        LinArgs h;
-        h.W = m.lm_head[0] + (size_t) s.lm_row0 * E; h.M = s.lm_rows; h.K = E; h.N = 1;
-        h.x_f32 = bb.pf_x + ((size_t) z * seq + (size_t) (N - 1)) * E; h.ln_g = m.lnf_g; h.ln_b = m.lnf_b; h.epi = EPI_LOGITS;
-        h.out = bb.logits + bb.ld_logits * (size_t) slot; h.ld_out = (int) bb.ld_logits; h.parity_rows = s.parity_rows; h.st = bb.state + slot;
-        launch_linear(st, h);
+        launch_linear(st, lm_head_args(m, s.lm_row0, s.lm_rows, s.parity_rows, bb.pf_x + ((size_t) z * seq + (size_t) (N - 1)) * E,
+                                       bb.logits + bb.ld_logits * (size_t) slot, (int) bb.ld_logits, bb.state + slot));
         launch_slot_sampler(c, st, slot_sample_args(c, s, bb, slot, 1, N));
     }
     HIP_OK(hipStreamSynchronize(st));                           // tok / tab / sts are stack objects
@@ -415,45 +398,28 @@ double engine_time_slots(bark_context * c, int which, int op, int B, int kind, i
             launch_attn_decode(c->stream, at);
             return;
         }
-        LinArgs a;
+        LinArgs a = layer_product(c, m, l, op);
         a.batched = 1; a.nbatch = B; a.kv_slot_stride = slot; a.N = 1;
         switch (op) {
-            case 0: a.W = L.attn_w; a.M = 3 * E; a.K = E; a.bias = L.attn_b; a.epi = EPI_QKV; a.q = bb.q; a.kc = kl; a.vc = vl; a.E = E; a.P = P; a.st = bb.state;
-                    if (kind == 0) { a.x_f32 = bb.x; a.ln_g = L.ln1_g; a.ln_b = L.ln1_b; a.ln_stats = B >= 24 ? bb.ln_stats : nullptr; }
-                    else if (kind == 6) { a.x_f32 = bb.x; a.ln_g = L.ln1_g; a.ln_b = L.ln1_b; }          // LayerNorm fused into the matrix-core product
-                    else a.x_f16 = c->xn;
-                    break;
-            case 1: a.W = L.proj_w; a.M = E; a.K = E; a.x_f16 = bb.att; a.bias = L.proj_b; a.epi = EPI_RESID; a.res = bb.x; break;
-            case 2: a.W = L.fc_w; a.M = 4 * E; a.K = E; a.bias = L.fc_b; a.epi = EPI_GELU; a.out_h = bb.h; a.lut = c->d_gelu_lut;
-                    if (kind == 0) { a.x_f32 = bb.x; a.ln_g = L.ln2_g; a.ln_b = L.ln2_b; a.ln_stats = B >= 24 ? bb.ln_stats : nullptr; }
-                    else if (kind == 6) { a.x_f32 = bb.x; a.ln_g = L.ln2_g; a.ln_b = L.ln2_b; }
-                    else a.x_f16 = c->xn;
-                    break;
-            default: a.W = L.mproj_w; a.M = E; a.K = 4 * E; a.x_f16 = bb.h; a.bias = L.mproj_b; a.epi = EPI_RESID; a.res = bb.x; break;
+            case OP_QKV:  a.q = bb.q; a.kc = kl; a.vc = vl; a.st = bb.state; break;
+            case OP_PROJ: a.x_f16 = bb.att; a.res = bb.x; break;
+            case OP_FC:   a.out_h = bb.h; break;
+            default:      a.x_f16 = bb.h; a.res = bb.x; break;
+        }
+        if (a.ln_g) {
+            if (kind == 0) { a.x_f32 = bb.x; a.ln_stats = B >= 24 ? bb.ln_stats : nullptr; }
+            else if (kind == 6) a.x_f32 = bb.x;                          // LayerNorm fused into the matrix-core product
+            else { a.x_f16 = c->xn; a.ln_g = a.ln_b = nullptr; }         // rows normalised already (op 4 is that launch)
         }
         if (kind == 0) launch_linear(c->stream, a); else launch_linear_slots(c->stream, a);
     };
     const int per_graph = 48;
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    try { for (int i = 0; i < per_graph; i++) launch(i % m.hp.n_layer); }
-    catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(c->stream, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
-    HIP_OK(hipStreamEndCapture(c->stream, &graph));
-    HIP_OK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void) hipGraphDestroy(graph);
+    hipGraphExec_t exec = capture_graph(c->stream, [&] { for (int i = 0; i < per_graph; i++) launch(i % m.hp.n_layer); });
     HIP_OK(hipGraphLaunch(exec, c->stream));
     const int reps = std::max(1, iters / per_graph);
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec, c->stream));
-    HIP_OK(hipEventRecord(e1, c->stream));
-    HIP_OK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
+    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec, c->stream)); });
     (void) hipGraphExecDestroy(exec);
-    return (double) ms * 1000.0 / (reps * per_graph);
+    return us / (reps * per_graph);
 }
 
 // Time line of ONE lock step over B slots at context `ctxlen`: the step is enqueued eagerly `reps` times with an event behind every launch
@@ -510,14 +476,7 @@ void engine_profile_lock_step(bark_context * c, int which, int B, int ctxlen, in
     batch_step(c, s, B);
     HIP_OK(hipStreamSynchronize(c->stream));
     reset();
-    hipEvent_t g0, g1; HIP_OK(hipEventCreate(&g0)); HIP_OK(hipEventCreate(&g1));
-    HIP_OK(hipEventRecord(g0, c->stream));
-    for (int r = 0; r < reps; r++) batch_step(c, s, B);
-    HIP_OK(hipEventRecord(g1, c->stream));
-    HIP_OK(hipEventSynchronize(g1));
-    float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, g0, g1));
-    (void) hipEventDestroy(g0); (void) hipEventDestroy(g1);
-    out.emplace_back("step (graph replay)", (double) ms * 1000.0 / reps);
+    out.emplace_back("step (graph replay)", time_on_stream_us(c, [&] { for (int r = 0; r < reps; r++) batch_step(c, s, B); }) / reps);
 }
 
 namespace { bool ensure_tail_context(bark_context * c); bool tail_stream_enabled(); }

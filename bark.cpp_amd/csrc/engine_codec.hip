@@ -104,16 +104,11 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
         auto & slot = c->lstm_graph;
         if (slot.exec && (slot.out != R || slot.gi != c->c_gi || slot.B != B)) { (void) hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
         if (!slot.exec) {
-            hipGraph_t graph = nullptr;
-            HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            try {
+            slot.exec = capture_graph(s, [&] {
                 a.t_base = c->d_lstm_t;
                 for (int i = 0; i < kBlock; i++) { a.t = i; launch_lstm_pair_step(s, a); }
                 launch_add_int(s, c->d_lstm_t, kBlock);
-            } catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(s, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
-            HIP_OK(hipStreamEndCapture(s, &graph));
-            HIP_OK(hipGraphInstantiate(&slot.exec, graph, nullptr, nullptr, 0));
-            (void) hipGraphDestroy(graph);
+            });
             slot.out = R; slot.gi = c->c_gi; slot.B = B;
         }
         const int hdr[2] = {0, Tmax};
@@ -161,13 +156,7 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
         auto & cg = c->codec_graph;
         if (cg.exec && (cg.T != T || cg.buf != A)) { (void) hipGraphExecDestroy(cg.exec); cg.exec = nullptr; }
         if (!cg.exec) {
-            hipGraph_t graph = nullptr;
-            HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            try { tail(false); }
-            catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(s, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
-            HIP_OK(hipStreamEndCapture(s, &graph));
-            HIP_OK(hipGraphInstantiate(&cg.exec, graph, nullptr, nullptr, 0));
-            (void) hipGraphDestroy(graph);
+            cg.exec = capture_graph(s, [&] { tail(false); });
             cg.T = T; cg.buf = A; cg.out = pcm_dev; cg.tmul = tmul;
         }
         HIP_OK(hipGraphLaunch(cg.exec, s));

@@ -1,11 +1,15 @@
 // engine_internal.h - declarations shared by the engine's translation units (engine_load.hip: model upload; engine.hip:
-// building blocks and the stage loops; engine_batch.hip: lock-step batching; engine_timing.hip: bench hooks).  Not an API.
+// building blocks and the stage loops; engine_batch.hip: lock-step batching; engine_codec.hip: EnCodec decode; engine_timing.hip: bench
+// hooks).  Every launch descriptor that follows from the model alone is stated once here / in engine.hip (layer_product, lm_head_args,
+// set_token_embedding), and so are graph capture (capture_graph), event timing (time_on_stream_us) and the fine stage's window plan
+// (fine_plan / fine_window / fine_write_back).  Not an API.
 #pragma once
 #include "engine.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -103,6 +107,24 @@ struct JobScope {
     JobScope(const JobScope &) = delete; JobScope & operator=(const JobScope &) = delete;
 };
 // seq > 0: the N rows are N / seq independent sequences (fine windows), sequence z with its cache at kbase / vbase + z * kv_seq_stride
+// One of the four products of GPT layer l, with everything that follows from the model alone: W / wq, M, K, bias, epi (QKV also E and P, FC the GELU
+// LUT) and in ln_g / ln_b the LayerNorm that belongs in front of it (ln1: QKV, ln2: FC).  The caller adds its input rows, outputs, N / slots, state and
+// route; one that runs the LayerNorm as a launch of its own (rows already normalised) takes the pair from the descriptor and clears it.
+enum LayerOp { OP_QKV = 0, OP_PROJ = 1, OP_FC = 2, OP_MPROJ = 3 };      // the `op` of the timing hooks
+LinArgs layer_product(const bark_context * c, const GptModel & m, int l, int op);
+// final LayerNorm + LM head on ONE row xrow (bark.cpp:1391-1405): rows [row0, row0 + n_rows) of the head, or the parity-selected codebook window
+// of the coarse model (parity_rows, from st->step); logits -> out, rows ld_out apart
+LinArgs lm_head_args(const GptModel & m, int row0, int n_rows, int parity_rows, const float * xrow, float * out, int ld_out, const StepState * st);
+// the model half of EmbedArgs / SampleArgs: token and position tables of a causal model
+template <typename Args> void set_token_embedding(Args & a, const bark_context * c, const GptModel & m) {
+    a.wte = m.wte[0]; a.wte_q = m.wte_q[0]; a.wpe = m.wpe; a.E = m.hp.n_embd; a.n_in = m.hp.n_in_vocab; a.P = c->P;
+}
+void embed_state_row(bark_context * c, const GptModel & m, const StepState * st, float * x);      // x = embedding of st->cur_token at position st->n_past
+// Stream capture -> executable graph: `body` enqueues its launches on s (capture mode: thread local).  A body that throws ends the capture - the
+// stream would stay in capture mode for good otherwise - and what it recorded is dropped.  Runs once per graph, off the hot path.
+hipGraphExec_t capture_graph(hipStream_t s, const std::function<void()> & body);
+// device time of what `body` enqueues on the context's stream, in microseconds: a pair of events around it, destroyed on every path
+double time_on_stream_us(bark_context * c, const std::function<void()> & body);
 void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float * kbase = nullptr, float * vbase = nullptr, int pos0 = 0,
                      const RowBufs * rb = nullptr, int seq = 0, size_t kv_seq_stride = 0, const SeqTab * seqtab = nullptr);
 void run_layers_decode(bark_context * c, GptModel & m);
@@ -129,6 +151,15 @@ void upload_filter(bark_context * c);
 void consume_uniforms(bark_context * c, int n_used);
 void progress(bark_context * c, bark_encoding_step step, int pct);
 void run_fine_forward(bark_context * c, int nn, int n_rows, const RowBufs * rb = nullptr, int Z = 1);
+// The fine stage's plan of one utterance (bark_eval_fine_encoder, bark.cpp:1961-2059): T frames in L = max(T, 1024) rows of in_arr [L][8], n_loops
+// windows of 1024 rows with a hop of 512; window n reads rows from start_idx and keeps the picks of its positions >= rel (rows from start_fill_idx)
+struct FinePlan { int T = 0, L = 0, n_loops = 0; std::vector<int32_t> in_arr; };
+struct FineWindow { int start_idx, start_fill_idx, rel; };
+FinePlan fine_plan(const bark_context_params & p, const std::vector<int32_t> & coarse);
+FineWindow fine_window(const FinePlan & f, int n);
+// window -> tok [8][plane] (this window's 1024 columns), and the picks of channels nc.. at positions >= rel back into in_arr
+void fine_window_tokens(const FinePlan & f, const FineWindow & w, int32_t * tok, size_t plane);
+void fine_write_back(FinePlan & f, const FineWindow & w, const bark_context_params & p, const int32_t * tok, size_t plane);
 void ensure_fine_batch(bark_context * c, int Z);            // scratch of engine_fine_many for Z windows side by side
 RowBufs fine_batch_rows(bark_context * c, int Z);
 

@@ -38,22 +38,14 @@ double engine_time_sample_filtered(bark_context * c, int n, int n_slots, int top
     FilterArgs f;
     f.logits = (float *) work.p; f.n = n; f.ld_logits = n; f.nbatch = n_slots; f.temp = 1.0f;
     f.top_k = (const int32_t *) par.p; f.top_p = (const float *) ((char *) par.p + (size_t) n_slots * 4);
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-    double total_ms = 0.0;
+    double total_us = 0.0;
     iters = std::max(1, iters);
     for (int i = -2; i < iters; i++) {                                    // two warm-up launches
         HIP_OK(hipMemcpyAsync(work.p, orig.p, rows.size() * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIP_OK(hipEventRecord(e0, c->stream));
-        launch_sample_filter(c->stream, f);
-        HIP_OK(hipEventRecord(e1, c->stream));
-        HIP_OK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-        if (i >= 0) total_ms += ms;
+        const double us = time_on_stream_us(c, [&] { launch_sample_filter(c->stream, f); });
+        if (i >= 0) total_us += us;
     }
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-    return total_ms * 1000.0 / iters;
+    return total_us / iters;
 }
 
 double engine_time_decode_step(bark_context * c, int which, int ctxlen, int iters, double * bytes_per_step) {
@@ -77,25 +69,19 @@ double engine_time_decode_step(bark_context * c, int which, int ctxlen, int iter
     for (int i = 0; i < 3; i++) HIP_OK(hipGraphLaunch(m.bench_graph, c->stream));
     set_state(c, st);
     iters = std::max(1, iters / per_graph) * per_graph;
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; i += per_graph) {
-        HIP_OK(hipGraphLaunch(m.bench_graph, c->stream));
-        if (((i / per_graph) & 127) == 127) set_state(c, st);             // out_tokens holds 2048 entries
-    }
-    HIP_OK(hipEventRecord(e1, c->stream));
-    HIP_OK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
+    const double us = time_on_stream_us(c, [&] {
+        for (int i = 0; i < iters; i += per_graph) {
+            HIP_OK(hipGraphLaunch(m.bench_graph, c->stream));
+            if (((i / per_graph) & 127) == 127) set_state(c, st);         // out_tokens holds 2048 entries
+        }
+    });
     if (bytes_per_step) {
         const double E = m.hp.n_embd, L = m.hp.n_layer;
         // f16 weights of all layers + evaluated LM-head rows + f32 K and V rows read
         const double wb = weight_bytes_per_element(m);
         *bytes_per_step = L * 12.0 * E * E * wb + (double) s.lm_rows * E * wb + 2.0 * ctxlen * E * L * 4.0;
     }
-    return (double) ms * 1000.0 / std::max(1, iters);
+    return us / std::max(1, iters);
 }
 
 // One decode GEMV, launched `iters` times back to back while rotating through the layers' weights (so that the
@@ -107,7 +93,7 @@ double engine_time_gemv(bark_context * c, int which, int op, int iters, double *
     op &= 3;
     HIP_OK(hipSetDevice(c->device));
     GptModel & m = c->gpt[which];
-    const int E = m.hp.n_embd, P = c->P;
+    const int E = m.hp.n_embd;
     StepState st = fresh_state(); st.n_past = 100; st.cur_token = 1;
     set_state(c, st);
     HIP_OK(hipMemsetAsync(c->x, 0, (size_t) E * 4, c->stream));
@@ -115,39 +101,23 @@ double engine_time_gemv(bark_context * c, int which, int op, int iters, double *
     HIP_OK(hipMemsetAsync(c->hbuf, 0, (size_t) 4 * E * 2, c->stream));
     if (m.q4) { HIP_OK(hipMemsetAsync(c->att32, 0, (size_t) E * 4, c->stream)); HIP_OK(hipMemsetAsync(c->h32, 0, (size_t) 4 * E * 4, c->stream)); }
     auto launch = [&](int l) {
-        const GptModel::Layer & L = m.layers[(size_t) l];
-        LinArgs a;
+        LinArgs a = layer_product(c, m, l, op);
         a.N = 1;
         switch (op) {
-            case 0: a.W = L.attn_w; a.wq = L.attn_q; a.M = 3 * E; a.K = E; a.x_f32 = c->x; a.ln_g = L.ln1_g; a.ln_b = L.ln1_b; a.bias = L.attn_b; a.epi = EPI_QKV;
-                    a.q = c->q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.E = E; a.P = P; a.st = c->d_state; break;
-            case 1: a.W = L.proj_w; a.wq = L.proj_q; a.M = E; a.K = E; if (m.q4) a.x_f32 = c->att32; else a.x_f16 = c->att; a.bias = L.proj_b; a.epi = EPI_RESID; a.res = c->x; break;
-            case 2: a.W = L.fc_w; a.wq = L.fc_q; a.M = 4 * E; a.K = E; a.x_f32 = c->x; a.ln_g = L.ln2_g; a.ln_b = L.ln2_b; a.bias = L.fc_b; a.epi = EPI_GELU;
-                    a.out_h = c->hbuf; a.out_h32 = m.q4 ? c->h32 : nullptr; a.lut = c->d_gelu_lut; break;
-            default: a.W = L.mproj_w; a.wq = L.mproj_q; a.M = E; a.K = 4 * E; if (m.q4) a.x_f32 = c->h32; else a.x_f16 = c->hbuf; a.bias = L.mproj_b; a.epi = EPI_RESID; a.res = c->x; break;
+            case OP_QKV:  a.x_f32 = c->x; a.q = c->q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.st = c->d_state; break;
+            case OP_PROJ: if (m.q4) a.x_f32 = c->att32; else a.x_f16 = c->att; a.res = c->x; break;
+            case OP_FC:   a.x_f32 = c->x; a.out_h = c->hbuf; a.out_h32 = m.q4 ? c->h32 : nullptr; break;
+            default:      if (m.q4) a.x_f32 = c->h32; else a.x_f16 = c->hbuf; a.res = c->x; break;
         }
         launch_linear(c->stream, a);
     };
     // op >= 4 ("hot"): always layer 0, so the weights stay in L2; otherwise rotate through the layers.
     // The launches are captured into one hipGraph (48 nodes) so that the host launch rate does not bound the result.
     const int per_graph = 48;
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < per_graph; i++) launch(hot ? 0 : i % m.hp.n_layer);
-    HIP_OK(hipStreamEndCapture(c->stream, &graph));
-    HIP_OK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void) hipGraphDestroy(graph);
+    hipGraphExec_t exec = capture_graph(c->stream, [&] { for (int i = 0; i < per_graph; i++) launch(hot ? 0 : i % m.hp.n_layer); });
     HIP_OK(hipGraphLaunch(exec, c->stream));
     const int reps = std::max(1, iters / per_graph);
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec, c->stream));
-    HIP_OK(hipEventRecord(e1, c->stream));
-    HIP_OK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
+    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec, c->stream)); });
     (void) hipGraphExecDestroy(exec);
     iters = reps * per_graph;
     if (bytes_per_launch) {
@@ -155,7 +125,7 @@ double engine_time_gemv(bark_context * c, int which, int op, int iters, double *
         const double w = op == 0 ? 3 * Ed * Ed : op == 1 ? Ed * Ed : 4 * Ed * Ed;
         *bytes_per_launch = w * weight_bytes_per_element(m);          // the weight matrix; vectors are < 1 % of it
     }
-    return (double) ms * 1000.0 / std::max(1, iters);
+    return us / std::max(1, iters);
 }
 
 #ifdef BARK_TRACE
@@ -215,20 +185,12 @@ double engine_time_fine_pass(bark_context * c, int iters, double * flops_per_pas
     auto pass = [&](int nn) { if (Z > 1) run_fine_forward(c, nn, 1024, &rb, Z); else run_fine_forward(c, nn, 1024); };
     pass(4);
     HIP_OK(hipStreamSynchronize(c->stream));
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; i++) pass(2 + i % 6);
-    HIP_OK(hipEventRecord(e1, c->stream));
-    HIP_OK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
+    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) pass(2 + i % 6); });
     if (flops_per_pass) {
         const double E = m.hp.n_embd, L = m.hp.n_layer, N = 1024;
         *flops_per_pass = Z * (2.0 * N * (L * 12.0 * E * E + 1024.0 * E) + 4.0 * N * N * E * L);     // SURVEY.md 8(d), per window
     }
-    return (double) ms * 1000.0 / std::max(1, iters);
+    return us / std::max(1, iters);
 }
 
 }  // namespace barkhip

@@ -238,6 +238,8 @@ void launch_argmax_rows(hipStream_t s, const float * logits, int ld, int n_rows,
 // 1024 codec: every convolution as one fmaf chain in (ci, k) order (C9) instead of the f16 matrix cores' order (C9m); oracle: set_codec_mfma(False)
 // 512  fine model: the attention of whole windows through attn_rows_kernel (scores in an LDS tile) instead of attn_window_kernel (scores in registers)
 int crosscheck_mask();
+// BARK_HIP_EXACT_SAMPLING (read once per process; tests): != 0 sends every sample and every per-row pick through the exact path (SampleArgs::force_exact)
+int exact_sampling();
 int xcd_panel_width(int n_tiles, int ncol);            // column-panel width of the XCD-aware tile order (device_utils.h: panel_tile)
 void init_kernel_attributes();
 // internal: per-file pieces of the above and the weight-type specific back ends of launch_linear

@@ -817,10 +817,13 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float * logits, 
     }
     if (lane == 0) out[(size_t) row * out_stride] = best;
 }
+int exact_sampling() {
+    static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0;      // tests: every row through the exact path
+    return force_exact;
+}
 void launch_argmax_rows(hipStream_t s, const float * logits, int ld, int n_rows, int n_cols, int32_t * out, int out_stride,
                         StepState * st) {
-    static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0;      // tests: every row through the exact path
-    hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, logits, ld, n_rows, n_cols, out, out_stride, st, force_exact);
+    hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, logits, ld, n_rows, n_cols, out, out_stride, st, exact_sampling());
 }
 
 }  // namespace barkhip
