@@ -42,6 +42,20 @@ class BarkHipSamplingFilter(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
 
 
+class BarkHipVoicePrompt(C.Structure):
+    """struct bark_hip_voice_prompt (bark_mi355x.h): speaker history of the three stages (rule C10v), time-major arrays."""
+    _fields_ = [("semantic", C.c_void_p), ("n_semantic", C.c_int32), ("coarse_Tx2", C.c_void_p), ("n_coarse_frames", C.c_int32),
+                ("fine_Tx8", C.c_void_p), ("n_fine_frames", C.c_int32)]
+
+
+def _voice_struct(voice):
+    """(struct, arrays that must stay alive while it is used) for a voice.VoicePrompt or any object with semantic / coarse [T][2] / fine [T][8]."""
+    sem = np.ascontiguousarray(voice.semantic, dtype=np.int32).reshape(-1)
+    co = np.ascontiguousarray(voice.coarse, dtype=np.int32).reshape(-1, 2)
+    fi = np.ascontiguousarray(voice.fine, dtype=np.int32).reshape(-1, 8)
+    return BarkHipVoicePrompt(sem.ctypes.data, len(sem), co.ctypes.data, len(co), fi.ctypes.data, len(fi)), (sem, co, fi)
+
+
 class BarkHipStats(C.Structure):
     _fields_ = [
         ("t_load_us", C.c_int64), ("t_eval_us", C.c_int64), ("t_semantic_us", C.c_int64), ("t_coarse_us", C.c_int64),
@@ -82,6 +96,7 @@ EXPORTS = [
     "bark_hip_time_decode_step", "bark_hip_time_gemv", "bark_hip_time_slots", "bark_hip_time_fine_pass", "bark_hip_time_fine_passes", "bark_hip_describe", "bark_hip_set_fine_order", "bark_hip_load_model_on_device", "bark_hip_batcher_create_multi",
     "bark_hip_batcher_create", "bark_hip_batcher_create_ex", "bark_hip_batcher_submit", "bark_hip_batcher_submit_ex", "bark_hip_batcher_wait", "bark_hip_batcher_stats", "bark_hip_batcher_admitted", "bark_hip_batcher_free",
     "bark_hip_set_sampling_filter", "bark_hip_generate_batch_filtered", "bark_hip_batcher_submit_filtered", "bark_hip_sample_rows_filtered", "bark_hip_time_sample_filter",
+    "bark_hip_set_voice_prompt", "bark_hip_generate_batch_voiced", "bark_hip_batcher_submit_voiced", "bark_hip_pick_rows",
 ]
 
 
@@ -167,6 +182,12 @@ def load_library() -> C.CDLL:
     lib.bark_hip_sample_rows_filtered.argtypes = [vp, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]
     lib.bark_hip_time_sample_filter.restype = C.c_double
     lib.bark_hip_time_sample_filter.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_float, C.c_int, C.c_int]
+    lib.bark_hip_set_voice_prompt.argtypes = [vp, C.POINTER(BarkHipVoicePrompt)]
+    lib.bark_hip_generate_batch_voiced.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter),
+                                                   C.POINTER(C.POINTER(BarkHipVoicePrompt))]
+    lib.bark_hip_batcher_submit_voiced.restype = C.c_int64
+    lib.bark_hip_batcher_submit_voiced.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter), C.POINTER(BarkHipVoicePrompt)]
+    lib.bark_hip_pick_rows.argtypes = [vp, fp, C.c_int, C.c_int, C.c_float, fp, ip, ip, ip]
     lib.bark_hip_batcher_wait.argtypes = [vp, C.c_int64, fp, C.c_int]
     lib.bark_hip_batcher_stats.restype = None
     lib.bark_hip_batcher_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -370,13 +391,23 @@ class BarkContext:
         if self._lib.bark_hip_reserve_batch(self._h, slots) != 0:
             raise RuntimeError("bark_hip_reserve_batch failed")
 
-    def generate_batch(self, texts, seeds=None, params=None, filters=None) -> list:
-        """In-engine batching (bark_hip_generate_batch[_seeded|_ex|_filtered]): returns one dict per utterance (or None if it failed).
+    def generate_batch(self, texts, seeds=None, params=None, filters=None, voices=None) -> list:
+        """In-engine batching (bark_hip_generate_batch[_seeded|_ex|_filtered|_voiced]): returns one dict per utterance (or None if it failed).
         params: one BarkHipRequestParams per utterance (request_params(...)); filters: one (top_k, top_p) pair or BarkHipSamplingFilter per
-        utterance (bark_hip_generate_batch_filtered; None: the context's filter)."""
+        utterance (bark_hip_generate_batch_filtered; None: the context's filter); voices: one voice.VoicePrompt or None (the context's voice)
+        per utterance (bark_hip_generate_batch_voiced)."""
         n = len(texts)
         ts = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
-        if filters is not None:
+        if voices is not None:
+            assert len(voices) == n and seeds is None
+            keep = [None if v is None else _voice_struct(v) for v in voices]
+            vs = (C.POINTER(BarkHipVoicePrompt) * n)(*[C.POINTER(BarkHipVoicePrompt)() if k is None else C.pointer(k[0]) for k in keep])
+            fl = None
+            if filters is not None:
+                fl = (BarkHipSamplingFilter * n)(*[f if isinstance(f, BarkHipSamplingFilter) else BarkHipSamplingFilter(int(f[0]), float(f[1])) for f in filters])
+            ps = (BarkHipRequestParams * n)(*params) if params is not None else None
+            good = self._lib.bark_hip_generate_batch_voiced(self._h, ts, n, ps, fl, vs)
+        elif filters is not None:
             assert len(filters) == n and seeds is None
             fl = (BarkHipSamplingFilter * n)(*[f if isinstance(f, BarkHipSamplingFilter) else BarkHipSamplingFilter(int(f[0]), float(f[1])) for f in filters])
             ps = (BarkHipRequestParams * n)(*params) if params is not None else None
@@ -448,6 +479,31 @@ class BarkContext:
         """Top-k / nucleus filter of the semantic and coarse samples (rule C8n; top_k 0 and top_p 1.0: off).  Greedy stages are not filtered."""
         if self._lib.bark_hip_set_sampling_filter(self._h, int(top_k), float(top_p)) != 0:
             raise ValueError(f"bark_hip_set_sampling_filter rejected top_k={top_k}, top_p={top_p} (top_k >= 0, 0 < top_p <= 1)")
+
+    def set_voice_prompt(self, voice=None):
+        """The context's voice prompt (rule C10v): a voice.VoicePrompt (semantic [n], coarse [T][2], fine [T][8]); None clears it."""
+        if voice is None:
+            rc = self._lib.bark_hip_set_voice_prompt(self._h, None)
+        else:
+            st, keep = _voice_struct(voice)
+            rc = self._lib.bark_hip_set_voice_prompt(self._h, C.byref(st))
+        if rc != 0:
+            raise ValueError("bark_hip_set_voice_prompt rejected the voice prompt (ids out of range, empty trimmed history, or a history too long for the coarse context)")
+
+    def pick_rows(self, logits, rel, tokens, temp: float = 0.0, u=None):
+        """Kernel-level hook (bark_hip_pick_rows): the fine stage's pick kernels on logits [n_windows * 1024, n_cols]; row z * 1024 + j of the token
+        plane `tokens` receives its pick when j >= rel[z].  Returns (plane int32 [n_windows * 1024], picks settled by the exact path)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        rl = _i32(rel).reshape(-1)
+        assert lg.shape[0] == 1024 * len(rl)
+        tok = _i32(tokens).reshape(-1).copy()
+        assert tok.size == lg.shape[0]
+        uu = None if u is None else np.ascontiguousarray(u, np.float64).reshape(-1)
+        nt = C.c_int32(0)
+        if self._lib.bark_hip_pick_rows(self._h, lg.ctypes.data, len(rl), lg.shape[1], float(temp), None if uu is None else uu.ctypes.data, rl.ctypes.data,
+                                        tok.ctypes.data, C.addressof(nt)) != 0:
+            raise RuntimeError("bark_hip_pick_rows failed")
+        return tok, int(nt.value)
 
     def sample_rows_filtered(self, logits, temp, top_k, top_p, u):
         """Kernel-level hook (bark_hip_sample_rows_filtered): rows of logits [n_rows, n] through the decode loop's filter + sampler launches;
@@ -547,10 +603,20 @@ class Batcher:
         except Exception:
             pass
 
-    def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None) -> int:
+    def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None,
+               voice=None) -> int:
         """top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
-        neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does."""
-        if top_k is not None or top_p is not None:
+        neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does.
+        voice: the request's own voice.VoicePrompt (bark_hip_batcher_submit_voiced; None: the context's)."""
+        if voice is not None:
+            flt = None
+            if top_k is not None or top_p is not None:
+                flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
+            if params is None:
+                params = self._ctx[0].request_params(seed=int(seed))
+            st, keep = _voice_struct(voice)
+            t = self._lib.bark_hip_batcher_submit_voiced(self._b, text.encode("utf-8"), C.byref(params), None if flt is None else C.byref(flt), C.byref(st))
+        elif top_k is not None or top_p is not None:
             flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
             if params is None:
                 params = self._ctx[0].request_params(seed=int(seed))

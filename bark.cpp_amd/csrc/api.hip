@@ -137,6 +137,7 @@ int bark_hip_tokenize(struct bark_context * bctx, const char * text, int32_t * o
         pp.text_pad_token = bctx->params.text_pad_token; pp.semantic_pad_token = bctx->params.semantic_pad_token;
         pp.semantic_infer_token = bctx->params.semantic_infer_token;
         std::vector<int32_t> ids = build_semantic_prompt(bctx->vocab, pp, text, false);
+        engine_voice_into_prompt(bctx->params, bctx->voice.get(), ids);
         memcpy(out513, ids.data(), ids.size() * 4);
         return (int) ids.size();
     });
@@ -299,6 +300,30 @@ int bark_hip_set_sampling_filter(struct bark_context * bctx, int32_t top_k, floa
         bctx->filter = f;
         return 0;
     });
+}
+int bark_hip_set_voice_prompt(struct bark_context * bctx, const struct bark_hip_voice_prompt * voice) {
+    if (!bctx) return -1;
+    return guarded("bark_hip_set_voice_prompt", -1, [&] {
+        VoicePtr v = engine_make_voice(bctx, voice);          // throws on a bad one: the context keeps what it had
+        bctx->voice = v;
+        return 0;
+    }, /*uses_gpu=*/false);
+}
+int bark_hip_generate_batch_voiced(struct bark_context * bctx, const char * const * texts, int n, const struct bark_hip_request_params * per_utterance,
+                                   const struct bark_hip_sampling_filter * filters, const struct bark_hip_voice_prompt * const * voices) {
+    if (!bctx || !texts || n <= 0) return -1;
+    for (int i = 0; i < n; i++) if (!texts[i]) return -1;
+    if (filters) for (int i = 0; i < n; i++) if (!filter_valid(filters[i])) return -1;
+    return guarded("bark_hip_generate_batch_voiced", -1, [&] {
+        std::vector<VoicePtr> vs;
+        if (voices) for (int i = 0; i < n; i++) vs.push_back(engine_make_voice(bctx, voices[i]));
+        return engine_generate_batch(bctx, texts, n, nullptr, per_utterance, nullptr, filters, voices ? vs.data() : nullptr);
+    });
+}
+int bark_hip_pick_rows(struct bark_context * bctx, const float * logits, int n_windows, int n_cols, float temp, const double * u, const int32_t * rel,
+                       int32_t * tokens_io, int32_t * near_ties) {
+    if (!bctx || !logits || !rel || !tokens_io) return -1;
+    return guarded("bark_hip_pick_rows", -1, [&] { engine_pick_rows(bctx, logits, n_windows, n_cols, temp, u, rel, tokens_io, near_ties); return 0; });
 }
 int bark_hip_sample_rows_filtered(struct bark_context * bctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k,
                                   const float * top_p, const double * u, int32_t * out_ids, float * out_eos_p) {

@@ -25,13 +25,14 @@
 using namespace barkhip;
 
 struct bark_hip_batcher {
-    struct Req { std::string text; bark_hip_request_params rp{}; bark_hip_sampling_filter flt{0, 1.0f}; std::vector<float> pcm; bool done = false, ok = false; };
+    struct Req { std::string text; bark_hip_request_params rp{}; bark_hip_sampling_filter flt{0, 1.0f}; VoicePtr voice; std::vector<float> pcm; bool done = false, ok = false; };
     bark_context * ctx = nullptr;                          // worker 0's context (the caller's); request defaults are read from it
     std::vector<bark_context *> ctxs;                      // one per worker; ctxs[1 ..] are clones owned by the batcher ...
     bool owns_workers = true;                              // ... unless the caller brought every context itself (bark_hip_batcher_create_multi: one per GPU)
     // the context's top-k / nucleus filter, copied when the collector is made (the workers own the contexts from then on): what a request without a
     // filter of its own gets, read under `mu` at submit time - nothing is ever written into a running worker's context
     bark_hip_sampling_filter default_filter{0, 1.0f};
+    VoicePtr default_voice;                                // the context's voice prompt, copied the same way (requests without a voice of their own)
     int max_batch = 32;
     std::chrono::microseconds max_wait{2000};
     std::mutex mu;
@@ -59,22 +60,26 @@ struct bark_hip_batcher {
             while (!queue.empty() && (int) batch.size() < job_cap) { batch.push_back(queue.front().second); queue.pop_front(); }
             if (batch.empty()) continue;                         // another worker took what was there
             lk.unlock();
-            std::vector<const char *> texts; std::vector<bark_hip_request_params> rps; std::vector<bark_hip_sampling_filter> flts;
-            for (auto & r : batch) { texts.push_back(r->text.c_str()); rps.push_back(r->rp); flts.push_back(r->flt); }
+            std::vector<const char *> texts; std::vector<bark_hip_request_params> rps; std::vector<bark_hip_sampling_filter> flts; std::vector<VoicePtr> voices;
+            for (auto & r : batch) { texts.push_back(r->text.c_str()); rps.push_back(r->rp); flts.push_back(r->flt); voices.push_back(r->voice); }
+            // every request carries its voice (or none): the worker's own context must not add one of its own
+            const VoicePtr ctx_voice = ctx->voice;
+            ctx->voice.reset();
             // continuous admission: requests that arrive while the job's semantic stage has free slots join it (engine_generate_batch asks here)
             BatchAdmit admit;
             admit.max_job = job_cap;
-            admit.next = [&](std::string & text, bark_hip_request_params & rp, bark_hip_sampling_filter & flt) {
+            admit.next = [&](std::string & text, bark_hip_request_params & rp, bark_hip_sampling_filter & flt, VoicePtr & voice) {
                 std::lock_guard<std::mutex> g(mu);
                 if (queue.empty() || (int) batch.size() >= job_cap) return false;
                 batch.push_back(queue.front().second); queue.pop_front();
-                text = batch.back()->text; rp = batch.back()->rp; flt = batch.back()->flt;
+                text = batch.back()->text; rp = batch.back()->rp; flt = batch.back()->flt; voice = batch.back()->voice;
                 n_admitted++;
                 return true;
             };
             bool failed = false;
-            try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit, flts.data()); }
+            try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit, flts.data(), voices.data()); }
             catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: batch failed: %s\n", e.what()); failed = true; }
+            ctx->voice = ctx_voice;
             lk.lock();
             for (size_t i = 0; i < batch.size(); i++) {
                 Req & r = *batch[i];
@@ -95,6 +100,7 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create_ex(struct bark_contex
     try {
         b->ctx = bctx; b->max_batch = max_batch; b->max_wait = std::chrono::microseconds((int64_t) max_wait_ms * 1000);
         b->default_filter = bctx->filter;
+        b->default_voice = bctx->voice;
         b->ctxs.push_back(bctx);
         for (int i = 1; i < n_streams; i++) {
             b->ctxs.push_back(engine_clone(bctx, (uint32_t) i));
@@ -129,6 +135,7 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create_multi(struct bark_con
     try {
         b->ctx = ctxs[0]; b->max_batch = max_batch; b->max_wait = std::chrono::microseconds((int64_t) max_wait_ms * 1000);
         b->default_filter = ctxs[0]->filter;
+        b->default_voice = ctxs[0]->voice;
         b->owns_workers = false;
         for (int i = 0; i < n_ctx; i++) b->ctxs.push_back(ctxs[i]);
         for (bark_context * c : b->ctxs) engine_reserve_batch(c, std::min(max_batch, 64));
@@ -146,12 +153,14 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create(struct bark_context *
     return bark_hip_batcher_create_ex(bctx, max_batch, max_wait_ms, 1);
 }
 
-static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp, const bark_hip_sampling_filter * flt = nullptr) {
+static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp, const bark_hip_sampling_filter * flt = nullptr,
+                               const VoicePtr * voice = nullptr) {
     auto r = std::make_shared<bark_hip_batcher::Req>();
     r->text = text; r->rp = rp;
     std::lock_guard<std::mutex> lk(b->mu);
     if (b->stop) return -1;
     r->flt = flt ? *flt : b->default_filter;
+    r->voice = voice ? *voice : b->default_voice;
     const int64_t t = b->next_ticket++;
     b->tickets[t] = r;
     b->queue.emplace_back(t, r);
@@ -175,6 +184,17 @@ BARK_API int64_t bark_hip_batcher_submit_filtered(struct bark_hip_batcher * b, c
                                                   const struct bark_hip_sampling_filter * filter) {
     if (!b || !text || (filter && !filter_valid(*filter))) return -1;
     return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter);
+}
+BARK_API int64_t bark_hip_batcher_submit_voiced(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                                const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice) {
+    if (!b || !text || (filter && !filter_valid(*filter))) return -1;
+    VoicePtr v;
+    if (voice) {
+        // checked against the collector's context as it was made (parameters and models are fixed while the collector lives); copies the arrays
+        try { v = engine_make_voice(b->ctx, voice); }
+        catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher_submit_voiced: %s\n", e.what()); return -1; }
+    }
+    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr);
 }
 
 BARK_API int bark_hip_batcher_wait(struct bark_hip_batcher * b, int64_t ticket, float * pcm, int capacity) {

@@ -62,6 +62,11 @@ struct CodecModel {
     struct Block { ConvT up; Conv c1, c2, sc; } blocks[4];
 };
 
+// A voice prompt (rule C10v): the speaker history the three stage loops start from, copied from a bark_hip_voice_prompt.  Held
+// by shared pointer: a context, the utterances of a job and the requests of a collector share one immutable copy.
+struct VoicePrompt { std::vector<int32_t> semantic, coarse, fine; };      // [n_sem], [Tc][2], [Tf][8]
+using VoicePtr = std::shared_ptr<const VoicePrompt>;
+
 }  // namespace barkhip
 
 // The opaque handle of bark.h.
@@ -109,6 +114,9 @@ struct bark_context {
     // settings from d_filter (uploaded at the start of a stage), so only switching the filter on or off needs fresh graphs.
     bark_hip_sampling_filter filter{0, 1.0f};
     int32_t * d_filter = nullptr;                       // [0]: top_k, [1]: top_p (float bits)
+    // speaker history of bark_generate_audio, the stage entry points and the jobs that carry no voices of their own (C10v, bark_hip_set_voice_prompt); null: none
+    barkhip::VoicePtr voice;
+    int32_t * d_fine_rel = nullptr;                     // [1] first position of the current fine window that keeps its pick (read by the captured pick kernels)
     uint16_t * d_gelu_lut = nullptr;
     int max_E = 0, max_H = 0, P = 1024;
     // codec scratch (grown on demand)
@@ -152,7 +160,7 @@ struct bark_context {
         int cap = 0;
         float * x = nullptr, * q = nullptr, * logits = nullptr, * kc = nullptr, * vc = nullptr;
         barkhip::half_t * xn = nullptr, * att = nullptr, * hbuf = nullptr, * q16 = nullptr, * k16 = nullptr, * vt16 = nullptr;
-        int32_t * tokens = nullptr, * picks = nullptr;   // [8][cap * 1024] window ids (codebook-major planes), [cap * 1024] scratch picks
+        int32_t * tokens = nullptr, * rel = nullptr;     // [8][cap * 1024] window ids (codebook-major planes), [cap] first position of each window that keeps its pick
         double * u = nullptr;                            // [6][cap * 1024] uniform draws (fine_temp > 0)
     } fine_batch;
     struct BatchResult { std::vector<int32_t> semantic, coarse, fine; std::vector<float> audio; bool ok = false; };
@@ -183,11 +191,23 @@ int  engine_gpt_eval(bark_context * ctx, int which, const int32_t * tokens, int 
 void engine_fine_eval(bark_context * ctx, const int32_t * tokens_8x1024, int nn, float * logits);
 
 std::vector<int32_t> engine_semantic(bark_context * ctx, const std::vector<int32_t> & prompt, std::vector<float> * eos_trace);
+// coarse and fine start from the context's voice prompt, if it has one (C10v); both return the NEW frames only
 std::vector<int32_t> engine_coarse(bark_context * ctx, const std::vector<int32_t> & semantic);          // [T][2]
 std::vector<int32_t> engine_fine(bark_context * ctx, const std::vector<int32_t> & coarse_Tx2);          // [T][8]
 // the fine stage of several utterances, their windows side by side in every forward pass (f16 model files; per-utterance results are those
-// of engine_fine); rngs: one generator per utterance (fine_temp > 0), advanced as engine_fine advances the context's
-std::vector<std::vector<int32_t>> engine_fine_many(bark_context * ctx, const std::vector<const std::vector<int32_t> *> & coarse, std::vector<std::mt19937> * rngs);
+// of engine_fine); rngs: one generator per utterance (fine_temp > 0), advanced as engine_fine advances the context's; voices: one voice prompt
+// per utterance (entries may be null: no voice), nullptr: the context's for everyone
+std::vector<std::vector<int32_t>> engine_fine_many(bark_context * ctx, const std::vector<const std::vector<int32_t> *> & coarse, std::vector<std::mt19937> * rngs,
+                                                   const std::vector<const VoicePrompt *> * voices = nullptr);
+// checks a voice prompt against the context's parameters and models (ids in range, non-empty trimmed history, history + first coarse window within the
+// coarse context) and copies it; throws on a bad one.  v == nullptr: a null pointer (no voice)
+VoicePtr engine_make_voice(const bark_context * ctx, const bark_hip_voice_prompt * v);
+// ids 256..511 of a 513-id semantic prompt <- the last min(n_sem, 256) history ids, right-padded with semantic_pad_token (C10v.1)
+void engine_voice_into_prompt(const bark_context_params & p, const VoicePrompt * v, std::vector<int32_t> & prompt513);
+// kernel-level hook (tests): the fine stage's pick launches on caller rows - n_windows * 1024 rows of n_cols logits, temp == 0: argmax_rows, else
+// sample_rows_multinomial with u[row]; tokens_io [n_windows * 1024] holds the plane before and after (row z * 1024 + j is written when j >= rel[z])
+void engine_pick_rows(bark_context * ctx, const float * logits, int n_windows, int n_cols, float temp, const double * u, const int32_t * rel, int32_t * tokens_io,
+                      int32_t * near_ties);
 // tap_stage >= 0: *tap receives the activation after that stage (0 first conv, 1 LSTM+skip, 2..5 up-blocks)
 std::vector<float>   engine_codec_decode(bark_context * ctx, const int32_t * codes, int n_q, int T, int tap_stage, std::vector<float> * tap);
 // all utterances of a batch in one pass (codes[b]: [n_q][T[b]]); the launches of one utterance serve all of them
@@ -197,11 +217,12 @@ bool engine_generate(bark_context * ctx, const char * text);
 // seeds: one std::mt19937 seed per utterance (temp > 0); nullptr: drawn from the context's generator, in order.  Returns #ok
 // Continuous admission: while the semantic stage of a job has free slots and nobody of the job waits for them, next() may hand over further
 // requests (false: none pending); they join the job - results are appended behind the n given ones - up to max_job utterances in total.
-struct BatchAdmit { std::function<bool(std::string & text, bark_hip_request_params & rp, bark_hip_sampling_filter & flt)> next; int max_job = 0; };
+struct BatchAdmit { std::function<bool(std::string & text, bark_hip_request_params & rp, bark_hip_sampling_filter & flt, VoicePtr & voice)> next; int max_job = 0; };
 // rps: per-utterance parameters (nullptr: the context's for everyone); seeds override rps[i].seed when both are given;
-// flts: per-utterance top-k / nucleus filters (nullptr: the context's for everyone)
+// flts: per-utterance top-k / nucleus filters (nullptr: the context's for everyone); voices: per-utterance voice prompts (nullptr, or a null entry:
+// the context's)
 int  engine_generate_batch(bark_context * ctx, const char * const * texts, int n, const uint32_t * seeds, const bark_hip_request_params * rps = nullptr,
-                           const BatchAdmit * admit = nullptr, const bark_hip_sampling_filter * flts = nullptr);
+                           const BatchAdmit * admit = nullptr, const bark_hip_sampling_filter * flts = nullptr, const VoicePtr * voices = nullptr);
 // checks a filter (top_k >= 0, 0 < top_p <= 1); false on a bad one
 bool filter_valid(const bark_hip_sampling_filter & f);
 inline bool filter_on(const bark_hip_sampling_filter & f) { return f.top_k > 0 || f.top_p < 1.0f; }

@@ -526,27 +526,37 @@ void run_fine_forward(bark_context * c, int nn, int n_rows, const RowBufs * rbp,
     launch_linear(c->stream, a);                           // lm_heads[codebook_idx - n_codes_given], bark.cpp:1573
 }
 
-FinePlan fine_plan(const bark_context_params & p, const std::vector<int32_t> & coarse) {
+FinePlan fine_plan(const bark_context_params & p, const std::vector<int32_t> & coarse, const VoicePrompt * voice) {
     const int nc = p.n_coarse_codebooks, cs = p.codebook_size;
     FinePlan f;
     f.T = (int) coarse.size() / nc;
     if (f.T <= 0 || f.T > 8192) throw std::runtime_error("fine: number of frames must be in 1..8192");
     for (int32_t v : coarse) if (v < 0 || v >= cs) throw std::runtime_error("fine: coarse code out of range");
-    // in_arr [L][8]: coarse rows, channels 2..7 and the time padding filled with `cs` (bark.cpp:1983-1996)
-    f.L = std::max(f.T, 1024);
+    // C10v: the last n_hist <= 512 rows of the voice prompt's fine history (all 8 codebooks) go in front (HF modeling_bark.py:1158-1176)
+    const int Tf = voice ? (int) voice->fine.size() / 8 : 0;
+    f.n_hist = std::min(Tf, 512);
+    // in_arr [L][8]: history rows, then the coarse rows with channels 2..7 and the time padding filled with `cs` (bark.cpp:1983-1996)
+    f.L = std::max(f.n_hist + f.T, 1024);
     f.in_arr.assign((size_t) f.L * 8, cs);
-    for (int t = 0; t < f.T; t++) for (int ch = 0; ch < nc; ch++) f.in_arr[(size_t) t * 8 + ch] = coarse[(size_t) t * nc + ch];
-    f.n_loops = std::max(0, (int) ceilf((float) (f.L - 1024) / 512.f)) + 1;          // bark.cpp:1998
+    for (int t = 0; t < f.n_hist; t++) for (int ch = 0; ch < 8; ch++) f.in_arr[(size_t) t * 8 + ch] = voice->fine[(size_t) (Tf - f.n_hist + t) * 8 + ch];
+    for (int t = 0; t < f.T; t++) for (int ch = 0; ch < nc; ch++) f.in_arr[(size_t) (f.n_hist + t) * 8 + ch] = coarse[(size_t) t * nc + ch];
+    f.n_loops = std::max(0, (int) ceilf((float) (f.T - (1024 - f.n_hist)) / 512.f)) + 1;          // bark.cpp:1998 with n_hist == 0
     return f;
+}
+std::vector<int32_t> fine_plan_result(FinePlan & f) {
+    f.in_arr.erase(f.in_arr.begin(), f.in_arr.begin() + (long) f.n_hist * 8);                  // the history rows ...
+    f.in_arr.resize((size_t) f.T * 8);                                                          // ... and the time padding are not part of the result
+    return std::move(f.in_arr);
 }
 // window n (bark.cpp:2002-2013).  T <= 1024: one window, start_idx == 0, rel == 0.  For longer inputs the reference
 // stores its samples at [rel + i] and runs out of the buffer (undefined behaviour); this engine and
 // the oracle implement the algorithm it was ported from (suno-ai/bark generate_fine): all 1024 positions are sampled
-// (the random stream advances as in the reference) and positions >= rel keep their sample.
+// (the random stream advances as in the reference) and positions >= rel keep their sample.  With a voice prompt (C10v) the
+// fill starts behind the n_hist history rows: rel == n_hist on every window but a short last one, where it is larger.
 FineWindow fine_window(const FinePlan & f, int n) {
     FineWindow w;
     w.start_idx = std::min(n * 512, f.L - 1024);
-    w.start_fill_idx = std::min(n * 512, f.L - 512);
+    w.start_fill_idx = std::min(f.n_hist + n * 512, f.L - 512);
     w.rel = w.start_fill_idx - w.start_idx;
     return w;
 }
@@ -555,7 +565,7 @@ void fine_window_tokens(const FinePlan & f, const FineWindow & w, int32_t * tok,
 }
 void fine_write_back(FinePlan & f, const FineWindow & w, const bark_context_params & p, const int32_t * tok, size_t plane) {
     for (int nn = p.n_coarse_codebooks; nn < p.n_fine_codebooks; nn++)                       // bark.cpp:2041-2046
-        for (int j = 0; j < p.codebook_size - w.rel; j++) f.in_arr[(size_t) (w.start_fill_idx + j) * 8 + nn] = tok[(size_t) nn * plane + w.rel + j];
+        for (int j = 0; j < 1024 - w.rel; j++) f.in_arr[(size_t) (w.start_fill_idx + j) * 8 + nn] = tok[(size_t) nn * plane + w.rel + j];
 }
 }  // namespace detail
 
@@ -639,6 +649,67 @@ std::vector<int32_t> engine_semantic(bark_context * c, const std::vector<int32_t
 }
 
 // ---------------------------------------------------------------------------------------------------
+// voice prompts (rule C10v; suno-ai/bark generation.py generate_text_semantic / generate_coarse / generate_fine)
+// ---------------------------------------------------------------------------------------------------
+namespace detail {
+VoiceTrim voice_trim(const bark_context_params & p, const VoicePrompt * v) {
+    VoiceTrim t;
+    if (!v) return t;
+    const int nc = p.n_coarse_codebooks;
+    const float stc_ratio = p.coarse_rate_hz / p.semantic_rate_hz * nc;                                          // as engine_coarse
+    const int n_sem = (int) v->semantic.size(), n_flat = (int) v->coarse.size();
+    const int n_sh = std::min(std::min((int) floorf(p.max_coarse_history / stc_ratio), n_sem - n_sem % 2), (int) floorf(n_flat / stc_ratio));
+    const int n_ch = (int) roundf(n_sh * stc_ratio);
+    // python's x[-0:] would take the whole array here, which nobody means
+    if (n_sh < 2 || n_ch <= 2 || n_ch > n_flat) throw std::runtime_error("voice prompt: the trimmed coarse history is empty");
+    t.sem.assign(v->semantic.end() - n_sh, v->semantic.end());
+    // the last n_ch interleaved ids, as the offset ids the model is fed, minus the last two (Suno's time-alignment step)
+    for (int k = n_flat - n_ch; k < n_flat - 2; k++) t.coarse.push_back(p.semantic_vocab_size + p.codebook_size * (k % nc) + v->coarse[(size_t) k]);
+    return t;
+}
+std::vector<int32_t> coarse_window_prompt(const bark_context_params & p, const VoiceTrim & vt, const std::vector<int32_t> & semantic, const std::vector<int32_t> & out, int step_idx) {
+    const float stc_ratio = p.coarse_rate_hz / p.semantic_rate_hz * p.n_coarse_codebooks;                        // bark.cpp:1757
+    const int max_semantic_history = (int) floorf(p.max_coarse_history / stc_ratio);
+    // window prompt (bark.cpp:1787-1807) over [semantic history ; semantic] and [coarse history ; generated so far]
+    const int n_sh = (int) vt.sem.size(), n_all = n_sh + (int) semantic.size();
+    const int semantic_idx = n_sh + (int) roundf(step_idx / stc_ratio);
+    std::vector<int32_t> in;
+    in.reserve(257 + (size_t) p.max_coarse_history);
+    for (int i = std::max(semantic_idx - max_semantic_history, 0); i < n_all && in.size() < 256; i++) in.push_back(i < n_sh ? vt.sem[(size_t) i] : semantic[(size_t) (i - n_sh)]);
+    in.resize(256, p.coarse_semantic_pad_token);
+    in.push_back(p.coarse_infer_token);
+    const int n_vc = (int) vt.coarse.size(), total = n_vc + (int) out.size();
+    for (int k = total - std::min(p.max_coarse_history, total); k < total; k++) in.push_back(k < n_vc ? vt.coarse[(size_t) k] : out[(size_t) (k - n_vc)]);
+    return in;
+}
+}  // namespace detail
+
+VoicePtr engine_make_voice(const bark_context * c, const bark_hip_voice_prompt * v) {
+    if (!v) return VoicePtr();
+    const bark_context_params & p = c->params;
+    if (p.n_coarse_codebooks != 2 || p.n_fine_codebooks != 8 || p.codebook_size != 1024) throw std::runtime_error("voice prompt: only 2 -> 8 codebooks of 1024 entries are supported");
+    if (v->n_semantic < 0 || v->n_coarse_frames < 0 || v->n_fine_frames < 0 || v->n_semantic > (1 << 20) || v->n_coarse_frames > (1 << 20) || v->n_fine_frames > (1 << 20) ||
+        (v->n_semantic && !v->semantic) || (v->n_coarse_frames && !v->coarse_Tx2) || (v->n_fine_frames && !v->fine_Tx8))
+        throw std::runtime_error("voice prompt: bad counts or null arrays");
+    auto vp = std::make_shared<VoicePrompt>();
+    vp->semantic.assign(v->semantic, v->semantic + v->n_semantic);
+    vp->coarse.assign(v->coarse_Tx2, v->coarse_Tx2 + (size_t) v->n_coarse_frames * 2);
+    vp->fine.assign(v->fine_Tx8, v->fine_Tx8 + (size_t) v->n_fine_frames * 8);
+    check_ids(vp->semantic.data(), vp->semantic.size(), p.semantic_vocab_size, "voice prompt (semantic)");
+    check_ids(vp->coarse.data(), vp->coarse.size(), p.codebook_size, "voice prompt (coarse)");
+    check_ids(vp->fine.data(), vp->fine.size(), p.codebook_size, "voice prompt (fine)");
+    const VoiceTrim t = voice_trim(p, vp.get());
+    if (p.sliding_window_size > 0 && 257 + std::min(p.max_coarse_history, (int) t.coarse.size()) + p.sliding_window_size - 1 > c->gpt[1].hp.block_size)
+        throw std::runtime_error("voice prompt: the history and the first coarse window exceed the coarse model's context");
+    return vp;
+}
+void engine_voice_into_prompt(const bark_context_params & p, const VoicePrompt * v, std::vector<int32_t> & prompt) {
+    if (!v || prompt.size() != 513) return;
+    const int n = std::min((int) v->semantic.size(), 256);
+    for (int i = 0; i < 256; i++) prompt[(size_t) 256 + i] = i < n ? v->semantic[v->semantic.size() - (size_t) n + i] : p.semantic_pad_token;      // HF modeling_bark.py:570-577
+}
+
+// ---------------------------------------------------------------------------------------------------
 // coarse stage: bark_eval_coarse_encoder (bark.cpp:1745-1863)
 // ---------------------------------------------------------------------------------------------------
 std::vector<int32_t> engine_coarse(bark_context * c, const std::vector<int32_t> & semantic) {
@@ -651,9 +722,9 @@ std::vector<int32_t> engine_coarse(bark_context * c, const std::vector<int32_t> 
     const StageCfg s = stage_cfg(c, 1);
     if (s.lm_row0 + 2 * s.lm_rows > m.hp.n_out_vocab) throw std::runtime_error("coarse: vocabulary too small");
     const float stc_ratio = p.coarse_rate_hz / p.semantic_rate_hz * p.n_coarse_codebooks;                        // bark.cpp:1757
-    const int max_semantic_history = (int) floorf(p.max_coarse_history / stc_ratio);
     const int n_steps = (int) (floorf(semantic.size() * stc_ratio / p.n_coarse_codebooks) * p.n_coarse_codebooks);  // bark.cpp:1775-1779
     if (n_steps <= 0) throw std::runtime_error("coarse: no steps to run");
+    const VoiceTrim voice = voice_trim(p, c->voice.get());      // C10v: empty without a voice prompt
     const int n_windows = (int) ceilf((float) n_steps / p.sliding_window_size);
     const bool greedy = p.temp == 0.0f || !c->host_sampling;
     if (p.temp != 0.0f && greedy) upload_uniforms(c, n_steps);
@@ -663,18 +734,11 @@ std::vector<int32_t> engine_coarse(bark_context * c, const std::vector<int32_t> 
     const bool reuse_prefix = !(crosscheck_mask() & 8);
     int step_idx = 0;
     for (int w = 0; w < n_windows; w++) {
-        // window prompt (bark.cpp:1787-1807)
-        const int semantic_idx = (int) roundf(step_idx / stc_ratio);
-        std::vector<int32_t> in(semantic.begin() + std::max(semantic_idx - max_semantic_history, 0), semantic.end());
-        const size_t had = in.size();
-        in.resize(256);
-        for (size_t i = had; i < 256; i++) in[i] = p.coarse_semantic_pad_token;
-        in.push_back(p.coarse_infer_token);
-        const int nh = std::min(p.max_coarse_history, (int) out.size());
-        in.insert(in.end(), out.end() - nh, out.end());
+        const std::vector<int32_t> in = coarse_window_prompt(p, voice, semantic, out, step_idx);
         const int N = (int) in.size();
         const int steps_here = std::min(p.sliding_window_size, n_steps - step_idx);
-        if (N + steps_here - 1 > m.hp.block_size) throw std::runtime_error("coarse: window exceeds the context");
+        if (N + steps_here - 1 > m.hp.block_size)
+            throw std::runtime_error(w == 0 && !voice.coarse.empty() ? "coarse: the voice prompt's history and the first window exceed the context" : "coarse: window exceeds the context");
         check_ids(in.data(), in.size(), m.hp.n_in_vocab, "coarse");
         // Prefix reuse: the cache still holds the rows of the previous window's prompt and of the tokens decoded after
         // it.  While the semantic slice does not move and the history is not truncated, the new prompt is that very
@@ -758,7 +822,7 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
     GptModel & m = c->gpt[2];
     const int nc = p.n_coarse_codebooks, nf = p.n_fine_codebooks, cs = p.codebook_size;
     if (nc != 2 || nf != 8 || cs != 1024) throw std::runtime_error("fine: only 2 -> 8 codebooks of 1024 entries are supported");
-    FinePlan plan = fine_plan(p, coarse);
+    FinePlan plan = fine_plan(p, coarse, c->voice.get());
     const int n_loops = plan.n_loops;
     const bool greedy = p.fine_temp == 0.0f;
     const bool device_multinomial = !greedy && !c->host_sampling;
@@ -769,20 +833,21 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
         const FineWindow w = fine_window(plan, n);
         const int rel = w.rel;
         fine_window_tokens(plan, w, buf.data(), 1024);
+        HIP_OK(hipMemcpyAsync(c->d_fine_rel, &w.rel, 4, hipMemcpyHostToDevice, c->stream));      // read by the pick kernels; complete when upload_tokens returns
         upload_tokens(c, buf.data(), buf.size());
         if (device_multinomial) upload_uniforms(c, (nf - nc) * 1024);
         for (int nn = nc; nn < nf; nn++) {
             progress(c, FINE, 100 * (n * (nf - nc) + (nn - nc + 1)) / (n_loops * (nf - nc)));
-            // rel > 0 (only the last windows of a long input): picks go to a scratch row, then positions >= rel are copied in
-            int32_t * pick_dst = rel == 0 ? c->d_tokens + (size_t) nn * 1024 : c->d_out_tokens;
             if (greedy || device_multinomial) {
-                // one pass = embed -> 12 layers -> head -> per-row pick, captured once per codebook as a hipGraph
+                // one pass = embed -> 12 layers -> head -> per-row pick, captured once per codebook as a hipGraph.  The picks go straight into the token
+                // plane: positions below the window's rel (d_fine_rel: a long input's last windows, every window under a voice prompt) keep their ids
+                int32_t * pick_dst = c->d_tokens + (size_t) nn * 1024;
                 auto enqueue = [&] {
                     run_fine_forward(c, nn, cs);               // only logits [0, 1024) of each row are sampled (bark.cpp:2031)
-                    if (greedy) launch_argmax_rows(c->stream, c->logits, cs, 1024, cs, pick_dst, 1, c->d_state);
-                    else launch_sample_rows_multinomial(c->stream, c->logits, cs, 1024, cs, p.fine_temp, c->d_u + (size_t) (nn - nc) * 1024, pick_dst, 1, c->d_state);
+                    if (greedy) launch_argmax_rows(c->stream, c->logits, cs, 1024, cs, pick_dst, 1, c->d_state, c->d_fine_rel);
+                    else launch_sample_rows_multinomial(c->stream, c->logits, cs, 1024, cs, p.fine_temp, c->d_u + (size_t) (nn - nc) * 1024, pick_dst, 1, c->d_state, c->d_fine_rel);
                 };
-                if (c->use_graph && rel == 0) {
+                if (c->use_graph) {
                     hipGraphExec_t & g = c->fine_graphs[nn + (fine_products_on_f16_mfma(c, m, false) ? 8 : 0)];
                     if (!g) g = capture_graph(c->stream, enqueue);
                     HIP_OK(hipGraphLaunch(g, c->stream));
@@ -790,8 +855,6 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
                 } else {
                     enqueue();
                 }
-                if (rel > 0)
-                    HIP_OK(hipMemcpyAsync(c->d_tokens + (size_t) nn * 1024 + rel, c->d_out_tokens + rel, (size_t) (1024 - rel) * 4, hipMemcpyDeviceToDevice, c->stream));
             } else {
                 const int n_out = m.hp.n_out_vocab;
                 run_fine_forward(c, nn, n_out);
@@ -813,8 +876,7 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
     }
     const StepState cur = get_state(c);
     c->stats.n_near_tie += cur.near_tie;
-    plan.in_arr.resize((size_t) plan.T * 8);                                                 // strip the time padding
-    return std::move(plan.in_arr);
+    return fine_plan_result(plan);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -833,7 +895,7 @@ void ensure_fine_batch(bark_context * c, int Z) {
     fb.kc = dev_alloc<float>(c, (size_t) Z * E * c->P); fb.vc = dev_alloc<float>(c, (size_t) Z * E * c->P);
     if (c->fast_gemm) { fb.q16 = dev_alloc<half_t>(c, R * E); fb.k16 = dev_alloc<half_t>(c, R * E); fb.vt16 = dev_alloc<half_t>(c, R * E); }
     fb.logits = dev_alloc<float>(c, R * 1024);
-    fb.tokens = dev_alloc<int32_t>(c, 8 * R); fb.picks = dev_alloc<int32_t>(c, R);
+    fb.tokens = dev_alloc<int32_t>(c, 8 * R); fb.rel = dev_alloc<int32_t>(c, (size_t) Z);
     fb.u = dev_alloc<double>(c, 6 * R);
     fb.cap = Z;                                             // (a smaller earlier allocation stays with the context until it is freed)
 }
@@ -845,7 +907,8 @@ RowBufs fine_batch_rows(bark_context * c, int Z) {
 }
 }  // namespace detail
 
-std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::vector<const std::vector<int32_t> *> & coarse, std::vector<std::mt19937> * rngs) {
+std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::vector<const std::vector<int32_t> *> & coarse, std::vector<std::mt19937> * rngs,
+                                                   const std::vector<const VoicePrompt *> * voices) {
     HIP_OK(hipSetDevice(c->device));
     const bark_context_params & p = c->params;
     GptModel & m = c->gpt[2];
@@ -856,10 +919,11 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
     const int U = (int) coarse.size();
     const bool greedy = p.fine_temp == 0.0f;
     if (!greedy && (!rngs || (int) rngs->size() != U)) throw std::runtime_error("fine_many: one generator per utterance is needed for fine_temp > 0");
+    if (voices && (int) voices->size() != U) throw std::runtime_error("fine_many: one voice entry per utterance");
     std::vector<FinePlan> us((size_t) U);
     int max_loops = 0;
     for (int u = 0; u < U; u++) {
-        us[(size_t) u] = fine_plan(p, *coarse[(size_t) u]);
+        us[(size_t) u] = fine_plan(p, *coarse[(size_t) u], voices ? (*voices)[(size_t) u] : c->voice.get());
         max_loops = std::max(max_loops, us[(size_t) u].n_loops);
     }
     ensure_fine_batch(c, U);
@@ -874,14 +938,15 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
         for (int u = 0; u < U; u++) if (n < us[(size_t) u].n_loops) act.push_back(u);
         const int Z = (int) act.size(), R = Z * 1024;
         buf.assign((size_t) 8 * R, cs);
-        bool any_rel = false;
+        std::vector<int32_t> rels;
         for (int z = 0; z < Z; z++) {
             const FinePlan & t = us[(size_t) act[(size_t) z]];
             win.push_back(fine_window(t, n));
-            any_rel = any_rel || win.back().rel > 0;
+            rels.push_back(win.back().rel);
             fine_window_tokens(t, win.back(), buf.data() + (size_t) z * 1024, (size_t) R);
         }
         HIP_OK(hipMemcpyAsync(fb.tokens, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(fb.rel, rels.data(), rels.size() * 4, hipMemcpyHostToDevice, c->stream));
         if (!greedy) {
             // utterance z draws (nf - nc) * 1024 uniforms per window, codebook-major, from a COPY of its generator (upload_uniforms)
             ubuf.assign((size_t) 6 * R, 0.0);
@@ -895,16 +960,12 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
         const RowBufs rb = fine_batch_rows(c, Z);
         for (int nn = nc; nn < nf; nn++) {
             progress(c, FINE, 100 * (n * (nf - nc) + (nn - nc + 1)) / (max_loops * (nf - nc)));
-            // a window with rel > 0 (the last ones of a long utterance) keeps the positions below rel: picks go to a scratch row first
-            int32_t * pick_dst = any_rel ? fb.picks : fb.tokens + (size_t) nn * R;
+            // window z keeps the positions below fb.rel[z] (the last windows of a long utterance, every window under a voice prompt): the pick
+            // kernels store the others straight into the token plane
+            int32_t * pick_dst = fb.tokens + (size_t) nn * R;
             run_fine_forward(c, nn, cs, &rb, Z);
-            if (greedy) launch_argmax_rows(c->stream, fb.logits, cs, R, cs, pick_dst, 1, c->d_state);
-            else launch_sample_rows_multinomial(c->stream, fb.logits, cs, R, cs, p.fine_temp, fb.u + (size_t) (nn - nc) * R, pick_dst, 1, c->d_state);
-            if (any_rel)
-                for (int z = 0; z < Z; z++) {
-                    const size_t at = (size_t) z * 1024 + (size_t) win[(size_t) z].rel;
-                    HIP_OK(hipMemcpyAsync(fb.tokens + (size_t) nn * R + at, fb.picks + at, (size_t) (1024 - win[(size_t) z].rel) * 4, hipMemcpyDeviceToDevice, c->stream));
-                }
+            if (greedy) launch_argmax_rows(c->stream, fb.logits, cs, R, cs, pick_dst, 1, c->d_state, fb.rel);
+            else launch_sample_rows_multinomial(c->stream, fb.logits, cs, R, cs, p.fine_temp, fb.u + (size_t) (nn - nc) * R, pick_dst, 1, c->d_state, fb.rel);
             c->stats.n_sample_fine += R;
         }
         HIP_OK(hipMemcpyAsync(buf.data(), fb.tokens, buf.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -917,8 +978,31 @@ std::vector<std::vector<int32_t>> engine_fine_many(bark_context * c, const std::
     const StepState cur = get_state(c);
     c->stats.n_near_tie += cur.near_tie;
     std::vector<std::vector<int32_t>> out((size_t) U);
-    for (int u = 0; u < U; u++) { us[(size_t) u].in_arr.resize((size_t) us[(size_t) u].T * 8); out[(size_t) u] = std::move(us[(size_t) u].in_arr); }
+    for (int u = 0; u < U; u++) out[(size_t) u] = fine_plan_result(us[(size_t) u]);
     return out;
+}
+
+// kernel-level hook: the fine stage's pick launches on caller rows (bark_hip_pick_rows)
+void engine_pick_rows(bark_context * c, const float * logits, int n_windows, int n_cols, float temp, const double * u, const int32_t * rel, int32_t * tokens_io,
+                      int32_t * near_ties) {
+    if (n_windows < 1 || n_windows > 64 || n_cols < 1 || n_cols > 1024 || !(temp >= 0.0f) || (temp > 0.0f && !u)) throw std::runtime_error("pick_rows: bad arguments");
+    for (int z = 0; z < n_windows; z++) if (rel[z] < 0 || rel[z] > 1024) throw std::runtime_error("pick_rows: rel must be in 0..1024");
+    HIP_OK(hipSetDevice(c->device));
+    const size_t R = (size_t) n_windows * 1024;
+    struct Buf { void * p = nullptr; ~Buf() { if (p) (void) hipFree(p); } };
+    Buf b_l, b_u, b_rel, b_tok;
+    HIP_OK(hipMalloc(&b_l.p, R * n_cols * 4)); HIP_OK(hipMalloc(&b_u.p, R * 8)); HIP_OK(hipMalloc(&b_rel.p, (size_t) n_windows * 4)); HIP_OK(hipMalloc(&b_tok.p, R * 4));
+    hipStream_t st = c->stream;
+    HIP_OK(hipMemcpyAsync(b_l.p, logits, R * n_cols * 4, hipMemcpyHostToDevice, st));
+    if (temp > 0.0f) HIP_OK(hipMemcpyAsync(b_u.p, u, R * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(b_rel.p, rel, (size_t) n_windows * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(b_tok.p, tokens_io, R * 4, hipMemcpyHostToDevice, st));
+    set_state(c, fresh_state());
+    if (temp == 0.0f) launch_argmax_rows(st, (const float *) b_l.p, n_cols, (int) R, n_cols, (int32_t *) b_tok.p, 1, c->d_state, (const int32_t *) b_rel.p);
+    else launch_sample_rows_multinomial(st, (const float *) b_l.p, n_cols, (int) R, n_cols, temp, (const double *) b_u.p, (int32_t *) b_tok.p, 1, c->d_state, (const int32_t *) b_rel.p);
+    HIP_OK(hipMemcpyAsync(tokens_io, b_tok.p, R * 4, hipMemcpyDeviceToHost, st));
+    const StepState cur = get_state(c);
+    if (near_ties) *near_ties = cur.near_tie;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -935,6 +1019,7 @@ bool engine_generate(bark_context * c, const char * text) {
     pp.block_size = c->gpt[0].hp.block_size; pp.text_encoding_offset = c->params.text_encoding_offset; pp.text_pad_token = c->params.text_pad_token;
     pp.semantic_pad_token = c->params.semantic_pad_token; pp.semantic_infer_token = c->params.semantic_infer_token;
     c->tokens = build_semantic_prompt(c->vocab, pp, text, true);
+    engine_voice_into_prompt(c->params, c->voice.get(), c->tokens);
     if (c->params.verbosity >= MEDIUM) {
         fprintf(stderr, "bark_tokenize_input: prompt: '%s'\nbark_tokenize_input: number of tokens in prompt = %zu, first 8 tokens:", text, c->tokens.size());
         for (int i = 0; i < 8 && i < (int) c->tokens.size(); i++) fprintf(stderr, " %d", c->tokens[(size_t) i]);

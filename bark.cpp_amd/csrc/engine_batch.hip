@@ -497,6 +497,8 @@ struct Utt {
     std::string text;
     bark_hip_request_params rp{};
     bark_hip_sampling_filter flt{0, 1.0f};               // top-k / nucleus filter of its semantic and coarse samples
+    VoicePtr voice;                                      // its voice prompt (C10v; null: none) and what the coarse stage keeps of it
+    VoiceTrim vt;
     std::mt19937 rng;
     std::vector<int32_t> coarse_out;                     // raw coarse ids of the windows done so far
     std::vector<int32_t> cached;                         // coarse: ids whose K / V rows sit in the utterance's slot cache
@@ -639,15 +641,18 @@ struct JobTail {
         if (many) {
             std::vector<const std::vector<int32_t> *> co;
             std::vector<std::mt19937> rr;
-            for (int b : take) { co.push_back(&c->batch_results[(size_t) b].coarse); rr.push_back(us[(size_t) b].rng); }
-            std::vector<std::vector<int32_t>> fine = engine_fine_many(t, co, &rr);
+            std::vector<const VoicePrompt *> vo;
+            for (int b : take) { co.push_back(&c->batch_results[(size_t) b].coarse); rr.push_back(us[(size_t) b].rng); vo.push_back(us[(size_t) b].voice.get()); }
+            std::vector<std::vector<int32_t>> fine = engine_fine_many(t, co, &rr, &vo);
             for (size_t k = 0; k < take.size(); k++) { c->batch_results[(size_t) take[k]].fine = std::move(fine[k]); us[(size_t) take[k]].rng = rr[k]; }
         } else {
             for (int b : take) {
                 bark_context::BatchResult & r = c->batch_results[(size_t) b];
-                std::swap(t->rng, us[(size_t) b].rng);                                // the fine stage draws from the utterance's generator
-                try { r.fine = engine_fine(t, r.coarse); } catch (...) { std::swap(t->rng, us[(size_t) b].rng); throw; }
+                std::swap(t->rng, us[(size_t) b].rng);                                // the fine stage draws from the utterance's generator ...
+                std::swap(t->voice, us[(size_t) b].voice);                            // ... and starts from its voice prompt
+                try { r.fine = engine_fine(t, r.coarse); } catch (...) { std::swap(t->rng, us[(size_t) b].rng); std::swap(t->voice, us[(size_t) b].voice); throw; }
                 std::swap(t->rng, us[(size_t) b].rng);
+                std::swap(t->voice, us[(size_t) b].voice);
             }
         }
         t->stats.t_fine_us += now_us() - t0;
@@ -717,7 +722,7 @@ struct JobTail {
 // finished (its own step cap / stop rule, its own number of coarse windows) is handed to the next waiting utterance, and once nobody
 // waits the batch is compacted (the last slot moves into the hole), so every lock step runs over live utterances only.
 int engine_generate_batch(bark_context * c, const char * const * texts, int n, const uint32_t * seeds, const bark_hip_request_params * rps, const BatchAdmit * admit,
-                          const bark_hip_sampling_filter * flts) {
+                          const bark_hip_sampling_filter * flts, const VoicePtr * voices) {
     HIP_OK(hipSetDevice(c->device));
     const JobScope job(c);
     const bark_context_params & p = c->params;
@@ -736,6 +741,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
         if (!(u.rp.temp >= 0.0f) || !(u.rp.fine_temp >= 0.0f)) throw std::runtime_error("generate_batch: temperatures must be >= 0");
         u.flt = flts ? flts[i] : c->filter;
         if (!filter_valid(u.flt)) throw std::runtime_error("generate_batch: top_k must be >= 0 and top_p in (0, 1]");
+        u.voice = voices && voices[i] ? voices[i] : c->voice;
         u.rng = std::mt19937(u.rp.seed);
     }
     if (c->host_sampling || c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd || c->any_w32) {
@@ -750,10 +756,12 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             if (c->params.temp != u.rp.temp || c->params.fine_temp != u.rp.fine_temp || c->params.min_eos_p != u.rp.min_eos_p || filter_on(c->filter) != filter_on(u.flt))
                 engine_invalidate_graphs(c);
             c->filter = u.flt;
+            std::swap(c->voice, u.voice);
             c->params.temp = u.rp.temp; c->params.fine_temp = u.rp.fine_temp; c->params.min_eos_p = u.rp.min_eos_p; c->params.n_steps_text_encoder = u.rp.n_steps_text_encoder;
             std::swap(c->rng, u.rng);
-            try { r.ok = engine_generate(c, u.text.c_str()); } catch (...) { std::swap(c->rng, u.rng); c->params = saved; c->filter = saved_flt; engine_invalidate_graphs(c); throw; }
+            try { r.ok = engine_generate(c, u.text.c_str()); } catch (...) { std::swap(c->rng, u.rng); std::swap(c->voice, u.voice); c->params = saved; c->filter = saved_flt; engine_invalidate_graphs(c); throw; }
             std::swap(c->rng, u.rng);
+            std::swap(c->voice, u.voice);
             if (r.ok) { r.semantic = c->semantic_tokens; r.coarse = c->coarse_tokens; r.fine = c->fine_tokens; r.audio = c->audio; good++; }
         }
         if (c->params.temp != saved.temp || c->params.fine_temp != saved.fine_temp || c->params.min_eos_p != saved.min_eos_p || filter_on(c->filter) != filter_on(saved_flt))
@@ -806,7 +814,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             // that arrived in the meantime join the job - they ride along through the remaining stages
             while (admit && queue.empty() && (int) slot_utt.size() < S && n < admit->max_job) {
                 Utt u;
-                if (!admit->next(u.text, u.rp, u.flt)) break;
+                if (!admit->next(u.text, u.rp, u.flt, u.voice)) break;
                 u.rng = std::mt19937(u.rp.seed);
                 u.cap = std::max(0, std::min(u.rp.n_steps_text_encoder, cap_max));
                 us.push_back(std::move(u)); c->batch_results.emplace_back(); prompts.emplace_back();
@@ -822,6 +830,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
                     set_slot_params(c, slot, u);
                     if (u.rp.temp > 0.0f) upload_slot_uniforms(c, slot, u.rng, u.cap);
                     prompts[(size_t) slot_utt[(size_t) slot]] = build_semantic_prompt(c->vocab, pp, u.text.c_str(), true);
+                    engine_voice_into_prompt(p, u.voice.get(), prompts[(size_t) slot_utt[(size_t) slot]]);
                     u.issued = 1;
                 }
                 upload_slot_params(c);
@@ -879,7 +888,6 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             throw std::runtime_error("coarse: unsupported parameters");
         if (s.lm_row0 + 2 * s.lm_rows > m.hp.n_out_vocab) throw std::runtime_error("coarse: vocabulary too small");
         const float stc_ratio = p.coarse_rate_hz / p.semantic_rate_hz * p.n_coarse_codebooks;
-        const int max_semantic_history = (int) floorf(p.max_coarse_history / stc_ratio);
         std::deque<int> queue;
         long total_steps = 0, done_steps = 0;
         for (int i = 0; i < n; i++) {
@@ -887,6 +895,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             if (sem.empty()) continue;
             us[(size_t) i].n_steps = (int) (floorf(sem.size() * stc_ratio / p.n_coarse_codebooks) * p.n_coarse_codebooks);
             if (us[(size_t) i].n_steps > 0) { queue.push_back(i); total_steps += us[(size_t) i].n_steps; }
+            us[(size_t) i].vt = voice_trim(p, us[(size_t) i].voice.get());
         }
         const bool reuse_prefix = !(crosscheck_mask() & 8);
         std::vector<int> slot_utt;
@@ -914,14 +923,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
                 Utt & u = us[(size_t) slot_utt[(size_t) b]];
                 const auto & sem = c->batch_results[(size_t) slot_utt[(size_t) b]].semantic;
                 const auto & out = u.coarse_out;
-                const int semantic_idx = (int) roundf(u.step_idx / stc_ratio);
-                std::vector<int32_t> in(sem.begin() + std::max(semantic_idx - max_semantic_history, 0), sem.end());
-                const size_t had = in.size();
-                in.resize(256);
-                for (size_t i = had; i < 256; i++) in[i] = p.coarse_semantic_pad_token;
-                in.push_back(p.coarse_infer_token);
-                const int nh = std::min(p.max_coarse_history, (int) out.size());
-                in.insert(in.end(), out.end() - nh, out.end());
+                std::vector<int32_t> in = coarse_window_prompt(p, u.vt, sem, out, u.step_idx);
                 here[(size_t) b] = std::min(p.sliding_window_size, u.n_steps - u.step_idx);
                 if ((int) in.size() + here[(size_t) b] - 1 > m.hp.block_size) throw std::runtime_error("coarse: window exceeds the context");
                 check_ids(in.data(), in.size(), m.hp.n_in_vocab, "coarse");
@@ -938,7 +940,14 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             }
             // a slot whose last window is shorter than the others' steps on to the end of the window: its rows must fit its context too
             for (int b = 0; b < B; b++)
-                if ((int) ins[(size_t) b].size() + max_here - 1 > m.hp.block_size) throw std::runtime_error("coarse: a lock-step window exceeds the context of a slot (history + sliding window too long for a batch)");
+                if ((int) ins[(size_t) b].size() + max_here - 1 > m.hp.block_size) {
+                    const Utt & u = us[(size_t) slot_utt[(size_t) b]];
+                    // rows a window without the voice prompt's history would need: when those fit, the history is what overflows
+                    const int own = 257 + std::min(p.max_coarse_history, (int) u.coarse_out.size());
+                    throw std::runtime_error(!u.vt.coarse.empty() && own + max_here - 1 <= m.hp.block_size
+                        ? "coarse: the voice prompt's history makes a lock-step window exceed the context of a slot (history + sliding window too long for a batch)"
+                        : "coarse: a lock-step window exceeds the context of a slot (history + sliding window too long for a batch)");
+                }
             int lock_steps = max_here - 1;                               // batched steps after every slot has its first sample
             std::vector<int> pf_slots, pf_L, pf_step; std::vector<const std::vector<int32_t> *> pf_ids;
             // states of the slots that continue with a decode step: uploaded without a host synchronisation per slot (64 slots x 13 windows of

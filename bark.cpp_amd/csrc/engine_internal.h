@@ -153,10 +153,20 @@ void progress(bark_context * c, bark_encoding_step step, int pct);
 void run_fine_forward(bark_context * c, int nn, int n_rows, const RowBufs * rb = nullptr, int Z = 1);
 // The fine stage's plan of one utterance (bark_eval_fine_encoder, bark.cpp:1961-2059): T frames in L = max(T, 1024) rows of in_arr [L][8], n_loops
 // windows of 1024 rows with a hop of 512; window n reads rows from start_idx and keeps the picks of its positions >= rel (rows from start_fill_idx)
-struct FinePlan { int T = 0, L = 0, n_loops = 0; std::vector<int32_t> in_arr; };
+// With a voice prompt (C10v) its last n_hist <= 512 fine rows sit in front: L = max(n_hist + T, 1024), the fill starts at row n_hist, the result is rows
+// n_hist .. n_hist + T (fine_plan_result)
+struct FinePlan { int T = 0, L = 0, n_loops = 0, n_hist = 0; std::vector<int32_t> in_arr; };
 struct FineWindow { int start_idx, start_fill_idx, rel; };
-FinePlan fine_plan(const bark_context_params & p, const std::vector<int32_t> & coarse);
+FinePlan fine_plan(const bark_context_params & p, const std::vector<int32_t> & coarse, const VoicePrompt * voice = nullptr);
+std::vector<int32_t> fine_plan_result(FinePlan & f);
 FineWindow fine_window(const FinePlan & f, int n);
+// C10v.2: what the coarse stage keeps of a voice prompt - the last n_sh semantic ids and the last n_ch - 2 interleaved coarse ids as offset ids; both empty
+// without a voice.  Throws when the trimmed history is empty (n_sh < 2 or n_ch <= 2).
+struct VoiceTrim { std::vector<int32_t> sem, coarse; };
+VoiceTrim voice_trim(const bark_context_params & p, const VoicePrompt * v);
+// prompt of the coarse window that starts at step_idx (bark.cpp:1787-1807): 256 semantic ids from [history ; semantic] (padded), the infer token, the last
+// max_coarse_history ids of [history ; out] (out: the offset ids generated so far)
+std::vector<int32_t> coarse_window_prompt(const bark_context_params & p, const VoiceTrim & vt, const std::vector<int32_t> & semantic, const std::vector<int32_t> & out, int step_idx);
 // window -> tok [8][plane] (this window's 1024 columns), and the picks of channels nc.. at positions >= rel back into in_arr
 void fine_window_tokens(const FinePlan & f, const FineWindow & w, int32_t * tok, size_t plane);
 void fine_write_back(FinePlan & f, const FineWindow & w, const bark_context_params & p, const int32_t * tok, size_t plane);

@@ -196,6 +196,8 @@ static void init_runtime(bark_context * ctxp, bool weights_uploaded_now) {
     ctx->d_lstm_t = dev_alloc<int>(ctx.get(), 2);
     ctx->d_u = dev_alloc<double>(ctx.get(), 8192);
     ctx->d_filter = dev_alloc<int32_t>(ctx.get(), 2);
+    ctx->d_fine_rel = dev_alloc<int32_t>(ctx.get(), 1);
+    HIP_OK(hipMemsetAsync(ctx->d_fine_rel, 0, 4, ctx->stream));
     { const char * e = getenv("BARK_HIP_HOST_SAMPLING"); ctx->host_sampling = e && atoi(e) != 0; }
     {
         std::vector<uint16_t> lut(65536);
@@ -534,6 +536,7 @@ bark_context * engine_clone(bark_context * src, uint32_t seed) {
     std::unique_ptr<bark_context> ctx(new bark_context());
     ctx->params = src->params;
     ctx->filter = src->filter;
+    ctx->voice = src->voice;
     ctx->rng = std::mt19937(seed);
     ctx->vocab = src->vocab;
     for (int g = 0; g < 3; g++) {

@@ -219,10 +219,12 @@ void launch_sample_filtered(hipStream_t s, const SampleArgs & a, const int32_t *
 // fine: per-row greedy pick over the first n_cols of each row -> out[i*out_stride]
 // fine stage, fine_temp > 0: row r picks with the uniform draw u[r]
 // st (optional): near_tie counts the picks settled by the exact path (u within 1e-6 of a bin boundary)
+// rel (optional, device memory, one entry per window of 1024 rows): row z * 1024 + j stores its pick only when j >= rel[z] - a fine window keeps the
+// positions below its rel (C10 / C10v), so the picks go straight into the token plane whatever rel holds; counting and uniforms do not depend on it
 void launch_sample_rows_multinomial(hipStream_t s, const float * logits, int ld, int n_rows, int n_cols, float temp, const double * u,
-                                    int32_t * out, int out_stride, StepState * st = nullptr);
+                                    int32_t * out, int out_stride, StepState * st = nullptr, const int32_t * rel = nullptr);
 void launch_argmax_rows(hipStream_t s, const float * logits, int ld, int n_rows, int n_cols, int32_t * out,
-                        int out_stride, StepState * st);
+                        int out_stride, StepState * st, const int32_t * rel = nullptr);
 
 // BARK_HIP_CROSSCHECK (bit mask, read once per process): the slower routes kept to check the default ones against, bit for bit
 //   1  N > 1 products through the one-row-per-wave kernels instead of the matrix cores (gemv_rows_kernel / gemm_q_rows_kernel)

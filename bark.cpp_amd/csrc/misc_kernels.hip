@@ -508,9 +508,11 @@ __global__ __launch_bounds__(1024) void sample_multinomial_kernel(const SampleAr
     }
 }
 
-// fine stage: one wave per row, multinomial over the first n_cols logits of the row; u[row] is that sample's uniform draw
+// fine stage: one wave per row, multinomial over the first n_cols logits of the row; u[row] is that sample's uniform draw.  rel (optional): rows
+// come in windows of 1024, row z * 1024 + j stores its pick only when j >= rel[z] (the positions below keep what the window was given); the pick is
+// made either way, so the near-tie count and the use of u do not depend on rel
 __global__ __launch_bounds__(256) void sample_rows_multinomial_kernel(const float * logits, int ld, int n_rows, int n_cols, float temp,
-                                                                     const double * u, int32_t * out, int out_stride, StepState * st) {
+                                                                     const double * u, int32_t * out, int out_stride, StepState * st, const int32_t * rel) {
     __shared__ float es[4][1024];                               // the rows' exponentials in index order (exact path)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
@@ -559,12 +561,12 @@ __global__ __launch_bounds__(256) void sample_rows_multinomial_kernel(const floa
             if (st) atomicAdd(&st->near_tie, 1);
         }
     }
-    if (lane == 0) out[(size_t) row * out_stride] = pick;
+    if (lane == 0 && (!rel || (row & 1023) >= rel[row >> 10])) out[(size_t) row * out_stride] = pick;
 }
 void launch_sample_rows_multinomial(hipStream_t s, const float * logits, int ld, int n_rows, int n_cols, float temp, const double * u,
-                                    int32_t * out, int out_stride, StepState * st) {
+                                    int32_t * out, int out_stride, StepState * st, const int32_t * rel) {
     if (n_cols > 1024) kernel_fail("bark-hip: the per-row multinomial pick takes at most 1024 columns");
-    hipLaunchKernelGGL(sample_rows_multinomial_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, logits, ld, n_rows, n_cols, temp, u, out, out_stride, st);
+    hipLaunchKernelGGL(sample_rows_multinomial_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, logits, ld, n_rows, n_cols, temp, u, out, out_stride, st, rel);
 }
 
 void launch_sample_greedy(hipStream_t s, const SampleArgs & a) {
@@ -785,9 +787,10 @@ void launch_sample_filtered(hipStream_t s, const SampleArgs & a, const int32_t *
 
 // fine stage, greedy: per-row pick of gpt_argmax_sample (bark.cpp:223-247) over the first n_cols logits.  Fast path as in sample_greedy_kernel: the
 // first index whose e_i is 1.0f wins unless another logit lies within kNearTie of the maximum; then (about one row in 10^6) the wave repeats the
-// reference's arithmetic literally - e_i in double precision, sequential float sum, p_i = e_i / sum, first strict maximum.
+// reference's arithmetic literally - e_i in double precision, sequential float sum, p_i = e_i / sum, first strict maximum.  rel: as in
+// sample_rows_multinomial_kernel (row z * 1024 + j stores its pick only when j >= rel[z]).
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float * logits, int ld, int n_rows, int n_cols, int32_t * out,
-                                                         int out_stride, StepState * st, int force_exact) {
+                                                         int out_stride, StepState * st, int force_exact, const int32_t * rel) {
     __shared__ float es[4][1024];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
@@ -815,15 +818,15 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float * logits, 
             if (st) atomicAdd(&st->near_tie, 1);
         }
     }
-    if (lane == 0) out[(size_t) row * out_stride] = best;
+    if (lane == 0 && (!rel || (row & 1023) >= rel[row >> 10])) out[(size_t) row * out_stride] = best;
 }
 int exact_sampling() {
     static const int force_exact = getenv("BARK_HIP_EXACT_SAMPLING") ? atoi(getenv("BARK_HIP_EXACT_SAMPLING")) : 0;      // tests: every row through the exact path
     return force_exact;
 }
 void launch_argmax_rows(hipStream_t s, const float * logits, int ld, int n_rows, int n_cols, int32_t * out, int out_stride,
-                        StepState * st) {
-    hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, logits, ld, n_rows, n_cols, out, out_stride, st, exact_sampling());
+                        StepState * st, const int32_t * rel) {
+    hipLaunchKernelGGL(argmax_rows_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, logits, ld, n_rows, n_cols, out, out_stride, st, exact_sampling(), rel);
 }
 
 }  // namespace barkhip

@@ -7,9 +7,11 @@
 // a counter starting at the server's --seed); its audio is what a fresh context loaded with that seed generates, whatever batch it joined.
 // "top_k": k (integer >= 0, 0 off) and "top_p": p (0 < p <= 1, 1 off) filter the request's semantic and coarse samples (bark_hip_sampling_filter);
 // a field left out takes the server's --top-k / --top-p, an invalid one is answered 400.
+// "voice": "name" gives the request the voice prompt (speaker history, bark_hip_voice_prompt) loaded with --voice name=file (repeatable; the file format
+// of bark.cpp_amd/voice.py); an unknown name is answered 400, a request without the field has no voice.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -24,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,6 +34,7 @@
 namespace {
 
 using barkhttp::json_string; using barkhttp::json_uint; using barkhttp::json_int; using barkhttp::json_float; using barkhttp::wav_f32;
+using barkhttp::VoiceFile;
 
 struct Options {
     std::string model, host = "127.0.0.1";
@@ -39,6 +43,7 @@ struct Options {
     uint32_t seed = 0;
     float temp = -1.0f, fine_temp = -1.0f;
     int32_t top_k = 0; float top_p = 1.0f;         // --top-k / --top-p: the filter of requests that carry no "top_k" / "top_p" of their own
+    std::vector<std::string> voices;               // --voice name=file
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -59,6 +64,7 @@ void respond(int fd, int status, const char * reason, const char * type, const s
 std::atomic<uint32_t> next_seed{0};
 bark_hip_request_params request_defaults{};            // the context's sampling parameters (a request with its own filter carries them explicitly)
 bark_hip_sampling_filter filter_defaults{0, 1.0f};
+std::map<std::string, VoiceFile> voice_table;          // --voice name=file, read-only once the server listens
 std::atomic<int> open_connections{0};
 constexpr int kMaxConnections = 512;                     // beyond that a connection is answered 503 at once
 
@@ -109,9 +115,21 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 ::close(fd);
                 return;
             }
+            const VoiceFile * vf = nullptr;
+            if (barkhttp::request_voice(body, voice_table, &vf) < 0) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"voice\" must name a voice loaded with --voice name=file");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
             uint32_t seed = 0;
             if (!json_uint(body, "seed", seed)) seed = next_seed.fetch_add(1);
-            if (hk || hp) {
+            if (vf) {
+                bark_hip_request_params rp = request_defaults; rp.seed = seed;
+                const bark_hip_voice_prompt vp{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
+                                               vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
+                ticket = bark_hip_batcher_submit_voiced(batcher, text.c_str(), &rp, &flt, &vp);
+            } else if (hk || hp) {
                 bark_hip_request_params rp = request_defaults; rp.seed = seed;
                 ticket = bark_hip_batcher_submit_filtered(batcher, text.c_str(), &rp, &flt);
             } else {
@@ -133,7 +151,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")]\n", argv0);
 }
 
 }  // namespace
@@ -155,9 +173,14 @@ int main(int argc, char ** argv) {
         else if (a == "--fine-temp") o.fine_temp = (float) atof(next("--fine-temp"));
         else if (a == "--top-k") o.top_k = (int32_t) atoi(next("--top-k"));
         else if (a == "--top-p") o.top_p = (float) atof(next("--top-p"));
+        else if (a == "--voice") o.voices.push_back(next("--voice"));
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
+    for (const std::string & v : o.voices) {
+        std::string err;
+        if (!barkhttp::add_voice(voice_table, v, err)) { fprintf(stderr, "%s: %s\n", argv[0], err.c_str()); return 1; }
+    }
     signal(SIGPIPE, SIG_IGN);
     bark_context_params params = bark_context_default_params();
     if (o.temp >= 0.0f) params.temp = o.temp;
@@ -172,6 +195,14 @@ int main(int argc, char ** argv) {
     filter_defaults = bark_hip_sampling_filter{o.top_k, o.top_p};
     request_defaults.temp = params.temp; request_defaults.fine_temp = params.fine_temp; request_defaults.min_eos_p = params.min_eos_p;
     request_defaults.n_steps_text_encoder = params.n_steps_text_encoder;
+    // a voice the engine would refuse (ids out of range, empty trimmed history, too long for the coarse context) is refused here, not at the first
+    // request that names it; the contexts themselves keep no voice: a request without the field has none
+    for (const auto & kv : voice_table) {
+        const VoiceFile & vf = kv.second;
+        const bark_hip_voice_prompt vp{vf.semantic.data(), (int32_t) vf.semantic.size(), vf.coarse.data(), (int32_t) (vf.coarse.size() / 2), vf.fine.data(), (int32_t) (vf.fine.size() / 8)};
+        if (bark_hip_set_voice_prompt(ctxs[0], &vp) != 0) { fprintf(stderr, "%s: voice '%s' was refused\n", argv[0], kv.first.c_str()); for (bark_context * x : ctxs) bark_free(x); return 1; }
+    }
+    (void) bark_hip_set_voice_prompt(ctxs[0], nullptr);
     bark_context * ctx = ctxs[0];
     bark_hip_batcher * batcher = ctxs.size() > 1 ? bark_hip_batcher_create_multi(ctxs.data(), (int) ctxs.size(), o.max_batch, o.max_wait_ms)
                                                  : bark_hip_batcher_create_ex(ctx, o.max_batch, o.max_wait_ms, o.streams);

@@ -2,8 +2,12 @@
 // can drive them without a device (tests/test_host_frontend.py).
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <map>
 #include <string>
+#include <vector>
 
 namespace barkhttp {
 
@@ -95,6 +99,49 @@ inline int json_float(const std::string & js, const char * key, float & out) {
     if (r <= 0) return r;
     if (!(v >= -3.4e38 && v <= 3.4e38)) return -1;
     out = (float) v;
+    return 1;
+}
+
+// A voice prompt file (bark.cpp_amd/voice.py writes it), little-endian: "BVP1", int32 n_sem, Tc, Tf, then the int32 arrays semantic [n_sem],
+// coarse [Tc][2], fine [Tf][8].
+struct VoiceFile { std::vector<int32_t> semantic, coarse, fine; };
+inline bool read_voice_file(const std::string & path, VoiceFile & out, std::string & err) {
+    FILE * f = fopen(path.c_str(), "rb");
+    if (!f) { err = "cannot open " + path; return false; }
+    std::vector<char> data;
+    char buf[65536];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof(buf), f)) > 0) data.insert(data.end(), buf, buf + k);
+    fclose(f);
+    int32_t n[3] = {0, 0, 0};
+    if (data.size() < 16 || memcmp(data.data(), "BVP1", 4) != 0) { err = path + ": not a voice prompt file"; return false; }
+    memcpy(n, data.data() + 4, 12);
+    if (n[0] < 0 || n[1] < 0 || n[2] < 0 || n[0] > (1 << 20) || n[1] > (1 << 20) || n[2] > (1 << 20) ||
+        data.size() != 16 + 4 * ((size_t) n[0] + 2 * (size_t) n[1] + 8 * (size_t) n[2])) { err = path + ": counts do not match the file size"; return false; }
+    const int32_t * a = reinterpret_cast<const int32_t *>(data.data() + 16);
+    out.semantic.assign(a, a + n[0]);
+    out.coarse.assign(a + n[0], a + n[0] + 2 * (size_t) n[1]);
+    out.fine.assign(a + n[0] + 2 * (size_t) n[1], a + n[0] + 2 * (size_t) n[1] + 8 * (size_t) n[2]);
+    return true;
+}
+// --voice name=file: adds the file to the table; false (err set) on a malformed argument or file
+inline bool add_voice(std::map<std::string, VoiceFile> & table, const std::string & arg, std::string & err) {
+    const size_t eq = arg.find('=');
+    if (eq == std::string::npos || eq == 0 || eq + 1 >= arg.size()) { err = "--voice expects name=file"; return false; }
+    VoiceFile v;
+    if (!read_voice_file(arg.substr(eq + 1), v, err)) return false;
+    table[arg.substr(0, eq)] = std::move(v);
+    return true;
+}
+// the request field "voice": 0 absent (*out = nullptr), 1 *out is the named voice, -1 not a string or an unknown name (a server answers 400)
+inline int request_voice(const std::string & js, const std::map<std::string, VoiceFile> & table, const VoiceFile ** out) {
+    *out = nullptr;
+    if (js.find("\"voice\"") == std::string::npos) return 0;
+    std::string name;
+    if (!json_string(js, "voice", name)) return -1;
+    const auto it = table.find(name);
+    if (it == table.end()) return -1;
+    *out = &it->second;
     return 1;
 }
 

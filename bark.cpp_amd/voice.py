@@ -1,0 +1,69 @@
+"""Voice prompts (speaker history, rule C10v of DESIGN.md section 3) for the MI355X Bark engine.
+
+A voice prompt is three id arrays, time-major like every [T][2] / [T][8] array of the C API:
+    semantic [n_sem]  ids in [0, 10000)      coarse [Tc][2]  ids in [0, 1024)      fine [Tf][8]  ids in [0, 1024)
+
+File format (`save` / `load`; also read by bark_batch_server --voice name=file), little-endian:
+    bytes 0..3   magic "BVP1"
+    3 x int32    n_sem, Tc, Tf
+    int32 arrays semantic [n_sem], coarse [Tc][2], fine [Tf][8], back to back
+"""
+from __future__ import annotations
+
+import struct
+
+import numpy as np
+
+MAGIC = b"BVP1"
+
+
+class VoicePrompt:
+    def __init__(self, semantic, coarse, fine):
+        self.semantic = np.ascontiguousarray(semantic, dtype=np.int32).reshape(-1)
+        self.coarse = np.ascontiguousarray(coarse, dtype=np.int32).reshape(-1, 2)
+        self.fine = np.ascontiguousarray(fine, dtype=np.int32).reshape(-1, 8)
+
+    def __eq__(self, other):
+        return (isinstance(other, VoicePrompt) and np.array_equal(self.semantic, other.semantic) and np.array_equal(self.coarse, other.coarse)
+                and np.array_equal(self.fine, other.fine))
+
+    def __repr__(self):
+        return f"VoicePrompt(n_sem={len(self.semantic)}, Tc={len(self.coarse)}, Tf={len(self.fine)})"
+
+    def save(self, path: str):
+        save(self, path)
+
+
+def from_npz(path: str) -> VoicePrompt:
+    """A Suno speaker preset: `semantic_prompt` [n], `coarse_prompt` [2][T], `fine_prompt` [8][T] - codebook-major, transposed here."""
+    with np.load(path) as z:
+        return VoicePrompt(z["semantic_prompt"], np.asarray(z["coarse_prompt"]).T, np.asarray(z["fine_prompt"]).T)
+
+
+def save(voice: VoicePrompt, path: str):
+    with open(path, "wb") as f:
+        f.write(MAGIC)
+        f.write(struct.pack("<3i", len(voice.semantic), len(voice.coarse), len(voice.fine)))
+        for a in (voice.semantic, voice.coarse, voice.fine):
+            f.write(np.ascontiguousarray(a, dtype="<i4").tobytes())
+
+
+def load(path: str) -> VoicePrompt:
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 16 or data[:4] != MAGIC:
+        raise ValueError(f"{path}: not a voice prompt file (magic {MAGIC!r} expected)")
+    n_sem, tc, tf = struct.unpack_from("<3i", data, 4)
+    if min(n_sem, tc, tf) < 0 or len(data) != 16 + 4 * (n_sem + 2 * tc + 8 * tf):
+        raise ValueError(f"{path}: counts {n_sem}, {tc}, {tf} do not match the file size {len(data)}")
+    a = np.frombuffer(data, dtype="<i4", offset=16)
+    return VoicePrompt(a[:n_sem], a[n_sem:n_sem + 2 * tc].reshape(tc, 2), a[n_sem + 2 * tc:].reshape(tf, 8))
+
+
+def from_generation(ctx) -> VoicePrompt:
+    """The token streams of the context's last bark_generate_audio call as the next utterance's voice prompt (long-form continuation: feed
+    every utterance the one before it)."""
+    v = VoicePrompt(ctx.semantic_tokens(), ctx.coarse_tokens(), ctx.fine_tokens())
+    if not len(v.semantic) or not len(v.coarse):
+        raise ValueError("from_generation: the context holds no generation")
+    return v

@@ -132,6 +132,37 @@ BARK_API int bark_hip_set_sampling_filter(struct bark_context * bctx, int32_t to
  * parameters).  Every utterance is bit-identical to a fresh context with its parameters, seed and filter. */
 BARK_API int bark_hip_generate_batch_filtered(struct bark_context * bctx, const char * const * texts, int n, const struct bark_hip_request_params * per_utterance,
                                               const struct bark_hip_sampling_filter * filters);
+/* Voice prompts (speaker history; rule C10v; suno-ai/bark generation.py `history_prompt`): the token streams of an earlier
+ * utterance of the speaker, which the three stage loops continue from.  All arrays are time-major, as every [T][2] / [T][8] array of this API
+ * (Suno's .npz presets are codebook-major: bark.cpp_amd/voice.py transposes).  semantic ids in [0, semantic_vocab_size), coarse and fine ids in
+ * [0, codebook_size).  With r = coarse_rate_hz / semantic_rate_hz * n_coarse_codebooks:
+ *   semantic  ids 256..511 of the 513-id prompt are the LAST min(n_semantic, 256) history ids, right-padded with semantic_pad_token;
+ *   coarse    n_sh = min(floor(max_coarse_history / r), n_semantic - n_semantic % 2, floor(2 n_coarse_frames / r)), n_ch = round(n_sh r): the last
+ *             n_sh semantic ids go in front of the semantic input (semantic_idx = n_sh + round(step_idx / r)), the last n_ch interleaved coarse ids
+ *             minus their last TWO in front of the generated ones; step count, window count, codebook parity and the result: the NEW ids only;
+ *   fine      the LAST min(n_fine_frames, 512) history rows (all 8 codebooks) go in front of the coarse rows; windows of 1024 rows with a hop of
+ *             512 fill from the first new row on; the result is the new rows;
+ *   codec     sees the new frames only.
+ * bark_hip_set_voice_prompt copies the arrays; NULL clears.  Returns 0, or -1 for ids out of range, a history whose trimmed form is empty (n_sh < 2 or
+ * n_ch <= 2) or a history that does not fit the coarse context with the context's window parameters (257 + min(max_coarse_history, n_ch - 2) +
+ * sliding_window_size - 1 rows).  It steers bark_generate_audio, bark_hip_tokenize (ids 256..511), bark_hip_coarse, bark_hip_fine, bark_hip_fine_many
+ * and the jobs / collector requests that carry no voice of their own; bark_hip_semantic keeps taking the prompt it is given.  bark_hip_clone_context
+ * copies it.  No voice prompt: the same kernels, graphs and bits as before. */
+struct bark_hip_voice_prompt {
+    const int32_t * semantic;   int32_t n_semantic;        /* [n_semantic]            */
+    const int32_t * coarse_Tx2; int32_t n_coarse_frames;   /* [n_coarse_frames][2]    */
+    const int32_t * fine_Tx8;   int32_t n_fine_frames;     /* [n_fine_frames][8]      */
+};
+BARK_API int bark_hip_set_voice_prompt(struct bark_context * bctx, const struct bark_hip_voice_prompt * voice);
+/* bark_hip_generate_batch_filtered with a voice per utterance (voices == NULL or voices[i] == NULL: the context's).  Every utterance is bit-identical
+ * to a fresh context with its parameters, seed, filter and voice under an equal fine order, whatever company it travels in. */
+BARK_API int bark_hip_generate_batch_voiced(struct bark_context * bctx, const char * const * texts, int n, const struct bark_hip_request_params * per_utterance,
+                                            const struct bark_hip_sampling_filter * filters, const struct bark_hip_voice_prompt * const * voices);
+/* Kernel-level hook of the fine stage's pick kernels (tests): n_windows * 1024 rows of n_cols (<= 1024) logits; temp == 0: the greedy pick, else the
+ * multinomial pick with the uniform draw u[row].  tokens_io [n_windows * 1024] is the token plane: row z * 1024 + j receives its pick when
+ * j >= rel[z] and keeps its value otherwise.  *near_ties (optional): picks settled by the exact path.  Returns 0 or -1. */
+BARK_API int bark_hip_pick_rows(struct bark_context * bctx, const float * logits, int n_windows, int n_cols, float temp, const double * u,
+                                const int32_t * rel, int32_t * tokens_io, int32_t * near_ties);
 /* Fixes the number of lock-step slots (1..64; at least 8 are allocated) before the first job; returns 0 or -1. */
 BARK_API int bark_hip_reserve_batch(struct bark_context * bctx, int slots);
 /* audio of utterance i of the last batch: returns the sample count (-1 on error), *data points into the context */
@@ -170,6 +201,10 @@ BARK_API int64_t bark_hip_batcher_submit_ex(struct bark_hip_batcher * b, const c
  * params == nullptr: the context's parameters with seed 0, as bark_hip_batcher_submit_ex. */
 BARK_API int64_t bark_hip_batcher_submit_filtered(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
                                                   const struct bark_hip_sampling_filter * filter);
+/* ... and its own voice prompt (the arrays are copied into the request); -1 for a voice bark_hip_set_voice_prompt would refuse.  voice == nullptr: the
+ * context's voice as it was when the collector was created. */
+BARK_API int64_t bark_hip_batcher_submit_voiced(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                                const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice);
 BARK_API int bark_hip_batcher_wait(struct bark_hip_batcher * b, int64_t ticket, float * pcm, int capacity);
 BARK_API void bark_hip_batcher_stats(struct bark_hip_batcher * b, int * n_batches, int * n_requests, int * largest_batch);
 /* requests that joined a job that was already running (continuous admission: while the semantic stage of a job has free slots, requests

@@ -346,11 +346,103 @@ def main_stages(preset: str, n_sem: int):
     print("wrote", dst, os.path.getsize(dst), "bytes:", n_sem, "semantic ids ->", coarse.shape, "coarse,", fine.shape, "fine")
 
 
+def main_voice(preset: str, n_sem: int):
+    """tests/golden/hf_<preset>_voice_s0.npz: HF's own `generate` with `history_prompt` (speaker history; rule C10v of DESIGN.md section 3) on the
+    synthetic `preset` weights - BarkSemanticModel.generate (history in ids 256..511 of the prompt), BarkCoarseModel.generate (preprocess_histories:
+    the trimmed semantic and coarse histories in front) and BarkFineModel.generate (up to 512 history rows in front, fill from n_history on) - greedy,
+    with the adjustments of the `stages` fixture (tanh GELU, ids above the second codebook masked, no suppression, no min_eos_p).  Three synthetic
+    histories (random ids: the rule does not care what they sound like, and no preset can be downloaded):
+      short   n_sem 35 (odd), Tc = Tf = 41: floor(2 Tc / r) = 27 is the smallest term and odd, n_ch = 81 - the kept coarse history starts on the SECOND codebook
+      full    n_sem 300, Tc = Tf = 700: every cap active (n_sh 209, n_ch 628, 256 prompt ids, 512 fine rows)
+      tf100   n_sem 120, Tc 200, Tf 100: fewer than 512 fine rows
+    Each history: semantic-from-text (48 steps), coarse from n_sem random semantic ids (700 -> 1052 frames: at least two fine windows for every
+    history), fine from that coarse.  Seed 99 (the `stages` fixture's): no near tie was met with it - tests/test_voice_prompt_ref.py holds the
+    oracle's evaluations under the HF numerics to these ids, id for id."""
+    import torch
+    import transformers.models.bark.modeling_bark as mb
+    from transformers.models.bark.configuration_bark import BarkCoarseConfig
+    from transformers.models.bark.generation_configuration_bark import (BarkCoarseGenerationConfig, BarkFineGenerationConfig,
+                                                                         BarkSemanticGenerationConfig)
+    orig_call = mb.AlternatingCodebooksLogitsProcessor.__call__
+
+    def call(self, input_ids, scores):
+        out = orig_call(self, input_ids, scores)
+        out[:, self.semantic_vocab_size + 2 * self.codebook_size:] = -float("inf")
+        return out
+    mb.AlternatingCodebooksLogitsProcessor.__call__ = call
+
+    class _NoSuppress:
+        def __init__(self, *a, **k): pass
+        def __call__(self, input_ids, scores): return scores
+    mb.SuppressTokensLogitsProcessor = _NoSuppress
+    torch.set_num_threads(8)
+    mf = read_model_file(ensure_model(preset, 0))
+    rng = np.random.default_rng(99)
+    semantic = rng.integers(0, 10000, n_sem).astype(np.int64)
+    n_text = 37
+    text_ids = rng.integers(0, 100000, n_text).astype(np.int64)
+    histories = {}
+    for name, (hs, tc, tf) in (("short", (35, 41, 41)), ("full", (300, 700, 700)), ("tf100", (120, 200, 100))):
+        histories[name] = (rng.integers(0, 10000, hs).astype(np.int64), rng.integers(0, 1024, (tc, 2)).astype(np.int64), rng.integers(0, 1024, (tf, 8)).astype(np.int64))
+    out = dict(semantic=semantic.astype(np.int32), text_ids=text_ids.astype(np.int32), n_semantic_steps=np.int32(48), names=np.array(sorted(histories)))
+    with torch.no_grad():
+        hps, tenss = mf["semantic"]
+        sbase = build_hf_gpt(hps, tenss, fine=False)
+        scfg = mb.BarkSemanticConfig(block_size=hps["block_size"], input_vocab_size=hps["n_in"], output_vocab_size=hps["n_out"], num_layers=hps["n_layer"],
+                                     num_heads=hps["n_head"], hidden_size=hps["n_embd"], dropout=0.0, bias=False)
+        scfg._attn_implementation = "eager"
+        sm = mb.BarkSemanticModel(scfg)
+        sm.load_state_dict(sbase.state_dict())
+        sm = use_tanh_gelu(sm).eval()
+        hp, tens = mf["coarse"]
+        base = build_hf_gpt(hp, tens, fine=False)
+        cfg = BarkCoarseConfig(block_size=hp["block_size"], input_vocab_size=hp["n_in"], output_vocab_size=hp["n_out"], num_layers=hp["n_layer"],
+                               num_heads=hp["n_head"], hidden_size=hp["n_embd"], dropout=0.0, bias=False)
+        cfg._attn_implementation = "eager"
+        co = mb.BarkCoarseModel(cfg)
+        co.load_state_dict(base.state_dict())
+        co = use_tanh_gelu(co).eval()
+        hpf, tensf = mf["fine"]
+        fi = use_tanh_gelu(build_hf_gpt(hpf, tensf, fine=True))
+        ids256 = np.zeros(256, np.int64); ids256[:n_text] = text_ids
+        mask = np.zeros(256, np.int64); mask[:n_text] = 1
+        sgen = BarkSemanticGenerationConfig(do_sample=False, temperature=1.0, min_eos_p=None, max_new_tokens=48)
+        sg = BarkSemanticGenerationConfig()
+        cg = BarkCoarseGenerationConfig(do_sample=False, temperature=1.0)
+        assert (sg.semantic_vocab_size, sg.semantic_rate_hz, cg.max_coarse_input_length, cg.max_coarse_history, cg.sliding_window_len,
+                cg.coarse_semantic_pad_token, cg.coarse_infer_token, cg.coarse_rate_hz) == (10000, 49.9, 256, 630, 60, 12048, 12050, 75)
+        for name, (h_sem, h_co, h_fi) in histories.items():
+            # HF's (and Suno's) layout: codebook-major
+            hist = dict(semantic_prompt=torch.from_numpy(h_sem), coarse_prompt=torch.from_numpy(h_co.T.copy()), fine_prompt=torch.from_numpy(h_fi.T.copy()))
+            sout = sm.generate(torch.from_numpy(ids256)[None], semantic_generation_config=sgen, history_prompt=hist, attention_mask=torch.from_numpy(mask)[None])
+            sem_ids = sout[0].numpy()
+            if (sem_ids == 10000).any():
+                sem_ids = sem_ids[: int(np.argmax(sem_ids == 10000))]
+            cout = co.generate(torch.from_numpy(semantic)[None].clone(), semantic_generation_config=sg, coarse_generation_config=cg, codebook_size=1024,
+                               history_prompt=hist)
+            flat = cout[0].numpy()
+            coarse = np.stack([flat[0::2] - 10000, flat[1::2] - 10000 - 1024], axis=1)
+            assert coarse.min() >= 0 and coarse.max() < 1024
+            fout = fi.generate(cout.clone(), semantic_generation_config=sg, coarse_generation_config=cg,
+                               fine_generation_config=BarkFineGenerationConfig(temperature=None), codebook_size=1024, history_prompt=hist)
+            fine = fout[0].numpy().T
+            assert fine.shape == (coarse.shape[0], 8) and np.array_equal(fine[:, :2], coarse)
+            out.update({f"{name}_h_semantic": h_sem.astype(np.int32), f"{name}_h_coarse": h_co.astype(np.int32), f"{name}_h_fine": h_fi.astype(np.int32),
+                        f"{name}_semantic_from_text": sem_ids.astype(np.int32), f"{name}_coarse": coarse.astype(np.int32), f"{name}_fine": fine.astype(np.int32)})
+            print(name, "semantic-from-text", len(sem_ids), "coarse", coarse.shape, "fine", fine.shape)
+    dst = os.path.join(ROOT, "tests", "golden", f"hf_{preset}_voice_s0.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
 def main():
     import torch
 
     if len(sys.argv) > 1 and sys.argv[1] == "stages":
         main_stages(sys.argv[2] if len(sys.argv) > 2 else "small", int(sys.argv[3]) if len(sys.argv) > 3 else 256)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "voice":
+        main_voice(sys.argv[2] if len(sys.argv) > 2 else "toy", int(sys.argv[3]) if len(sys.argv) > 3 else 700)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "codec":
         main_codec(sys.argv[2] if len(sys.argv) > 2 else "small")
