@@ -97,6 +97,7 @@ EXPORTS = [
     "bark_hip_batcher_create", "bark_hip_batcher_create_ex", "bark_hip_batcher_submit", "bark_hip_batcher_submit_ex", "bark_hip_batcher_wait", "bark_hip_batcher_stats", "bark_hip_batcher_admitted", "bark_hip_batcher_free",
     "bark_hip_set_sampling_filter", "bark_hip_generate_batch_filtered", "bark_hip_batcher_submit_filtered", "bark_hip_sample_rows_filtered", "bark_hip_time_sample_filter",
     "bark_hip_set_voice_prompt", "bark_hip_generate_batch_voiced", "bark_hip_batcher_submit_voiced", "bark_hip_pick_rows",
+    "bark_hip_has_codec_encoder", "bark_hip_codec_encode", "bark_hip_codec_encode_many", "bark_hip_codec_encode_tap", "bark_hip_rvq_encode", "bark_hip_codec_encode_latents", "bark_hip_codec_encode_device_us",
 ]
 
 
@@ -140,6 +141,14 @@ def load_library() -> C.CDLL:
     lib.bark_hip_fine_many.argtypes = [vp, ip, ip, C.c_int, ip, C.c_int]
     lib.bark_hip_codec_decode.argtypes = [vp, ip, C.c_int, C.c_int, fp, C.c_int]
     lib.bark_hip_codec_tap.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, fp, C.c_int]
+    lib.bark_hip_has_codec_encoder.argtypes = [vp]
+    lib.bark_hip_codec_encode.argtypes = [vp, fp, C.c_int, C.c_int, ip, C.c_int]
+    lib.bark_hip_codec_encode_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.c_int, ip, C.c_int]
+    lib.bark_hip_codec_encode_tap.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.c_int]
+    lib.bark_hip_rvq_encode.argtypes = [vp, fp, C.c_int, C.c_int, ip]
+    lib.bark_hip_codec_encode_latents.argtypes = [vp, fp, C.c_int]
+    lib.bark_hip_codec_encode_device_us.restype = C.c_double
+    lib.bark_hip_codec_encode_device_us.argtypes = [vp]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
     lib.bark_hip_generate_batch_seeded.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_uint32)]
     lib.bark_hip_generate_batch_ex.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams)]
@@ -375,6 +384,66 @@ class BarkContext:
         if n < 0:
             raise RuntimeError("bark_hip_codec_tap failed")
         return out[:n].copy()
+
+    def has_codec_encoder(self) -> bool:
+        return bool(self._lib.bark_hip_has_codec_encoder(self._h))
+
+    def codec_encode(self, pcm, n_q: int = 8) -> np.ndarray:
+        """EnCodec encode (bark_hip_codec_encode): 24 kHz mono float samples -> codes [n_q][T], T = ceil(n / 320)."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        T = (len(x) + 319) // 320
+        codes = np.zeros((max(n_q, 1), max(T, 1)), np.int32)
+        n = self._lib.bark_hip_codec_encode(self._h, x.ctypes.data, len(x), n_q, codes.ctypes.data, codes.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_codec_encode failed")
+        return codes[:, :n].copy()
+
+    def codec_encode_many(self, pcm_list, n_q: int = 8) -> list:
+        """n <= 32 recordings in one pass (bark_hip_codec_encode_many): one [n_q][T_i] array per recording."""
+        xs = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in pcm_list]
+        ns = _i32([len(x) for x in xs])
+        Ts = [(len(x) + 319) // 320 for x in xs]
+        ptrs = (C.c_void_p * len(xs))(*[x.ctypes.data for x in xs])
+        out = np.zeros(max(n_q, 1) * max(sum(Ts), 1), np.int32)
+        n = self._lib.bark_hip_codec_encode_many(self._h, ptrs, ns.ctypes.data, len(xs), n_q, out.ctypes.data, out.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_codec_encode_many failed")
+        res, off = [], 0
+        for t in Ts:
+            res.append(out[off:off + n_q * t].reshape(n_q, t).copy()); off += n_q * t
+        return res
+
+    def codec_encode_tap(self, pcm, stage: int) -> np.ndarray:
+        """Parity tap of the encoder (bark_hip_codec_encode_tap), channel-major [C][T']: stage 0 first conv, 1..4 down-sampling convs, 5 LSTM + skip, 6 latent."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        out = np.zeros(max(len(x), 1) * 64 + 4096, np.float32)
+        n = self._lib.bark_hip_codec_encode_tap(self._h, x.ctypes.data, len(x), stage, out.ctypes.data, out.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_codec_encode_tap failed")
+        rows = len(x)
+        for s in (2, 4, 5, 8)[:min(max(stage, 0), 4)]:
+            rows = (rows + s - 1) // s
+        return out[:n].copy().reshape(-1, rows)
+
+    def codec_encode_latents(self, n_frames: int, hidden_dim: int = 128) -> np.ndarray:
+        """The latents [sum T_i][hidden_dim] the last codec_encode / codec_encode_many call quantised (bark_hip_codec_encode_latents); n_frames = sum T_i."""
+        out = np.zeros((n_frames, hidden_dim), np.float32)
+        if self._lib.bark_hip_codec_encode_latents(self._h, out.ctypes.data, out.size) != n_frames:
+            raise RuntimeError("bark_hip_codec_encode_latents failed")
+        return out
+
+    def codec_encode_device_us(self) -> float:
+        """hipEvent time between the first and the last kernel of the last codec_encode / codec_encode_many call (bark_hip_codec_encode_device_us)."""
+        return float(self._lib.bark_hip_codec_encode_device_us(self._h))
+
+    def rvq_encode(self, latents_TxH, n_q: int = 8) -> np.ndarray:
+        """Kernel-level hook (bark_hip_rvq_encode): latents [T][hidden_dim] -> codes [n_q][T] by the RVQ kernel alone (rule C11q)."""
+        z = np.ascontiguousarray(latents_TxH, dtype=np.float32)
+        assert z.ndim == 2
+        codes = np.zeros((max(n_q, 1), len(z)), np.int32)
+        if self._lib.bark_hip_rvq_encode(self._h, z.ctypes.data, len(z), n_q, codes.ctypes.data) < 0:
+            raise RuntimeError("bark_hip_rvq_encode failed")
+        return codes
 
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""

@@ -3,6 +3,7 @@
 // a diagnostic on stderr, like the reference (bark.cpp:1174-1177, 2379-2401).
 #include "engine.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -11,6 +12,8 @@
 #include <vector>
 
 using namespace barkhip;
+
+#define HIP_OK_API(expr) do { if ((expr) != hipSuccess) throw std::runtime_error("HIP error at " #expr); } while (0)
 
 namespace {
 int64_t wall_us() {
@@ -250,6 +253,60 @@ int bark_hip_codec_tap(struct bark_context * bctx, const int32_t * codes, int n_
         if ((int) tap.size() > capacity) return -1;
         memcpy(out, tap.data(), tap.size() * 4);
         return (int) tap.size();
+    });
+}
+
+int bark_hip_has_codec_encoder(struct bark_context * bctx) { return (bctx && bctx->codec.enc.present) ? 1 : 0; }
+
+int bark_hip_codec_encode_many(struct bark_context * bctx, const float * const * pcm, const int * n_samples, int n, int n_q, int32_t * codes_concat, int capacity) {
+    if (!bctx || !pcm || !n_samples || !codes_concat || n <= 0 || n > 32) return -1;
+    for (int i = 0; i < n; i++) if (!pcm[i]) return -1;
+    return guarded("bark_hip_codec_encode", -1, [&] {
+        long total = 0;                                             // refused before any work: a result that does not fit
+        for (int i = 0; i < n; i++) total += n_samples[i] > 0 ? (n_samples[i] + 319) / 320 : 0;
+        if (n_q > 0 && total * n_q > (long) capacity) throw std::runtime_error("output buffer too small");
+        std::vector<std::vector<int32_t>> r = engine_codec_encode_many(bctx, std::vector<const float *>(pcm, pcm + n), std::vector<int>(n_samples, n_samples + n), n_q, -1, nullptr);
+        size_t off = 0;
+        for (auto & v : r) { memcpy(codes_concat + off, v.data(), v.size() * 4); off += v.size(); }
+        return (int) (off / (size_t) n_q);
+    });
+}
+
+int bark_hip_codec_encode(struct bark_context * bctx, const float * pcm, int n_samples, int n_q, int32_t * codes, int capacity) {
+    return bark_hip_codec_encode_many(bctx, &pcm, &n_samples, 1, n_q, codes, capacity);
+}
+
+int bark_hip_codec_encode_tap(struct bark_context * bctx, const float * pcm, int n_samples, int stage, float * out, int capacity) {
+    if (!bctx || !pcm || !out || stage < 0) return -1;
+    return guarded("bark_hip_codec_encode_tap", -1, [&] {
+        std::vector<float> tap;
+        engine_codec_encode_many(bctx, {pcm}, {n_samples}, 1, stage, &tap);
+        if ((long) tap.size() > (long) capacity) return -1;
+        memcpy(out, tap.data(), tap.size() * 4);
+        return (int) tap.size();
+    });
+}
+
+int bark_hip_codec_encode_latents(struct bark_context * bctx, float * out_TxH, int capacity) {
+    if (!bctx || !out_TxH || !bctx->enc_latents) return -1;
+    return guarded("bark_hip_codec_encode_latents", -1, [&] {
+        const size_t n = (size_t) bctx->enc_latent_rows * (size_t) bctx->codec.hp.hidden_dim;
+        if (n > (size_t) std::max(capacity, 0)) return -1;
+        HIP_OK_API(hipSetDevice(bctx->device));
+        HIP_OK_API(hipMemcpyAsync(out_TxH, bctx->enc_latents, n * 4, hipMemcpyDeviceToHost, bctx->stream));
+        HIP_OK_API(hipStreamSynchronize(bctx->stream));
+        return bctx->enc_latent_rows;
+    });
+}
+
+double bark_hip_codec_encode_device_us(struct bark_context * bctx) { return bctx ? bctx->enc_device_us : -1.0; }
+
+int bark_hip_rvq_encode(struct bark_context * bctx, const float * latents_TxH, int T, int n_q, int32_t * codes) {
+    if (!bctx || !latents_TxH || !codes) return -1;
+    return guarded("bark_hip_rvq_encode", -1, [&] {
+        std::vector<int32_t> r = engine_rvq_encode(bctx, latents_TxH, T, n_q);
+        memcpy(codes, r.data(), r.size() * 4);
+        return T;
     });
 }
 

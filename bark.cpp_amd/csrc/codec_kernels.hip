@@ -265,4 +265,194 @@ void launch_add(hipStream_t s, const float * a, const float * b, size_t n, float
     hipLaunchKernelGGL(add_kernel, dim3(blocks), dim3(256), 0, s, a, b, n, out);
 }
 
+// ---- EnCodec encoder ------------------------------------------------------------------------------
+// EncodecConv1d with a stride (modeling_encodec.py: EncodecConv1d.forward / _pad1d), the 24 kHz model's causal reflect padding: left pad K - stride,
+// right pad rows_out * stride - rows (rows_out = ceil(rows / stride)), both by reflection; an input not longer than the larger pad is first extended
+// with zeros to that pad + 1 rows, reflected, and the same number of rows is cut off the END of the padded array - every output row reads padded rows
+// below that cut, so only the reflection point moves.  Source row of tap kk of output row t; -1: the operand is zero.
+__device__ __forceinline__ int conv_down_src_row(int K, int stride, int kk, int t, int rows, int rows_out) {
+    const int pl = K - stride, pr = rows_out * stride - rows;
+    const int mp = pl > pr ? pl : pr;
+    const int Lp = rows <= mp ? mp + 1 : rows;                    // length the reflection sees
+    int j = t * stride + kk - pl;
+    if (j < 0) j = -j;
+    else if (j >= Lp) j = 2 * Lp - 2 - j;
+    return (j >= 0 && j < rows) ? j : -1;
+}
+__device__ __forceinline__ int utt_index_of_row(const CodecBatch & cb, int row) {
+    int z = 0;
+    while (z + 1 < cb.B && row >= cb.Tpre[z + 1]) z++;
+    return z;
+}
+
+// C9m, sibling of conv_tm_mfma_kernel: one wave = 32 OUTPUT rows x 32 output channels; the operand rows of a lane are the K input rows of its output row
+__global__ __launch_bounds__(256) void conv_down_mfma_kernel(const ConvDownArgs a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int orow = (blockIdx.x * 4 + w) * 32 + l31;             // global output row of this lane's column
+    const int co0 = blockIdx.y * 32;
+    const bool live = orow < a.rows_out;
+    int t = 0, rows = 0, rows_out = 0, in0 = 0;
+    if (live) {
+        const int z = utt_index_of_row(a.cb_out, orow);
+        t = orow - a.cb_out.Tpre[z]; rows_out = a.cb_out.T[z]; rows = a.cb_in.T[z]; in0 = a.cb_in.Tpre[z];
+    }
+    const int nkb = a.kd16 >> 4;
+    const half_t * wrow = a.W + ((size_t) co0 + l31) * a.kd16 + 8 * half;
+    floatx16c acc;
+    #pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
+    auto load_b = [&](int kb) {
+        const int kdd = 16 * kb + 8 * half;
+        half8 bv;
+        #pragma unroll
+        for (int e = 0; e < 8; e++) bv[e] = (half_t) 0.0f;
+        if (live && kdd < a.kd) {
+            const int kk = kdd / a.cin, ci0 = kdd - kk * a.cin;
+            const int j = conv_down_src_row(a.K, a.stride, kk, t, rows, rows_out);
+            if (j >= 0) bv = *reinterpret_cast<const half8 *>(a.xh + (size_t) (in0 + j) * a.cin + ci0);
+        }
+        return bv;
+    };
+    int kb = 0;
+    for (; kb + 4 <= nkb; kb += 4) {
+        half8 av[4], bv[4];
+        #pragma unroll
+        for (int i = 0; i < 4; i++) { av[i] = *reinterpret_cast<const half8 *>(wrow + 16 * (kb + i)); bv[i] = load_b(kb + i); }
+        #pragma unroll
+        for (int i = 0; i < 4; i++) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[i], acc, 0, 0, 0);
+    }
+    for (; kb < nkb; kb++) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8 *>(wrow + 16 * kb), load_b(kb), acc, 0, 0, 0);
+    if (!live) return;
+    #pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const int co = co0 + 8 * g + 4 * half;
+        #pragma unroll
+        for (int e = 0; e < 4; e++) {
+            if (co + e >= a.cout) break;
+            const float v = acc[4 * g + e] + a.bias[co + e];
+            const size_t o = (size_t) orow * a.cout + co + e;
+            if (a.y) a.y[o] = v;
+            if (a.yh_raw) a.yh_raw[o] = to_half(v);
+            if (a.yh_elu) a.yh_elu[o] = to_half(elu_canon(v));
+        }
+    }
+}
+
+// C9: one fmaf chain per output in (ci, k) order, bias last
+__global__ __launch_bounds__(256) void conv_down_chain_kernel(const ConvDownArgs a) {
+    const size_t idx = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t) a.rows_out * a.cout) return;
+    const int orow = (int) (idx / a.cout), co = (int) (idx % a.cout);
+    const int z = utt_index_of_row(a.cb_out, orow);
+    const int t = orow - a.cb_out.Tpre[z], rows_out = a.cb_out.T[z], rows = a.cb_in.T[z], in0 = a.cb_in.Tpre[z];
+    float acc = 0.0f;
+    for (int ci = 0; ci < a.cin; ci++) {
+        const float * wr = a.w32 + ((size_t) co * a.cin + ci) * a.K;
+        for (int k = 0; k < a.K; k++) {
+            const int j = conv_down_src_row(a.K, a.stride, k, t, rows, rows_out);
+            const float xv = j >= 0 ? (float) a.xh[(size_t) (in0 + j) * a.cin + ci] : 0.0f;
+            acc = fmaf(wr[k], xv, acc);
+        }
+    }
+    const float v = acc + a.bias[co];
+    if (a.y) a.y[idx] = v;
+    if (a.yh_raw) a.yh_raw[idx] = to_half(v);
+    if (a.yh_elu) a.yh_elu[idx] = to_half(elu_canon(v));
+}
+
+void launch_conv_down(hipStream_t s, const ConvDownArgs & a) {
+    if (a.stride < 1 || a.K < a.stride || !a.cb_in.T || !a.cb_out.T) kernel_fail("bark-hip: strided convolution needs kernel >= stride >= 1 and both stages' row tables (got %d, %d)", a.K, a.stride);
+    if (a.W && !(crosscheck_mask() & 1024)) {
+        hipLaunchKernelGGL(conv_down_mfma_kernel, dim3((a.rows_out + 127) / 128, a.cout32 / 32), dim3(256), 0, s, a);
+        return;
+    }
+    const size_t n = (size_t) a.rows_out * a.cout;
+    hipLaunchKernelGGL(conv_down_chain_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, a);
+}
+
+// C11q: kRvqFrames frames per workgroup, their residuals in LDS; work-item i scores the codebook rows i, i + 256, .. against all of them (one read of
+// a row serves every frame), each distance one chain over d ascending: t = r_d - e_jd; p = t * t; acc = acc + p (-ffp-contract=off: nothing fused).
+// The pick is the smallest distance, ties to the lowest row: in the work-item by scanning its rows in ascending order, across work-items by comparing (d, j).
+constexpr int kRvqFrames = 4, kRvqMaxDim = 1024;
+__global__ __launch_bounds__(256) void rvq_encode_kernel(const float * codebooks, int n_bins, int Hd, const float * z, int n_q, int rows_total, int32_t * codes, const CodecBatch cb) {
+    __shared__ float r[kRvqFrames * kRvqMaxDim];
+    __shared__ float wd[4 * kRvqFrames];
+    __shared__ int wj[4 * kRvqFrames];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = blockIdx.x * kRvqFrames;
+    const int nf = min(kRvqFrames, rows_total - f0);
+    for (int i = tid; i < kRvqFrames * Hd; i += 256) {
+        const int f = i / Hd, d = i - f * Hd;
+        r[f * kRvqMaxDim + d] = f < nf ? z[(size_t) (f0 + f) * Hd + d] : 0.0f;
+    }
+    __syncthreads();
+    for (int q = 0; q < n_q; q++) {
+        const float * E = codebooks + (size_t) q * n_bins * Hd;
+        float best[kRvqFrames]; int bj[kRvqFrames];
+        #pragma unroll
+        for (int f = 0; f < kRvqFrames; f++) { best[f] = INFINITY; bj[f] = 0x7fffffff; }
+        for (int j = tid; j < n_bins; j += 256) {
+            const float * e = E + (size_t) j * Hd;
+            float acc[kRvqFrames];
+            #pragma unroll
+            for (int f = 0; f < kRvqFrames; f++) acc[f] = 0.0f;
+            int d = 0;
+            if (!(Hd & 3)) {
+                for (; d < Hd; d += 4) {
+                    const float4 ev = *reinterpret_cast<const float4 *>(e + d);
+                    #pragma unroll
+                    for (int f = 0; f < kRvqFrames; f++) {
+                        const float * rf = r + f * kRvqMaxDim + d;
+                        float t = rf[0] - ev.x; float p = t * t; acc[f] = acc[f] + p;
+                        t = rf[1] - ev.y; p = t * t; acc[f] = acc[f] + p;
+                        t = rf[2] - ev.z; p = t * t; acc[f] = acc[f] + p;
+                        t = rf[3] - ev.w; p = t * t; acc[f] = acc[f] + p;
+                    }
+                }
+            }
+            for (; d < Hd; d++) {
+                const float ev = e[d];
+                #pragma unroll
+                for (int f = 0; f < kRvqFrames; f++) { const float t = r[f * kRvqMaxDim + d] - ev; const float p = t * t; acc[f] = acc[f] + p; }
+            }
+            #pragma unroll
+            for (int f = 0; f < kRvqFrames; f++) if (acc[f] < best[f]) { best[f] = acc[f]; bj[f] = j; }
+        }
+        #pragma unroll
+        for (int f = 0; f < kRvqFrames; f++) {
+            for (int m = 1; m < 64; m <<= 1) {
+                const float od = __shfl_xor(best[f], m, 64); const int oj = __shfl_xor(bj[f], m, 64);
+                if (od < best[f] || (od == best[f] && oj < bj[f])) { best[f] = od; bj[f] = oj; }
+            }
+            if (lane == 0) { wd[wave * kRvqFrames + f] = best[f]; wj[wave * kRvqFrames + f] = bj[f]; }
+        }
+        __syncthreads();
+        int pick[kRvqFrames];
+        #pragma unroll
+        for (int f = 0; f < kRvqFrames; f++) {
+            float bd = wd[f]; int b = wj[f];
+            for (int w = 1; w < 4; w++) {
+                const float od = wd[w * kRvqFrames + f]; const int oj = wj[w * kRvqFrames + f];
+                if (od < bd || (od == bd && oj < b)) { bd = od; b = oj; }
+            }
+            pick[f] = min(b, n_bins - 1);
+        }
+        #pragma unroll
+        for (int f = 0; f < kRvqFrames; f++) {
+            const float * e = E + (size_t) pick[f] * Hd;
+            for (int d = tid; d < Hd; d += 256) r[f * kRvqMaxDim + d] = r[f * kRvqMaxDim + d] - e[d];
+            if (tid == f && f < nf) {
+                int row0, rows;
+                utt_of_row(cb, 0, 1, f0 + f, row0, rows);
+                codes[(size_t) n_q * row0 + (size_t) q * rows + (f0 + f - row0)] = pick[f];
+            }
+        }
+        __syncthreads();
+    }
+}
+void launch_rvq_encode(hipStream_t s, const float * codebooks, int n_bins, int Hd, const float * z, int n_q, int rows_total, int32_t * codes, const CodecBatch & cb) {
+    if (Hd < 1 || Hd > kRvqMaxDim || !cb.T) kernel_fail("bark-hip: the RVQ encoder takes latents of 1..%d dimensions (got %d)", kRvqMaxDim, Hd);
+    hipLaunchKernelGGL(rvq_encode_kernel, dim3((rows_total + kRvqFrames - 1) / kRvqFrames), dim3(256), 0, s, codebooks, n_bins, Hd, z, n_q, rows_total, codes, cb);
+}
+
 }  // namespace barkhip

@@ -60,6 +60,10 @@ struct CodecModel {
     Conv init, fin;
     Lstm lstm[2];
     struct Block { ConvT up; Conv c1, c2, sc; } blocks[4];
+    // SEANet encoder (optional: files written without it report none).  Its tensors live in allocations of their own (SharedWeights::extra), so the
+    // slab, its size and the decoder are what they are without an encoder.  down: the strided convolution behind the residual block (kernel 2 stride)
+    struct EncBlock { Conv c1, c2, sc, down; int stride = 0; };
+    struct Encoder { bool present = false; int F = 0; Conv init, fin; EncBlock blocks[4]; Lstm lstm[2]; } enc;
 };
 
 // A voice prompt (rule C10v): the speaker history the three stage loops start from, copied from a bark_hip_voice_prompt.  Held
@@ -128,6 +132,11 @@ struct bark_context {
     int * d_lstm_t = nullptr;                           // step counter of the replayed LSTM block
     int * d_codec_T = nullptr;                          // frame counts of the utterances being decoded and their prefix sums (CodecBatch)
     struct LstmGraph { hipGraphExec_t exec = nullptr; int B = 0; const float * out = nullptr; const float * gi = nullptr; } lstm_graph;    // 64 wave-front steps
+    LstmGraph lstm_graph_enc;                           // the same block with the encoder's weights and row table: a slot of its own, so encode / decode never replay each other's capture
+    int * d_enc_T = nullptr;                            // encoder: row counts and prefix sums of the recordings at each of its five stages ([5][80], laid out as d_codec_T)
+    float * d_pcm = nullptr; size_t d_pcm_elems = 0;    // encoder: the recordings' samples back to back
+    hipEvent_t enc_ev[2] = {nullptr, nullptr}; double enc_device_us = -1.0;      // events around the kernels of an encode call, and what the last call took between them
+    const float * enc_latents = nullptr; int enc_latent_rows = 0;      // the latents [rows][hidden_dim] of the last encode call, until the next codec call of this context
     struct CodecGraph { hipGraphExec_t exec = nullptr; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -213,6 +222,13 @@ std::vector<float>   engine_codec_decode(bark_context * ctx, const int32_t * cod
 // all utterances of a batch in one pass (codes[b]: [n_q][T[b]]); the launches of one utterance serve all of them
 std::vector<std::vector<float>> engine_codec_decode_many(bark_context * ctx, const std::vector<const int32_t *> & codes, int n_q, const std::vector<int> & T,
                                                          int tap_stage, std::vector<float> * tap);
+// EnCodec encoder: n <= 32 recordings (pcm[b]: n_samples[b] floats, 24 kHz mono) in one pass -> codes[b] [n_q][T[b]], T[b] = ceil(n_samples[b] / 320).
+// tap_stage >= 0 (one recording): *tap receives the activation after that stage, channel-major (0 first conv, 1..4 the down-sampling convs, 5 LSTM + skip,
+// 6 the latent [H][T]).  Throws without an encoder in the file, on an empty / too long (> 4096 frames) / non-finite recording, on n_q outside the file's codebooks.
+std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * ctx, const std::vector<const float *> & pcm, const std::vector<int> & n_samples, int n_q,
+                                                           int tap_stage, std::vector<float> * tap);
+// kernel-level hook: latents [T][H] -> codes [n_q][T] by the RVQ kernel alone (C11q)
+std::vector<int32_t> engine_rvq_encode(bark_context * ctx, const float * latents, int T, int n_q);
 bool engine_generate(bark_context * ctx, const char * text);
 // seeds: one std::mt19937 seed per utterance (temp > 0); nullptr: drawn from the context's generator, in order.  Returns #ok
 // Continuous admission: while the semantic stage of a job has free slots and nobody of the job waits for them, next() may hand over further

@@ -1,14 +1,72 @@
-// engine_codec.hip - EnCodec decode (encodec_decompress_audio call site, /root/reference/bark.cpp:2143-2167) for one utterance or
+// engine_codec.hip - EnCodec decode and encode (decode: encodec_decompress_audio call site, /root/reference/bark.cpp:2143-2167) for one utterance or
 // for all utterances of a lock-step batch at once.  Architecture: HF modeling_encodec.py:316-347 (decoder stack), :236-249 (LSTM +
 // skip), :252-282 (residual blocks), :381-448 (RVQ de-embedding); kernels in codec_kernels.hip, the LSTM input projection in kernels.hip.
 #include "engine_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <stdexcept>
 
 using namespace barkhip;
 using namespace barkhip::detail;
+
+
+namespace {
+// scratch shared by decode and encode: three f32 and three f16 activation buffers of `need` elements, the LSTM's rows for Ts frames, its cells, the row tables
+void ensure_codec_scratch(bark_context * c, size_t need, int Ts, int D) {
+    if (need > c->cbuf_elems) {
+        for (auto & b : c->cbuf) b = dev_alloc<float>(c, need);
+        for (auto & b : c->cbuf_hh) b = dev_alloc<half_t>(c, need);
+        c->cbuf_elems = need;
+    }
+    if ((size_t) Ts > c->c_T) {
+        c->c_gi = dev_alloc<float>(c, (size_t) Ts * 4 * D);
+        c->c_hseq_h = dev_alloc<half_t>(c, (size_t) Ts * D);
+        c->c_xt_h = dev_alloc<half_t>(c, (size_t) Ts * D);
+        c->c_hseq2_h = dev_alloc<half_t>(c, (size_t) Ts * D);
+        c->c_T = (size_t) Ts;
+    }
+    if (!c->c_cell) { c->c_cell = dev_alloc<float>(c, (size_t) 32 * D); c->c_cell2 = dev_alloc<float>(c, (size_t) 32 * D); c->d_codec_T = dev_alloc<int>(c, 80); }
+}
+
+// 2-layer LSTM (modeling_encodec.py:236-249) over the f16 rows c->c_xt_h [Ts][D] -> out2 [Ts][D] f32 (the skip is the caller's), both layers as a wave
+// front: launch i = layer 1 at step i + layer 2 at step i - 1 (its input projection formed in the same kernel): T + 1 strictly sequential launches
+// instead of 2 T, for all utterances at once.  64 of them are captured once as a hipGraph whose nodes take their launch index from a device counter,
+// so one graph serves every T (and is re-captured only when the batch size or a buffer changes).  `slot`: the capture of THESE weights and THIS row
+// table (decoder and encoder each own one).
+void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context::LstmGraph & slot, const CodecBatch & cb, int Ts, int Tmax, float * out2) {
+    hipStream_t s = c->stream;
+    const int D = c->codec.D, B = cb.B;
+    {
+        LinArgs g;
+        g.W = lstm[0].w_ih; g.M = 4 * D; g.K = D; g.N = Ts; g.x_f16 = c->c_xt_h; g.epi = EPI_LOGITS; g.out = c->c_gi; g.ld_out = 4 * D;
+        launch_linear(s, g);
+    }
+    LstmPairArgs a;
+    a.gi1 = c->c_gi; a.w_hh1 = lstm[0].w_hh; a.b_ih1 = lstm[0].b_ih; a.b_hh1 = lstm[0].b_hh; a.c1 = c->c_cell; a.h1 = c->c_hseq_h;
+    a.w_ih2 = lstm[1].w_ih; a.w_hh2 = lstm[1].w_hh; a.b_ih2 = lstm[1].b_ih; a.b_hh2 = lstm[1].b_hh; a.c2 = c->c_cell2; a.h2 = c->c_hseq2_h;
+    a.out2 = out2; a.T = Tmax; a.D = D; a.cb = cb;
+    if (!c->use_graph) {
+        for (int i = 0; i <= Tmax; i++) { a.t = i; launch_lstm_pair_step(s, a); }
+        return;
+    }
+    constexpr int kBlock = 64;
+    if (slot.exec && (slot.out != out2 || slot.gi != c->c_gi || slot.B != B)) { (void) hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
+    if (!slot.exec) {
+        slot.exec = capture_graph(s, [&] {
+            a.t_base = c->d_lstm_t;
+            for (int i = 0; i < kBlock; i++) { a.t = i; launch_lstm_pair_step(s, a); }
+            launch_add_int(s, c->d_lstm_t, kBlock);
+        });
+        slot.out = out2; slot.gi = c->c_gi; slot.B = B;
+    }
+    const int hdr[2] = {0, Tmax};
+    HIP_OK(hipMemcpyAsync(c->d_lstm_t, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                         // hdr is a stack object
+    for (int i0 = 0; i0 <= Tmax; i0 += kBlock) HIP_OK(hipGraphLaunch(slot.exec, s));
+}
+}  // namespace
 
 namespace barkhip {
 
@@ -18,6 +76,7 @@ namespace barkhip {
 std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const std::vector<const int32_t *> & codes, int n_q, const std::vector<int> & T,
                                                          int tap_stage, std::vector<float> * tap) {
     HIP_OK(hipSetDevice(c->device));
+    c->enc_latents = nullptr; c->enc_latent_rows = 0;
     CodecModel & cm = c->codec;
     const int B = (int) T.size();
     if (B < 1 || B > 32 || codes.size() != T.size()) throw std::runtime_error("codec: 1..32 utterances per call");
@@ -37,19 +96,7 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
     // largest activation: rows x channels at every stage (time-major; the hidden channels of a residual block are half its width)
     size_t need = (size_t) std::max(cm.hp.hidden_dim, D) * Ts;
     { int ch = D; size_t tt = (size_t) Ts; for (auto & b : cm.blocks) { ch = b.up.cout; tt *= b.up.stride; need = std::max(need, (size_t) ch * tt); } }
-    if (need > c->cbuf_elems) {
-        for (auto & b : c->cbuf) b = dev_alloc<float>(c, need);
-        for (auto & b : c->cbuf_hh) b = dev_alloc<half_t>(c, need);
-        c->cbuf_elems = need;
-    }
-    if ((size_t) Ts > c->c_T) {
-        c->c_gi = dev_alloc<float>(c, (size_t) Ts * 4 * D);
-        c->c_hseq_h = dev_alloc<half_t>(c, (size_t) Ts * D);
-        c->c_xt_h = dev_alloc<half_t>(c, (size_t) Ts * D);
-        c->c_hseq2_h = dev_alloc<half_t>(c, (size_t) Ts * D);
-        c->c_T = (size_t) Ts;
-    }
-    if (!c->c_cell) { c->c_cell = dev_alloc<float>(c, (size_t) 32 * D); c->c_cell2 = dev_alloc<float>(c, (size_t) 32 * D); c->d_codec_T = dev_alloc<int>(c, 80); }
+    ensure_codec_scratch(c, need, Ts, D);
     if ((size_t) n_q * Ts > c->d_codes_elems) { c->d_codes = dev_alloc<int32_t>(c, (size_t) n_q * Ts); c->d_codes_elems = (size_t) n_q * Ts; }
     for (int b = 0; b < B; b++)
         HIP_OK(hipMemcpyAsync(c->d_codes + (size_t) n_q * Tpre[(size_t) b], codes[(size_t) b], (size_t) n_q * T[(size_t) b] * 4, hipMemcpyHostToDevice, s));
@@ -84,38 +131,7 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
     launch_rvq_gather(s, cm.codebooks, cm.hp.n_bins, cm.hp.hidden_dim, c->d_codes, n_q, Tmax, Ts, A, cb);
     launch_act_round(s, A, (size_t) cm.hp.hidden_dim * Ts, 0, H0);
     conv(cm.init, H0, 1, nullptr, Bf, c->c_xt_h, nullptr);      // Bf = x [row][D]; its f16 image is the LSTM's input
-    // 2-layer LSTM + skip (modeling_encodec.py:236-249), both layers as a wave front: launch i = layer 1 at step i + layer 2 at step
-    // i - 1 (its input projection formed in the same kernel): T + 1 strictly sequential launches instead of 2 T, for all utterances at
-    // once.  64 of them are captured once as a hipGraph whose nodes take their launch index from a device counter, so one graph
-    // serves every T (and is re-captured only when the batch size or a buffer changes).
-    {
-        LinArgs g;
-        g.W = cm.lstm[0].w_ih; g.M = 4 * D; g.K = D; g.N = Ts; g.x_f16 = c->c_xt_h; g.epi = EPI_LOGITS; g.out = c->c_gi; g.ld_out = 4 * D;
-        launch_linear(s, g);
-    }
-    LstmPairArgs a;
-    a.gi1 = c->c_gi; a.w_hh1 = cm.lstm[0].w_hh; a.b_ih1 = cm.lstm[0].b_ih; a.b_hh1 = cm.lstm[0].b_hh; a.c1 = c->c_cell; a.h1 = c->c_hseq_h;
-    a.w_ih2 = cm.lstm[1].w_ih; a.w_hh2 = cm.lstm[1].w_hh; a.b_ih2 = cm.lstm[1].b_ih; a.b_hh2 = cm.lstm[1].b_hh; a.c2 = c->c_cell2; a.h2 = c->c_hseq2_h;
-    a.out2 = R; a.T = Tmax; a.D = D; a.cb = cb;
-    if (!c->use_graph) {
-        for (int i = 0; i <= Tmax; i++) { a.t = i; launch_lstm_pair_step(s, a); }
-    } else {
-        constexpr int kBlock = 64;
-        auto & slot = c->lstm_graph;
-        if (slot.exec && (slot.out != R || slot.gi != c->c_gi || slot.B != B)) { (void) hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
-        if (!slot.exec) {
-            slot.exec = capture_graph(s, [&] {
-                a.t_base = c->d_lstm_t;
-                for (int i = 0; i < kBlock; i++) { a.t = i; launch_lstm_pair_step(s, a); }
-                launch_add_int(s, c->d_lstm_t, kBlock);
-            });
-            slot.out = R; slot.gi = c->c_gi; slot.B = B;
-        }
-        const int hdr[2] = {0, Tmax};
-        HIP_OK(hipMemcpyAsync(c->d_lstm_t, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
-        HIP_OK(hipStreamSynchronize(s));                         // hdr is a stack object
-        for (int i0 = 0; i0 <= Tmax; i0 += kBlock) HIP_OK(hipGraphLaunch(slot.exec, s));
-    }
+    run_lstm_pair(c, cm.lstm, c->lstm_graph, cb, Ts, Tmax, R);
     // parity taps are handed out channel-major [C][T'] (one utterance)
     auto grab = [&](int stage, const float * buf, int C, size_t rows) {
         if (tap_stage != stage || !tap) return;
@@ -175,6 +191,134 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
 
 std::vector<float> engine_codec_decode(bark_context * c, const int32_t * codes, int n_q, int T, int tap_stage, std::vector<float> * tap) {
     return std::move(engine_codec_decode_many(c, {codes}, n_q, {T}, tap_stage, tap)[0]);
+}
+
+// EnCodec encode (HF modeling_encodec.py: EncodecEncoder, EncodecResidualVectorQuantizer.encode): PCM -> latents -> codes, for up to 32 recordings in one
+// pass.  Time-major activations as in the decoder; the stages are ragged (ceil at every stride), so each stage has its own row table (d_enc_T) and every
+// launch takes its stage's CodecBatch with factor 1.  The first convolution reads the f16 image of the PCM, like every other convolution operand (R1).
+std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, const std::vector<const float *> & pcm, const std::vector<int> & n_samples, int n_q,
+                                                           int tap_stage, std::vector<float> * tap) {
+    HIP_OK(hipSetDevice(c->device));
+    c->enc_latents = nullptr; c->enc_latent_rows = 0;
+    CodecModel & cm = c->codec;
+    const CodecModel::Encoder & en = cm.enc;
+    if (!en.present) throw std::runtime_error("codec: the model file holds no encoder");
+    const int B = (int) n_samples.size();
+    if (B < 1 || B > 32 || pcm.size() != n_samples.size()) throw std::runtime_error("codec: 1..32 recordings per call");
+    if (tap_stage >= 0 && B != 1) throw std::runtime_error("codec: activation taps take one recording");
+    if (tap_stage > 6) throw std::runtime_error("codec: the encoder has tap stages 0..6");
+    if (n_q <= 0 || n_q > cm.n_q) throw std::runtime_error("codec: n_q outside the file's codebooks");
+    // rows of every recording at the five stages, and their prefix sums: hdr[stage] = {[0, 32) rows, [40, 73) prefix sums}
+    int hdr[5][80] = {};
+    int ch[5]; ch[0] = en.F;
+    for (int b = 0; b < B; b++) {
+        const int n = n_samples[(size_t) b];
+        if (n < 1 || n > 4096 * 320 || !pcm[(size_t) b]) throw std::runtime_error("codec: a recording needs 1 .. 4096 frames of samples");
+        for (int i = 0; i < n; i++) if (!std::isfinite(pcm[(size_t) b][i])) throw std::runtime_error("codec: non-finite sample");
+        int L = n;
+        for (int st = 0; st < 5; st++) {
+            hdr[st][b] = L; hdr[st][40 + b + 1] = hdr[st][40 + b] + L;
+            if (st < 4) L = (L + en.blocks[st].stride - 1) / en.blocks[st].stride;
+        }
+    }
+    for (int st = 0; st < 4; st++) ch[st + 1] = en.blocks[st].down.cout;
+    int rows[5];
+    size_t need = 0;
+    for (int st = 0; st < 5; st++) { rows[st] = hdr[st][40 + B]; need = std::max(need, (size_t) rows[st] * ch[st]); }
+    const int Ts = rows[4], D = cm.D, Hd = cm.hp.hidden_dim;
+    int Tmax = 0;
+    for (int b = 0; b < B; b++) Tmax = std::max(Tmax, hdr[4][b]);
+    need = std::max(need, (size_t) Ts * std::max(D, Hd));
+    hipStream_t s = c->stream;
+    ensure_codec_scratch(c, need, Ts, D);
+    if (!c->d_enc_T) c->d_enc_T = dev_alloc<int>(c, 5 * 80);
+    if ((size_t) rows[0] > c->d_pcm_elems) { c->d_pcm = dev_alloc<float>(c, (size_t) rows[0]); c->d_pcm_elems = (size_t) rows[0]; }
+    if ((size_t) n_q * Ts > c->d_codes_elems) { c->d_codes = dev_alloc<int32_t>(c, (size_t) n_q * Ts); c->d_codes_elems = (size_t) n_q * Ts; }
+    for (int b = 0; b < B; b++)
+        HIP_OK(hipMemcpyAsync(c->d_pcm + hdr[0][40 + b], pcm[(size_t) b], (size_t) n_samples[(size_t) b] * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->d_enc_T, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                            // hdr is a stack object
+    CodecBatch cb[5];
+    for (int st = 0; st < 5; st++) { cb[st].T = c->d_enc_T + 80 * st; cb[st].Tpre = c->d_enc_T + 80 * st + 40; cb[st].B = B; }
+    float * A = c->cbuf[0], * Bf = c->cbuf[1], * R = c->cbuf[2];
+    half_t * H0 = c->cbuf_hh[0], * H1 = c->cbuf_hh[1], * H2 = c->cbuf_hh[2];
+
+    auto conv = [&](const CodecModel::Conv & cv, const half_t * xh, int st, const float * add, float * y, half_t * yh_raw, half_t * yh_elu) {
+        ConvTmArgs a;
+        a.W = cv.wm; a.w32 = cv.w32; a.bias = cv.b; a.cin = cv.cin; a.cout = cv.cout; a.cout32 = (cv.cout + 31) & ~31; a.K = cv.k;
+        a.kd = cv.k * cv.cin; a.kd16 = (a.kd + 15) & ~15;
+        a.xh = xh; a.rows_in = rows[st]; a.tm_in = 1; a.cb = cb[st];
+        a.add = add; a.y = y; a.yh_raw = yh_raw; a.yh_elu = yh_elu;
+        launch_conv_tm(s, a);
+    };
+    auto grab = [&](int stage, const float * buf, int C, size_t nrows) {
+        if (tap_stage != stage || !tap) return;
+        std::vector<float> tm((size_t) C * nrows);
+        HIP_OK(hipMemcpyAsync(tm.data(), buf, tm.size() * 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        tap->resize(tm.size());
+        for (size_t r = 0; r < nrows; r++) for (int k = 0; k < C; k++) (*tap)[(size_t) k * nrows + r] = tm[r * (size_t) C + k];
+    };
+    const bool taps = tap_stage >= 0;
+    for (auto & e : c->enc_ev) if (!e) HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventRecord(c->enc_ev[0], s));
+    launch_act_round(s, c->d_pcm, (size_t) rows[0], 0, H0);                  // the PCM's f16 image [rows][1]
+    conv(en.init, H0, 0, nullptr, taps ? A : nullptr, H1, H2);              // H1 = f16(x): shortcut input, H2 = f16(ELU(x)): conv1 input
+    grab(0, A, ch[0], (size_t) rows[0]);
+    for (int b = 0; b < 4; b++) {
+        const CodecModel::EncBlock & bl = en.blocks[b];
+        // residual block: shortcut(x) + conv2(elu(conv1(elu(x)))), then ELU: the strided convolution's input
+        conv(bl.c1, H2, b, nullptr, nullptr, nullptr, H0);
+        conv(bl.c2, H0, b, nullptr, R, nullptr, nullptr);
+        conv(bl.sc, H1, b, R, nullptr, nullptr, H0);
+        ConvDownArgs d;
+        d.W = bl.down.wm; d.w32 = bl.down.w32; d.bias = bl.down.b; d.cin = bl.down.cin; d.cout = bl.down.cout; d.cout32 = (bl.down.cout + 31) & ~31;
+        d.K = bl.down.k; d.stride = bl.stride; d.kd = d.K * d.cin; d.kd16 = (d.kd + 15) & ~15;
+        d.xh = H0; d.rows_out = rows[b + 1]; d.cb_in = cb[b]; d.cb_out = cb[b + 1];
+        if (b < 3) { d.y = taps ? A : nullptr; d.yh_raw = H1; d.yh_elu = H2; }
+        else { d.y = Bf; d.yh_raw = c->c_xt_h; }                            // Bf = x [row][D] for the skip; its f16 image is the LSTM's input
+        launch_conv_down(s, d);
+        grab(1 + b, b < 3 ? A : Bf, ch[b + 1], (size_t) rows[b + 1]);
+    }
+    run_lstm_pair(c, en.lstm, c->lstm_graph_enc, cb[4], Ts, Tmax, R);
+    launch_add(s, R, Bf, (size_t) D * Ts, A);                               // y + x
+    grab(5, A, D, (size_t) Ts);
+    launch_act_round(s, A, (size_t) D * Ts, 1, H0);
+    conv(en.fin, H0, 4, nullptr, Bf, nullptr, nullptr);                     // Bf = latent [row][H]
+    grab(6, Bf, Hd, (size_t) Ts);
+    launch_rvq_encode(s, cm.codebooks, cm.hp.n_bins, Hd, Bf, n_q, Ts, c->d_codes, cb[4]);
+    HIP_OK(hipEventRecord(c->enc_ev[1], s));
+    c->enc_latents = Bf; c->enc_latent_rows = Ts;
+    std::vector<int32_t> all((size_t) n_q * Ts);
+    HIP_OK(hipMemcpyAsync(all.data(), c->d_codes, all.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->enc_ev[0], c->enc_ev[1])); c->enc_device_us = 1e3 * ms; }
+    std::vector<std::vector<int32_t>> out((size_t) B);
+    for (int b = 0; b < B; b++) out[(size_t) b].assign(all.begin() + (size_t) n_q * hdr[4][40 + b], all.begin() + (size_t) n_q * hdr[4][40 + b + 1]);
+    return out;
+}
+
+std::vector<int32_t> engine_rvq_encode(bark_context * c, const float * latents, int T, int n_q) {
+    HIP_OK(hipSetDevice(c->device));
+    c->enc_latents = nullptr; c->enc_latent_rows = 0;
+    CodecModel & cm = c->codec;
+    if (!cm.enc.present) throw std::runtime_error("codec: the model file holds no encoder");
+    if (T < 1 || T > 65536 || n_q <= 0 || n_q > cm.n_q) throw std::runtime_error("codec: bad latent shape / n_q");
+    const int Hd = cm.hp.hidden_dim;
+    hipStream_t s = c->stream;
+    ensure_codec_scratch(c, (size_t) T * std::max(Hd, cm.D), 0, cm.D);
+    if (!c->d_enc_T) c->d_enc_T = dev_alloc<int>(c, 5 * 80);
+    if ((size_t) n_q * T > c->d_codes_elems) { c->d_codes = dev_alloc<int32_t>(c, (size_t) n_q * T); c->d_codes_elems = (size_t) n_q * T; }
+    int hdr[80] = {};
+    hdr[0] = T; hdr[41] = T;
+    HIP_OK(hipMemcpyAsync(c->d_enc_T, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->cbuf[1], latents, (size_t) T * Hd * 4, hipMemcpyHostToDevice, s));
+    CodecBatch cb; cb.T = c->d_enc_T; cb.Tpre = c->d_enc_T + 40; cb.B = 1;
+    launch_rvq_encode(s, cm.codebooks, cm.hp.n_bins, Hd, c->cbuf[1], n_q, T, c->d_codes, cb);
+    std::vector<int32_t> codes((size_t) n_q * T);
+    HIP_OK(hipMemcpyAsync(codes.data(), c->d_codes, codes.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));                            // also: hdr is a stack object
+    return codes;
 }
 
 }  // namespace barkhip

@@ -86,6 +86,8 @@ bark_context::~bark_context() {
     }
     for (auto & g : batch_graphs) if (g.second) (void) hipGraphExecDestroy(g.second);
     if (lstm_graph.exec) (void) hipGraphExecDestroy(lstm_graph.exec);
+    if (lstm_graph_enc.exec) (void) hipGraphExecDestroy(lstm_graph_enc.exec);
+    for (auto & e : enc_ev) if (e) (void) hipEventDestroy(e);
     if (codec_graph.exec) (void) hipGraphExecDestroy(codec_graph.exec);
     for (auto & g : fine_graphs) if (g) (void) hipGraphExecDestroy(g);
     for (void * p : allocs) (void) hipFree(p);
@@ -517,6 +519,65 @@ bark_context * engine_load(const char * path, const bark_context_params & params
         cm.codebooks = cb;
     }
 
+    // ---- codec encoder (optional; HF modeling_encodec.py EncodecEncoder: conv, 4 x (residual block, ELU, strided conv), LSTM, ELU, conv) -------------
+    // Uploaded into allocations of their own: the slab and everything that is derived from its size are the same with and without an encoder in the file.
+    if (mf.codec.count("encoder.model.0.conv.conv.weight")) {
+        CodecModel::Encoder & en = cm.enc;
+        auto up = [&](const void * src, size_t bytes) -> const void * {
+            void * d = nullptr;
+            HIP_OK(hipMalloc(&d, std::max<size_t>(bytes, 4)));
+            ctx->weights->extra.push_back(d);
+            HIP_OK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+            return d;
+        };
+        auto conv = [&](const std::string & p, CodecModel::Conv & cv) {
+            const TensorRef & t = codec_weight(p + ".weight", 0, 0);                 // [cout][cin][k] f16
+            if (t.n_dims != 3 || t.ne[3] != 1 || t.ne[0] > 64 || t.ne[1] > 4096 || t.ne[2] > 4096) throw std::runtime_error("codec conv weight '" + p + "' has an unexpected shape");
+            cv.k = (int) t.ne[0]; cv.cin = (int) t.ne[1]; cv.cout = (int) t.ne[2];
+            const TensorRef & b = need(mf.codec, p + ".bias", 0, 0, 0);
+            if (b.nelements() != cv.cout) throw std::runtime_error("codec bias size mismatch at " + p);
+            cv.b = (const float *) up(b.data, (size_t) cv.cout * 4);
+            std::vector<float> f((size_t) t.nelements());
+            for (size_t i = 0; i < f.size(); i++) { uint16_t h; memcpy(&h, t.data + 2 * i, 2); f[i] = (float) __builtin_bit_cast(_Float16, h); }
+            cv.w32 = (const float *) up(f.data(), f.size() * 4);
+            if (cv.cin & 7) return;
+            const int kd = cv.k * cv.cin, kd16 = (kd + 15) & ~15, c32 = (cv.cout + 31) & ~31;       // C9m image, as the decoder's conv_image
+            std::vector<uint16_t> img((size_t) c32 * kd16, 0);
+            for (int co = 0; co < cv.cout; co++) for (int ci = 0; ci < cv.cin; ci++) for (int k = 0; k < cv.k; k++)
+                memcpy(&img[(size_t) co * kd16 + (size_t) k * cv.cin + ci], t.data + 2 * (((size_t) co * cv.cin + ci) * cv.k + k), 2);
+            cv.wm = (const half_t *) up(img.data(), img.size() * 2);
+        };
+        static const int enc_ratios[4] = {2, 4, 5, 8};      // the decoder's ratios reversed (modeling_encodec.py: EncodecEncoder)
+        conv("encoder.model.0.conv.conv", en.init);
+        en.F = en.init.cout;
+        int ch = en.F;
+        bool ok = en.init.cin == 1;
+        for (int i = 0; i < 4; i++) {
+            const int idx = 1 + 3 * i;
+            CodecModel::EncBlock & b = en.blocks[i];
+            conv("encoder.model." + std::to_string(idx) + ".block.1.conv.conv", b.c1);
+            conv("encoder.model." + std::to_string(idx) + ".block.3.conv.conv", b.c2);
+            conv("encoder.model." + std::to_string(idx) + ".shortcut.conv.conv", b.sc);
+            conv("encoder.model." + std::to_string(idx + 2) + ".conv.conv", b.down);
+            b.stride = enc_ratios[i];
+            ok = ok && b.c1.cin == ch && b.c2.cin == b.c1.cout && b.c2.cout == ch && b.sc.cin == ch && b.sc.cout == ch && b.down.cin == ch && b.down.k == 2 * b.stride;
+            ch = b.down.cout;
+        }
+        conv("encoder.model.15.conv.conv", en.fin);
+        ok = ok && ch == cm.D && en.fin.cin == ch && en.fin.cout == cm.hp.hidden_dim;
+        if (!ok) throw std::runtime_error("codec: encoder convolutions do not chain (channel counts / strides), or its LSTM width differs from the decoder's");
+        for (int l = 0; l < 2; l++) {
+            const std::string sfx = std::to_string(l);
+            const TensorRef & wi = codec_weight("encoder.model.13.lstm.weight_ih_l" + sfx, cm.D, 4 * cm.D);
+            const TensorRef & wh = codec_weight("encoder.model.13.lstm.weight_hh_l" + sfx, cm.D, 4 * cm.D);
+            en.lstm[l].w_ih = (const half_t *) up(wi.data, wi.nbytes());
+            en.lstm[l].w_hh = (const half_t *) up(wh.data, wh.nbytes());
+            en.lstm[l].b_ih = (const float *) up(need(mf.codec, "encoder.model.13.lstm.bias_ih_l" + sfx, 0, 4 * cm.D, 0).data, (size_t) 4 * cm.D * 4);
+            en.lstm[l].b_hh = (const float *) up(need(mf.codec, "encoder.model.13.lstm.bias_hh_l" + sfx, 0, 4 * cm.D, 0).data, (size_t) 4 * cm.D * 4);
+        }
+        en.present = true;
+    }
+
     init_runtime(ctx.get(), true);
     hipDeviceProp_t prop;
     HIP_OK(hipGetDeviceProperties(&prop, ctx->device));
@@ -527,7 +588,8 @@ bark_context * engine_load(const char * path, const bark_context_params & params
              prop.name, prop.gcnArchName, prop.multiProcessorCount, wfmt, ctx->weight_bytes / 1e6, ctx->gpt[0].hp.n_embd, ctx->gpt[1].hp.n_embd,
              ctx->gpt[2].hp.n_embd, ctx->gpt[0].hp.n_layer, ctx->gpt[1].hp.n_layer, ctx->gpt[2].hp.n_layer, (int) ctx->use_graph);
     ctx->description = buf;
-    if (params.verbosity >= MEDIUM) fprintf(stderr, "%s\n", buf);
+    if (cm.enc.present) ctx->description += ", codec encoder";
+    if (params.verbosity >= MEDIUM) fprintf(stderr, "%s\n", ctx->description.c_str());
     return ctx.release();
 }
 

@@ -290,4 +290,25 @@ void launch_lstm_pair_step(hipStream_t s, const LstmPairArgs & a);
 void launch_add_int(hipStream_t s, int * p, int v);       // *p += v
 void launch_add(hipStream_t s, const float * a, const float * b, size_t n, float * out);
 
+// ---- EnCodec encoder (codec_kernels.hip) ---------------------------------------------------------
+// The encoder's stages have ragged lengths (L, ceil(L / 2), ceil(L / 8), ceil(L / 40), ceil(L / 320) rows per recording), so every launch takes
+// the CodecBatch of ITS stage with factor 1: T / Tpre are that stage's row counts and prefix sums.  Its stride-1 convolutions are launch_conv_tm
+// as in the decoder; the down-sampling convolution (EncodecConv1d with stride: left pad K - stride and right pad rows_out * stride - rows_in, both
+// by reflection, inputs not longer than the larger pad zero-extended first - DESIGN.md section 3, "encoder padding") has kernels of its own:
+//   y[orow][co] = bias[co] + dot(kernel image of co, the K input rows of output row orow);   C9m over kd = k * cin + ci (W), else C9 on w32
+// cb_in / cb_out: the stages of the input and of the output rows (both with device arrays).
+struct ConvDownArgs {
+    const half_t * W = nullptr; const float * w32 = nullptr; const float * bias = nullptr;
+    int cin = 0, cout = 0, cout32 = 0, K = 0, stride = 1, kd = 0, kd16 = 0;
+    const half_t * xh = nullptr;
+    float * y = nullptr; half_t * yh_raw = nullptr, * yh_elu = nullptr;
+    int rows_out = 0;
+    CodecBatch cb_in, cb_out;
+};
+void launch_conv_down(hipStream_t s, const ConvDownArgs & a);
+// Greedy residual vector quantisation (EncodecResidualVectorQuantizer.encode), order C11q: per frame and stage q, d_j = sum_d (r_d - e_jd)^2 with
+// t = r_d - e_jd; p = t * t; acc = acc + p for d ascending (every operation rounded to f32), j* = argmin_j d_j (ties: the lowest j), r <- r - e_{q,j*}.
+// z [rows_total][Hd] f32 latents, the recordings back to back (cb); codes of recording b: [n_q][T[b]] at n_q Tpre[b]
+void launch_rvq_encode(hipStream_t s, const float * codebooks, int n_bins, int Hd, const float * z, int n_q, int rows_total, int32_t * codes, const CodecBatch & cb);
+
 }  // namespace barkhip

@@ -67,3 +67,11 @@ def from_generation(ctx) -> VoicePrompt:
     if not len(v.semantic) or not len(v.coarse):
         raise ValueError("from_generation: the context holds no generation")
     return v
+
+
+def from_audio(ctx, pcm, semantic) -> VoicePrompt:
+    """A voice prompt from a recording of the speaker (24 kHz mono float samples): the coarse and fine streams are the first 2 / 8 codebooks of the
+    EnCodec encoder's codes (ctx.codec_encode; the model file must carry the encoder).  The semantic ids come from the caller: Bark derives them from
+    the audio with a HuBERT model and its quantiser, which this library does not include."""
+    codes = ctx.codec_encode(pcm, 8)                  # [8][T]
+    return VoicePrompt(semantic, codes[:2].T, codes[:8].T)

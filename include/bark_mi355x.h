@@ -82,6 +82,28 @@ BARK_API int bark_hip_codec_decode(struct bark_context * bctx, const int32_t * c
  * 2..5 (the four upsampling blocks).  Returns the element count or -1. */
 BARK_API int bark_hip_codec_tap(struct bark_context * bctx, const int32_t * codes, int n_q, int T, int stage, float * out, int capacity);
 
+/* EnCodec encode (the other direction of the codec; the file must carry the SEANet encoder - the converter's files and the `small` / `large`
+ * synthetic files do, `toy` / `mini` do not).  Returns 1 if the context's model file holds the encoder, else 0. */
+BARK_API int bark_hip_has_codec_encoder(struct bark_context * bctx);
+/* pcm: n_samples floats, 24 kHz mono -> codes [n_q][T] (time contiguous, as bark_hip_codec_decode takes them; capacity in ids), greedy residual vector
+ * quantisation over the first n_q codebooks (rule C11q).  Returns T = ceil(n_samples / 320), or -1: no encoder in the file,
+ * n_samples < 1 or more than 4096 frames, n_q outside 1 .. the file's codebook count, a non-finite sample, capacity < n_q * T. */
+BARK_API int bark_hip_codec_encode(struct bark_context * bctx, const float * pcm, int n_samples, int n_q, int32_t * codes, int capacity);
+/* n <= 32 recordings in one pass (one launch per operator for all of them, as the decoder's batch); recording i's [n_q][T_i] codes back to back in
+ * codes_concat, bit-identical to n single calls.  Returns sum T_i or -1. */
+BARK_API int bark_hip_codec_encode_many(struct bark_context * bctx, const float * const * pcm, const int * n_samples, int n, int n_q, int32_t * codes_concat, int capacity);
+/* Per-layer parity tap of the encoder, one recording: activation [C][T'] after stage 0 (first conv), 1..4 (after each down-sampling conv), 5 (LSTM + skip),
+ * 6 (the latent [hidden_dim][T]).  Returns the element count or -1. */
+BARK_API int bark_hip_codec_encode_tap(struct bark_context * bctx, const float * pcm, int n_samples, int stage, float * out, int capacity);
+/* The latents [sum T_i][hidden_dim] (time-major, the recordings back to back) that the last bark_hip_codec_encode / _many call of this context quantised;
+ * valid until the context's next codec call.  Returns the row count, or -1 (none held, capacity in floats too small). */
+BARK_API int bark_hip_codec_encode_latents(struct bark_context * bctx, float * out_TxH, int capacity);
+/* Time on the context's stream between the first and the last kernel of its last bark_hip_codec_encode / _many call, in microseconds (hipEvents;
+ * the uploads in front and the copy of the codes behind are outside); < 0: no call yet. */
+BARK_API double bark_hip_codec_encode_device_us(struct bark_context * bctx);
+/* Kernel-level hook (tests): latents [T][hidden_dim] -> codes [n_q][T] by the RVQ kernel alone (T <= 65536).  Returns T or -1. */
+BARK_API int bark_hip_rvq_encode(struct bark_context * bctx, const float * latents_TxH, int T, int n_q, int32_t * codes);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);

@@ -435,9 +435,90 @@ def main_voice(preset: str, n_sem: int):
     print("wrote", dst, os.path.getsize(dst), "bytes")
 
 
+def build_hf_encoder(hp, tens, n_q: int):
+    """HF EncodecEncoder + EncodecResidualVectorQuantizer on the file's tensors (`encoder.model.` -> `layers.`, as build_hf_codec does for the decoder)"""
+    import torch
+    from transformers.models.encodec.configuration_encodec import EncodecConfig
+    from transformers.models.encodec.modeling_encodec import EncodecEncoder, EncodecResidualVectorQuantizer
+
+    cfg = EncodecConfig(num_filters=hp["n_filters"], hidden_size=hp["hidden_dim"], codebook_size=hp["n_bins"], codebook_dim=hp["hidden_dim"],
+                        use_causal_conv=True, norm_type="time_group_norm", target_bandwidths=[n_q * 0.75])
+    assert cfg.num_quantizers == n_q, cfg.num_quantizers
+    enc = EncodecEncoder(cfg)
+    for mod in enc.modules():
+        if hasattr(mod, "norm_type"):
+            mod.norm_type = "weight_norm"     # the file holds the folded weight: plain convolutions, no GroupNorm
+    t = lambda a: torch.from_numpy(np.array(a, dtype=np.float32))
+    sd = {}
+    for name, arr in tens.items():
+        if name.startswith("encoder."):
+            sd[name.replace("encoder.model.", "layers.").replace(".conv.conv.", ".conv.")] = t(arr)
+    own = enc.state_dict()
+    for k, v in sd.items():
+        assert k in own and tuple(own[k].shape) == tuple(v.shape), (k, v.shape)
+    assert all(k in sd or ".norm." in k for k in own), [k for k in own if k not in sd and ".norm." not in k]
+    enc.load_state_dict({k: sd.get(k, v) for k, v in own.items()})
+    vq = EncodecResidualVectorQuantizer(cfg)
+    for q in range(n_q):
+        vq.layers[q].codebook.embed.copy_(t(tens[f"quantizer.vq.layers.{q}._codebook.embed"]))
+    return enc.eval(), vq.eval()
+
+
+def main_encoder(preset: str):
+    """tests/golden/hf_<preset>_encoder_s0.npz: HF EncodecEncoder and EncodecResidualVectorQuantizer.encode (8 codebooks) on the synthetic `preset` codec
+    weights, on the first n samples of tests/codec_encoder_ref.fixture_signal.  Per length n: the f32 latent [H][T], HF's codes [8][T], the activations behind
+    the engine's taps (`toy_enc`; for n = 24000 only stages 4 and 5, to keep the file small) and latent_f16emu_maxabs - the largest deviation from the f32
+    latent of the same HF encoder with the input of every Conv1d / LSTM rounded to f16 by a forward pre-hook: the reference's own sensitivity to the
+    operand format of the engine, measured without the engine."""
+    import torch
+    from tests.codec_encoder_ref import FIXTURE_LENGTHS, fixture_signal
+    torch.set_num_threads(8)
+    hp, tens = read_model_file(ensure_model(preset, 0))["codec"]
+    enc, vq = build_hf_encoder(hp, tens, 8)
+    tap_layers = (0, 3, 6, 9, 12, 13, 15)
+    out = {"lengths": np.array(FIXTURE_LENGTHS[preset], np.int32)}
+
+    def run(x, keep):
+        h = torch.from_numpy(x)[None, None]
+        for i, layer in enumerate(enc.layers):
+            h = layer(h)
+            if i in tap_layers:
+                keep.append(h[0].numpy().copy())
+        return h
+
+    def round_input(mod, args):
+        return tuple(a.half().float() if torch.is_tensor(a) and a.is_floating_point() else a for a in args)
+
+    with torch.no_grad():
+        for n in FIXTURE_LENGTHS[preset]:
+            x = fixture_signal(n)
+            taps = []
+            z = run(x, taps)
+            codes = vq.encode(z, bandwidth=6.0)[:, 0].numpy().astype(np.int32)
+            hooks = [m.register_forward_pre_hook(round_input) for m in enc.modules() if isinstance(m, (torch.nn.Conv1d, torch.nn.LSTM))]
+            z16 = run(x, [])
+            for hk in hooks:
+                hk.remove()
+            out[f"latent_n{n}"] = z[0].numpy()
+            out[f"codes_n{n}"] = codes
+            out[f"latent_f16emu_maxabs_n{n}"] = np.float64((z16 - z).abs().max().item())
+            if preset == "toy_enc":
+                for st in range(6):
+                    if n < 24000 or st >= 4:
+                        out[f"tap{st}_n{n}"] = taps[st]
+            print(n, "->", tuple(z.shape), "latent rms %.3f" % float(z.pow(2).mean().sqrt()), "f16emu max abs %.3e" % out[f"latent_f16emu_maxabs_n{n}"])
+    dst = os.path.join(ROOT, "tests", "golden", f"hf_{preset}_encoder_s0.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
 def main():
     import torch
 
+    if len(sys.argv) > 1 and sys.argv[1] == "encoder":
+        for preset in (sys.argv[2:] or ["toy_enc", "small"]):
+            main_encoder(preset)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "stages":
         main_stages(sys.argv[2] if len(sys.argv) > 2 else "small", int(sys.argv[3]) if len(sys.argv) > 3 else 256)
         return

@@ -48,13 +48,16 @@ class Preset:
     codec_filters: int = 32      # EnCodec num_filters (24 kHz model: 32)
     codec_hidden: int = 128      # RVQ / latent dimension
     codec_n_q: int = 32          # quantizers stored in the file (24 kbps); 8 are used at 6 kbps
-    with_encoder: bool = True    # the real file also carries the (unused here) SEANet encoder
+    with_encoder: bool = True    # the real file also carries the SEANet encoder (bark_hip_codec_encode)
 
 
 PRESETS = {
     # head_dim is 64 in every real Bark model; the toy presets keep that.
     "toy": Preset(n_embd=128, n_layer=2, n_head=2, codec_filters=8, codec_n_q=8, with_encoder=False),
     "mini": Preset(n_embd=256, n_layer=4, n_head=4, codec_filters=16, codec_n_q=8, with_encoder=False),
+    # toy / mini with the SEANet encoder in the codec section (the codec encoder's tests; `small` and `large` carry it as the real file does)
+    "toy_enc": Preset(n_embd=128, n_layer=2, n_head=2, codec_filters=8, codec_n_q=8, with_encoder=True),
+    "mini_enc": Preset(n_embd=256, n_layer=4, n_head=4, codec_filters=16, codec_n_q=8, with_encoder=True),
     "small": Preset(n_embd=768, n_layer=12, n_head=12),
     "large": Preset(n_embd=1024, n_layer=24, n_head=16),
 }
