@@ -373,6 +373,8 @@ void launch_conv_down(hipStream_t s, const ConvDownArgs & a) {
 // C11q: kRvqFrames frames per workgroup, their residuals in LDS; work-item i scores the codebook rows i, i + 256, .. against all of them (one read of
 // a row serves every frame), each distance one chain over d ascending: t = r_d - e_jd; p = t * t; acc = acc + p (-ffp-contract=off: nothing fused).
 // The pick is the smallest distance, ties to the lowest row: in the work-item by scanning its rows in ascending order, across work-items by comparing (d, j).
+// A frame in which no distance compared below +inf (a non-finite latent, or squares that overflow) has no pick: its code is -1 at this and every later
+// stage, its residual is left alone, and the host turns the -1 into an error (engine_codec.hip) - never a code.
 constexpr int kRvqFrames = 4, kRvqMaxDim = 1024;
 __global__ __launch_bounds__(256) void rvq_encode_kernel(const float * codebooks, int n_bins, int Hd, const float * z, int n_q, int rows_total, int32_t * codes, const CodecBatch cb) {
     __shared__ float r[kRvqFrames * kRvqMaxDim];
@@ -435,12 +437,14 @@ __global__ __launch_bounds__(256) void rvq_encode_kernel(const float * codebooks
                 const float od = wd[w * kRvqFrames + f]; const int oj = wj[w * kRvqFrames + f];
                 if (od < bd || (od == bd && oj < b)) { bd = od; b = oj; }
             }
-            pick[f] = min(b, n_bins - 1);
+            pick[f] = b < n_bins ? b : -1;
         }
         #pragma unroll
         for (int f = 0; f < kRvqFrames; f++) {
-            const float * e = E + (size_t) pick[f] * Hd;
-            for (int d = tid; d < Hd; d += 256) r[f * kRvqMaxDim + d] = r[f * kRvqMaxDim + d] - e[d];
+            if (pick[f] >= 0) {
+                const float * e = E + (size_t) pick[f] * Hd;
+                for (int d = tid; d < Hd; d += 256) r[f * kRvqMaxDim + d] = r[f * kRvqMaxDim + d] - e[d];
+            }
             if (tid == f && f < nf) {
                 int row0, rows;
                 utt_of_row(cb, 0, 1, f0 + f, row0, rows);

@@ -66,6 +66,11 @@ void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context
     HIP_OK(hipStreamSynchronize(s));                         // hdr is a stack object
     for (int i0 = 0; i0 <= Tmax; i0 += kBlock) HIP_OK(hipGraphLaunch(slot.exec, s));
 }
+
+// C11q: rvq_encode_kernel writes -1 for a frame in which no distance compared below +inf (a non-finite latent): an error, never a code
+void throw_on_missing_pick(const std::vector<int32_t> & codes) {
+    for (int32_t v : codes) if (v < 0) throw std::runtime_error("codec: a latent frame has no finite distance to any codebook row (non-finite latent)");
+}
 }  // namespace
 
 namespace barkhip {
@@ -214,7 +219,8 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
     for (int b = 0; b < B; b++) {
         const int n = n_samples[(size_t) b];
         if (n < 1 || n > 4096 * 320 || !pcm[(size_t) b]) throw std::runtime_error("codec: a recording needs 1 .. 4096 frames of samples");
-        for (int i = 0; i < n; i++) if (!std::isfinite(pcm[(size_t) b][i])) throw std::runtime_error("codec: non-finite sample");
+        // refused at the door: a sample that is not finite, or whose f16 image - what the first convolution reads - is not (|x| >= 65520)
+        for (int i = 0; i < n; i++) if (!std::isfinite(pcm[(size_t) b][i]) || !std::isfinite((float) (_Float16) pcm[(size_t) b][i])) throw std::runtime_error("codec: non-finite sample (or one beyond the f16 range)");
         int L = n;
         for (int st = 0; st < 5; st++) {
             hdr[st][b] = L; hdr[st][40 + b + 1] = hdr[st][40 + b] + L;
@@ -293,6 +299,7 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
     HIP_OK(hipMemcpyAsync(all.data(), c->d_codes, all.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->enc_ev[0], c->enc_ev[1])); c->enc_device_us = 1e3 * ms; }
+    throw_on_missing_pick(all);
     std::vector<std::vector<int32_t>> out((size_t) B);
     for (int b = 0; b < B; b++) out[(size_t) b].assign(all.begin() + (size_t) n_q * hdr[4][40 + b], all.begin() + (size_t) n_q * hdr[4][40 + b + 1]);
     return out;
@@ -318,6 +325,7 @@ std::vector<int32_t> engine_rvq_encode(bark_context * c, const float * latents, 
     std::vector<int32_t> codes((size_t) n_q * T);
     HIP_OK(hipMemcpyAsync(codes.data(), c->d_codes, codes.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));                            // also: hdr is a stack object
+    throw_on_missing_pick(codes);
     return codes;
 }
 

@@ -87,7 +87,9 @@ BARK_API int bark_hip_codec_tap(struct bark_context * bctx, const int32_t * code
 BARK_API int bark_hip_has_codec_encoder(struct bark_context * bctx);
 /* pcm: n_samples floats, 24 kHz mono -> codes [n_q][T] (time contiguous, as bark_hip_codec_decode takes them; capacity in ids), greedy residual vector
  * quantisation over the first n_q codebooks (rule C11q).  Returns T = ceil(n_samples / 320), or -1: no encoder in the file,
- * n_samples < 1 or more than 4096 frames, n_q outside 1 .. the file's codebook count, a non-finite sample, capacity < n_q * T. */
+ * n_samples < 1 or more than 4096 frames, n_q outside 1 .. the file's codebook count, a sample that is not finite or whose f16 image is not
+ * (|x| >= 65520: every convolution reads the f16 image of its input), a latent frame with no finite distance to any codebook row (an error, never a
+ * code), capacity < n_q * T. */
 BARK_API int bark_hip_codec_encode(struct bark_context * bctx, const float * pcm, int n_samples, int n_q, int32_t * codes, int capacity);
 /* n <= 32 recordings in one pass (one launch per operator for all of them, as the decoder's batch); recording i's [n_q][T_i] codes back to back in
  * codes_concat, bit-identical to n single calls.  Returns sum T_i or -1. */
@@ -101,7 +103,8 @@ BARK_API int bark_hip_codec_encode_latents(struct bark_context * bctx, float * o
 /* Time on the context's stream between the first and the last kernel of its last bark_hip_codec_encode / _many call, in microseconds (hipEvents;
  * the uploads in front and the copy of the codes behind are outside); < 0: no call yet. */
 BARK_API double bark_hip_codec_encode_device_us(struct bark_context * bctx);
-/* Kernel-level hook (tests): latents [T][hidden_dim] -> codes [n_q][T] by the RVQ kernel alone (T <= 65536).  Returns T or -1. */
+/* Kernel-level hook (tests): latents [T][hidden_dim] -> codes [n_q][T] by the RVQ kernel alone (T <= 65536).  Returns T, or -1: bad shape, or a frame
+ * with no finite distance to any codebook row (a NaN or infinite entry). */
 BARK_API int bark_hip_rvq_encode(struct bark_context * bctx, const float * latents_TxH, int T, int n_q, int32_t * codes);
 
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and

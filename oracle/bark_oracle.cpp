@@ -351,6 +351,13 @@ struct Codec {
     Conv init, fin;
     Lstm lstm[2];
     struct Block { ConvT up; Conv c1, c2, sc; } blocks[4];
+    // the SEANet encoder (optional: `encoder.model.*` in the file), its weights treated as the decoder's
+    struct Encoder {
+        bool present = false;
+        Conv init, fin;
+        Lstm lstm[2];
+        struct Block { Conv c1, c2, sc, down; int stride = 0; } blocks[4];
+    } enc;
 };
 
 static bool load_codec(Reader & r, Codec & c) {
@@ -419,6 +426,31 @@ static bool load_codec(Reader & r, Codec & c) {
              conv("decoder.model." + std::to_string(idx + 1) + ".shortcut.conv.conv", c.blocks[i].sc);
     }
     ok = ok && conv("decoder.model.15.conv.conv", c.fin);
+    if (ok && tens.count("encoder.model.0.conv.conv.weight")) {
+        // EncodecEncoder: conv, 4 x (residual block, ELU, strided conv), LSTM, ELU, conv - the decoder's ratios reversed
+        Codec::Encoder & e = c.enc;
+        ok = conv("encoder.model.0.conv.conv", e.init) && e.init.cin == 1;
+        int ch = e.init.cout;
+        for (int i = 0; i < 4 && ok; i++) {
+            const int idx = 1 + 3 * i;
+            Codec::Encoder::Block & b = e.blocks[i];
+            b.stride = ratios[3 - i];
+            ok = conv("encoder.model." + std::to_string(idx) + ".block.1.conv.conv", b.c1) &&
+                 conv("encoder.model." + std::to_string(idx) + ".block.3.conv.conv", b.c2) &&
+                 conv("encoder.model." + std::to_string(idx) + ".shortcut.conv.conv", b.sc) &&
+                 conv("encoder.model." + std::to_string(idx + 2) + ".conv.conv", b.down) &&
+                 b.c1.cin == ch && b.c2.cin == b.c1.cout && b.c2.cout == ch && b.sc.cin == ch && b.sc.cout == ch && b.down.cin == ch && b.down.k == 2 * b.stride;
+            ch = b.down.cout;
+        }
+        for (int l = 0; l < 2 && ok; l++) {
+            std::string s = std::to_string(l);
+            ok = getw("encoder.model.13.lstm.weight_ih_l" + s, e.lstm[l].w_ih) && getw("encoder.model.13.lstm.weight_hh_l" + s, e.lstm[l].w_hh) &&
+                 get("encoder.model.13.lstm.bias_ih_l" + s, e.lstm[l].b_ih) && get("encoder.model.13.lstm.bias_hh_l" + s, e.lstm[l].b_hh);
+        }
+        ok = ok && conv("encoder.model.15.conv.conv", e.fin) && e.fin.cin == ch && ch == c.init.cout && e.fin.cout == c.hidden_dim;
+        if (!ok) fprintf(stderr, "oracle: the codec encoder's tensors do not chain\n");
+        e.present = ok;
+    }
     for (int q = 0; ok; q++) {
         auto it = tens.find("quantizer.vq.layers." + std::to_string(q) + "._codebook.embed");
         if (it == tens.end()) break;
@@ -1384,7 +1416,7 @@ static std::vector<float> reflect_pad(const std::vector<float> & x, int C, int T
 
 // C9m: the convolution as a product on the f16 matrix cores (gemm_mfma), y[t][co] = C1m-dot(Wm[co], col_t) over kd = k * cin + ci
 static bool conv_uses_mfma(const Oracle & o, int cin) { return o.num.codec_mfma && o.num.act_round_f16 && o.num.dot_order == 0 && (cin & 7) == 0; }
-static std::vector<float> conv1d_mfma(const Conv & cv, const std::vector<float> & xp, int Tp, int T, int nth) {
+static std::vector<float> conv1d_mfma(const Conv & cv, const std::vector<float> & xp, int Tp, int T, int nth, int stride = 1) {
     const int kd = cv.k * cv.cin;
     if (cv.wm.empty()) {
         cv.wm_bits.resize((size_t) cv.cout * kd);
@@ -1396,32 +1428,36 @@ static std::vector<float> conv1d_mfma(const Conv & cv, const std::vector<float> 
     std::vector<float> X((size_t) T * kd), Y((size_t) T * cv.cout);
     #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1)
     for (int t = 0; t < T; t++)
-        for (int k = 0; k < cv.k; k++) for (int ci = 0; ci < cv.cin; ci++) X[(size_t) t * kd + (size_t) k * cv.cin + ci] = xp[(size_t) ci * Tp + t + k];
+        for (int k = 0; k < cv.k; k++) for (int ci = 0; ci < cv.cin; ci++) X[(size_t) t * kd + (size_t) k * cv.cin + ci] = xp[(size_t) ci * Tp + (size_t) t * stride + k];
     gemm_mfma(cv.wm[0], X.data(), kd, Y.data(), cv.cout, cv.cout, T, kd, nth);
     std::vector<float> y((size_t) cv.cout * T);
     for (int co = 0; co < cv.cout; co++) for (int t = 0; t < T; t++) y[(size_t) co * T + t] = Y[(size_t) t * cv.cout + co] + cv.b[co];
     return y;
 }
 
-// causal stride-1 conv: out[co][t] = b[co] + sum_{ci,k} w[co][ci][k] * xpad[ci][t + k]   (modeling_encodec.py:159-176)
-static std::vector<float> conv1d(const Oracle & o, const Conv & cv, const std::vector<float> & x, int T, int nth) {
+// causal conv: out[co][t] = b[co] + sum_{ci,k} w[co][ci][k] * xpad[ci][t * stride + k]   (modeling_encodec.py:159-176).  x: [cin][T]; the result has
+// Tout = ceil(T / stride) columns.  Padding (EncodecConv1d.forward): left = k - stride, right = Tout * stride - T, both by reflection (stride 1: the
+// decoder's k - 1 and 0).
+static std::vector<float> conv1d(const Oracle & o, const Conv & cv, const std::vector<float> & x, int T, int nth, int stride = 1, int * Tout = nullptr) {
     int Tp = 0;
-    std::vector<float> xp = reflect_pad(x, cv.cin, T, cv.k - 1, 0, Tp);
+    const int To = (T + stride - 1) / stride;
+    if (Tout) *Tout = To;
+    std::vector<float> xp = reflect_pad(x, cv.cin, T, cv.k - stride, To * stride - T, Tp);
     if (o.num.act_round_f16) for (float & v : xp) v = round_h(v);       // im2col to f16
-    if (conv_uses_mfma(o, cv.cin)) return conv1d_mfma(cv, xp, Tp, T, nth);
-    std::vector<float> y((size_t) cv.cout * T);
+    if (conv_uses_mfma(o, cv.cin)) return conv1d_mfma(cv, xp, Tp, To, nth, stride);
+    std::vector<float> y((size_t) cv.cout * To);
     #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1)
     for (int co = 0; co < cv.cout; co++) {
-        float * yo = y.data() + (size_t) co * T;
-        for (int t = 0; t < T; t++) yo[t] = 0.f;
+        float * yo = y.data() + (size_t) co * To;
+        for (int t = 0; t < To; t++) yo[t] = 0.f;
         for (int ci = 0; ci < cv.cin; ci++) {
             const float * xi = xp.data() + (size_t) ci * Tp;
             for (int k = 0; k < cv.k; k++) {
                 const float w = cv.w[((size_t) co * cv.cin + ci) * cv.k + k];
-                for (int t = 0; t < T; t++) yo[t] = fmaf(w, xi[t + k], yo[t]);
+                for (int t = 0; t < To; t++) yo[t] = fmaf(w, xi[(size_t) t * stride + k], yo[t]);
             }
         }
-        for (int t = 0; t < T; t++) yo[t] += cv.b[co];
+        for (int t = 0; t < To; t++) yo[t] += cv.b[co];
     }
     return y;
 }
@@ -1540,6 +1576,87 @@ static bool codec_decode(Oracle & o, const int32_t * codes, int n_q, int T, std:
     for (float & v : x) v = elu(v);
     pcm = conv1d(o, c.fin, x, Tc, nth);
     return true;
+}
+
+// C11q, one frame at a time: d_j = sum_d (r_d - e_jd)^2 formed as t = r_d - e_jd; p = t * t; acc = acc + p over d ascending, every
+// operation rounded to f32 (the Makefile's -ffp-contract=off: nothing fused); the pick is the first j whose distance compares below every earlier one
+// (ties to the lowest j); r <- r - e_j.  A frame in which no distance compares below +inf (a non-finite latent) is an error, never a code.
+// latents: [T][H]; codes: [n_q][T]
+static bool rvq_encode(const Codec & c, const float * latents, int T, int n_q, int32_t * codes) {
+    const int H = c.hidden_dim;
+    if (T <= 0 || n_q <= 0 || n_q > (int) c.codebooks.size()) return false;
+    std::vector<float> r(H);
+    for (int f = 0; f < T; f++) {
+        for (int d = 0; d < H; d++) r[d] = latents[(size_t) f * H + d];
+        for (int q = 0; q < n_q; q++) {
+            const float * E = c.codebooks[q].data();
+            float best = INFINITY; int bj = -1;
+            for (int j = 0; j < c.n_bins; j++) {
+                const float * e = E + (size_t) j * H;
+                float acc = 0.0f;
+                for (int d = 0; d < H; d++) { const float t = r[d] - e[d]; const float p = t * t; acc = acc + p; }
+                if (acc < best) { best = acc; bj = j; }
+            }
+            if (bj < 0) return false;
+            codes[(size_t) q * T + f] = bj;
+            const float * e = E + (size_t) bj * H;
+            for (int d = 0; d < H; d++) r[d] = r[d] - e[d];
+        }
+    }
+    return true;
+}
+
+// EnCodec encoder (HF modeling_encodec.py: EncodecEncoder), the restatement of the engine's engine_codec_encode_many for one recording: first convolution,
+// four times (residual block, ELU, strided convolution), two-layer LSTM with skip, ELU, last convolution.  Every convolution reads the f16 image of its
+// input under act_round_f16 - the first one too (the PCM).  latent: [H][T], T = ceil(n / 320).
+// tap: if tap_stage >= 0, *tap receives the activation after that stage (0 first conv, 1..4 strided convs, 5 LSTM + skip, 6 the latent), [C][T']
+static bool codec_encode_latent(Oracle & o, const float * pcm, int n, std::vector<float> & latent, int & T, int nth, int tap_stage = -1, std::vector<float> * tap = nullptr) {
+    const Codec::Encoder & e = o.codec.enc;
+    if (!e.present || !pcm || n < 1 || n > 4096 * 320 || tap_stage > 6) return false;
+    // a sample whose f16 image is not finite is refused at the door
+    for (int i = 0; i < n; i++) if (!std::isfinite(o.num.act_round_f16 ? round_h(pcm[i]) : pcm[i])) return false;
+    std::vector<float> x(pcm, pcm + n);
+    int L = n;
+    x = conv1d(o, e.init, x, L, nth);
+    if (tap_stage == 0) *tap = x;
+    for (int b = 0; b < 4; b++) {
+        const Codec::Encoder::Block & B = e.blocks[b];
+        // residual block: shortcut(x) + conv2(elu(conv1(elu(x))))
+        std::vector<float> r = x;
+        for (float & v : r) v = elu(v);
+        r = conv1d(o, B.c1, r, L, nth);
+        for (float & v : r) v = elu(v);
+        r = conv1d(o, B.c2, r, L, nth);
+        std::vector<float> s = conv1d(o, B.sc, x, L, nth);
+        for (size_t i = 0; i < s.size(); i++) s[i] = s[i] + r[i];
+        for (float & v : s) v = elu(v);
+        int Ln = 0;
+        x = conv1d(o, B.down, s, L, nth, B.stride, &Ln); L = Ln;
+        if (tap_stage == 1 + b) *tap = x;
+    }
+    const int D = e.fin.cin;
+    {   // 2-layer LSTM with skip connection
+        std::vector<float> y = lstm_layer(o, e.lstm[0], x, D, L, nth);
+        y = lstm_layer(o, e.lstm[1], y, D, L, nth);
+        for (size_t i = 0; i < x.size(); i++) x[i] = y[i] + x[i];
+    }
+    if (tap_stage == 5) *tap = x;
+    for (float & v : x) v = elu(v);
+    latent = conv1d(o, e.fin, x, L, nth);
+    if (tap_stage == 6) *tap = latent;
+    T = L;
+    return true;
+}
+
+// codes: [n_q][T]
+static bool codec_encode(Oracle & o, const float * pcm, int n, int n_q, std::vector<int32_t> & codes, int nth) {
+    std::vector<float> z; int T = 0;
+    if (n_q <= 0 || n_q > (int) o.codec.codebooks.size() || !codec_encode_latent(o, pcm, n, z, T, nth)) return false;
+    const int H = o.codec.hidden_dim;
+    std::vector<float> zt((size_t) T * H);
+    for (int d = 0; d < H; d++) for (int t = 0; t < T; t++) zt[(size_t) t * H + d] = z[(size_t) d * T + t];
+    codes.assign((size_t) n_q * T, 0);
+    return rvq_encode(o.codec, zt.data(), T, n_q, codes.data());
 }
 
 static Oracle * oracle_open(const char * path) {
@@ -1685,6 +1802,33 @@ int orc_codec_decode(void * h, const int32_t * codes, int n_q, int T, float * pc
     if (!codec_decode(*(Oracle *) h, codes, n_q, T, out, nth)) return -1;
     memcpy(pcm, out.data(), out.size() * 4);
     return (int) out.size();
+}
+
+int orc_has_codec_encoder(void * h) { return ((Oracle *) h)->codec.enc.present ? 1 : 0; }
+
+// activation after encoder stage `stage` (see codec_encode_latent), [C][T']; returns the element count or -1
+int orc_codec_encode_tap(void * h, const float * pcm, int n, int stage, float * out, int capacity, int nth) {
+    std::vector<float> z, tap; int T = 0;
+    if (stage < 0 || stage > 6 || !out) return -1;
+    if (!codec_encode_latent(*(Oracle *) h, pcm, n, z, T, nth, stage, &tap)) return -1;
+    if ((long) tap.size() > (long) capacity) return -1;
+    memcpy(out, tap.data(), tap.size() * sizeof(float));
+    return (int) tap.size();
+}
+
+// codes: [n_q][T], T = ceil(n / 320); returns T or -1
+int orc_codec_encode(void * h, const float * pcm, int n, int n_q, int32_t * codes, int nth) {
+    std::vector<int32_t> out;
+    if (!codes || !codec_encode(*(Oracle *) h, pcm, n, n_q, out, nth)) return -1;
+    memcpy(codes, out.data(), out.size() * sizeof(int32_t));
+    return (int) (out.size() / (size_t) n_q);
+}
+
+// rule C11q alone: latents [T][hidden_dim] -> codes [n_q][T]; returns T or -1
+int orc_rvq_encode(void * h, const float * latents_TxH, int T, int n_q, int32_t * codes) {
+    Oracle * o = (Oracle *) h;
+    if (!o->codec.enc.present || !latents_TxH || !codes) return -1;
+    return rvq_encode(o->codec, latents_TxH, T, n_q, codes) ? T : -1;
 }
 
 struct orc_result {

@@ -84,6 +84,10 @@ class Oracle:
         lib.orc_fine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         lib.orc_codec_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         lib.orc_codec_tap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        lib.orc_has_codec_encoder.argtypes = [C.c_void_p]
+        lib.orc_codec_encode_tap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        lib.orc_codec_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        lib.orc_rvq_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.orc_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self.h = lib.orc_open(model_path.encode())
         if not self.h:
@@ -216,6 +220,39 @@ class Oracle:
         if n < 0:
             raise RuntimeError("oracle codec tap failed")
         return out[:n].copy()
+
+    def has_codec_encoder(self) -> bool:
+        return bool(self.lib.orc_has_codec_encoder(self.h))
+
+    def codec_encode(self, pcm, n_q: int = 8) -> np.ndarray:
+        """24 kHz mono float samples -> codes [n_q][T], T = ceil(n / 320) (the engine's codec_encode)."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        codes = np.zeros((max(n_q, 1), max((len(x) + 319) // 320, 1)), np.int32)
+        n = self.lib.orc_codec_encode(self.h, x.ctypes.data, len(x), n_q, codes.ctypes.data, self.n_threads)
+        if n < 0:
+            raise RuntimeError("oracle codec encode failed")
+        return codes[:, :n].copy()
+
+    def codec_encode_tap(self, pcm, stage: int) -> np.ndarray:
+        """Activation of the encoder, channel-major [C][T']: stage 0 first conv, 1..4 down-sampling convs, 5 LSTM + skip, 6 latent."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        out = np.zeros(max(len(x), 1) * 64 + 4096, np.float32)
+        n = self.lib.orc_codec_encode_tap(self.h, x.ctypes.data, len(x), stage, out.ctypes.data, out.size, self.n_threads)
+        if n < 0:
+            raise RuntimeError("oracle codec encode tap failed")
+        rows = len(x)
+        for s in (2, 4, 5, 8)[:min(max(stage, 0), 4)]:
+            rows = (rows + s - 1) // s
+        return out[:n].copy().reshape(-1, rows)
+
+    def rvq_encode(self, latents_TxH, n_q: int = 8) -> np.ndarray:
+        """Rule C11q alone: latents [T][hidden_dim] -> codes [n_q][T]."""
+        z = np.ascontiguousarray(latents_TxH, dtype=np.float32)
+        assert z.ndim == 2
+        codes = np.zeros((max(n_q, 1), len(z)), np.int32)
+        if self.lib.orc_rvq_encode(self.h, z.ctypes.data, len(z), n_q, codes.ctypes.data) < 0:
+            raise RuntimeError("oracle rvq encode failed")
+        return codes
 
     def generate(self, text: str, p: OrcParams) -> dict:
         sem = np.zeros(1024, np.int32)

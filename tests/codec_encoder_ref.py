@@ -6,6 +6,10 @@ EncodecResidualVectorQuantizer.encode) on the tensors of a model file - the refe
   rvq_c11q         rule C11q: d_j = sum_d (r_d - e_jd)^2 as t = r_d - e_jd; p = t * t; acc = acc + p over d ascending, every
                    operation rounded to f32; argmin with ties to the lowest j; r <- r - e_j.  Bit for bit what rvq_encode_kernel computes.
   hf_margins       per frame and stage the f64 gap between the two smallest squared distances along HF's own greedy path (the decision rule of G2)
+  decided_frames   G2's rule: the frames whose codes a latent deviating from HF's cannot flip
+  write_tie_model / tie_latents / midpoint_latents / stage0_pick
+                   the adversarial inputs of C11q (exact ties, midpoints of two rows, scaled midpoints) and the stage-0 loop in the stated order and in the
+                   two orders a wrong kernel would most likely use (fused multiply-add, d descending)
 """
 import os
 import sys
@@ -142,3 +146,93 @@ def hf_margins(latents_TxH: np.ndarray, cbs: np.ndarray, codes: np.ndarray) -> n
         out[q] = s[:, 1] - s[:, 0]
         r = r - e[codes[q]]
     return out
+
+
+def decided_frames(z_TxH: np.ndarray, z_hf_TxH: np.ndarray, cbs: np.ndarray, codes_hf: np.ndarray) -> np.ndarray:
+    """[T] bool: a frame is decided when at every stage HF's margin exceeds 4 |z[t] - z_hf[t]|_2 max_j |e_qj| - the deviation of z from HF's latent cannot
+    flip one of its picks, so it must carry HF's codes"""
+    margins = hf_margins(z_hf_TxH, cbs, codes_hf)                                           # [n_q][T]
+    enorm = np.sqrt((cbs.astype(np.float64) ** 2).sum(-1)).max(-1)                          # [n_q]
+    delta = np.sqrt(((np.asarray(z_TxH, np.float64) - z_hf_TxH) ** 2).sum(-1))              # [T]
+    return (margins > 4.0 * delta[None, :] * enorm[:len(margins), None]).all(0)
+
+
+# ---- adversarial inputs of C11q ---------------------------------------------------------------------------------------------------------------------
+# (low row, its copy): both in one work-item of rvq_encode_kernel (j, j + 256), in neighbouring lanes, in different waves, the last row and a low one
+TIE_PAIRS = ((10, 266), (20, 21), (30, 94), (5, 1023))
+TIE_BOOKS = (0, 3)
+
+
+def write_tie_model(src: str, dst: str) -> np.ndarray:
+    """copy of a model file in which, in the codebooks TIE_BOOKS, the second row of every TIE_PAIRS entry is overwritten with the first; returns the
+    patched codebooks [8][bins][H]"""
+    import model_patch
+    buf = bytearray(open(src, "rb").read())
+    info = model_patch.walk(buf)["codec"]
+    for q in TIE_BOOKS:
+        t = info[f"quantizer.vq.layers.{q}._codebook.embed"]
+        ttype = int(np.frombuffer(buf, "<i4", 1, t["ttype_off"])[0])
+        assert ttype == 0 and len(t["dims"]) == 2, (ttype, t["dims"])               # f32 [bins][H]: dims = (H, bins)
+        H, bins = t["dims"]
+        assert t["end"] - t["data_off"] == 4 * H * bins and bins > max(max(p) for p in TIE_PAIRS)
+        for lo, hi in TIE_PAIRS:
+            a, b = t["data_off"] + 4 * H * lo, t["data_off"] + 4 * H * hi
+            buf[b:b + 4 * H] = buf[a:a + 4 * H]
+    tmp = dst + ".tmp%d" % os.getpid()
+    with open(tmp, "wb") as f:
+        f.write(buf)
+    os.replace(tmp, dst)
+    return codebooks(codec_tensors(dst)[1], 8)
+
+
+def tie_latents(cbs: np.ndarray) -> np.ndarray:
+    """[17][H] latents on the codebooks of write_tie_model: for every duplicated row of codebook 0 the row itself (both distances 0) and the row plus
+    N(0, 0.01) noise (equal non-zero distances); the same for codebook 3 behind random rows of codebooks 0 - 2, so that the tie arises at stage 3; the
+    all-zero latent"""
+    rng = np.random.default_rng(77)
+    H = cbs.shape[2]
+    out = []
+    for lo, _ in TIE_PAIRS:
+        out.append(cbs[0][lo].copy())
+        out.append((cbs[0][lo] + 0.01 * rng.standard_normal(H)).astype(np.float32))
+    for lo, _ in TIE_PAIRS:
+        head = ((cbs[0][rng.integers(100, 1000)] + cbs[1][rng.integers(0, 1024)]) + cbs[2][rng.integers(0, 1024)]).astype(np.float32)
+        out.append((head + cbs[3][lo]).astype(np.float32))
+        out.append((head + cbs[3][lo] + 0.01 * rng.standard_normal(H)).astype(np.float32))
+    out.append(np.zeros(H, np.float32))
+    return np.stack(out).astype(np.float32)
+
+
+def midpoint_latents(cbs: np.ndarray, T: int, scale: float = 1.0, seed: int = 0) -> np.ndarray:
+    """[T][H]: scale * f32((e_a + e_b) / 2) for pairs of stage-0 rows.  scale 1: random pairs - in exact arithmetic the latent is equally far from both
+    rows, so rounding alone decides the pick, and the residual carries the decision through the later stages.  Other scales: s (e_a + e_b) / 2 differs
+    in its two squared distances by (1 - s)(|e_a|^2 - |e_b|^2), so the pairs are recomputed as neighbours in the order of the rows' norms - the pairs
+    for which the scaled latent stays closest to equidistant."""
+    rng = np.random.default_rng(4242 + seed)
+    e = cbs[0].astype(np.float32)
+    if scale == 1.0:
+        a = rng.integers(0, len(e), T)
+        b = (a + 1 + rng.integers(0, len(e) - 1, T)) % len(e)
+    else:
+        order = np.argsort((e.astype(np.float64) ** 2).sum(1), kind="stable")
+        k = rng.integers(0, len(e) - 1, T)
+        a, b = order[k], order[k + 1]
+    mid = ((e[a].astype(np.float64) + e[b].astype(np.float64)) / 2).astype(np.float32)
+    return (mid * np.float32(scale)).astype(np.float32)
+
+
+def stage0_pick(latents_TxH: np.ndarray, e: np.ndarray, order: str = "c11q") -> np.ndarray:
+    """[T] stage-0 picks of C11q's loop ("c11q") and of the same loop with acc = f32(f64(acc) + f64(t) f64(t)) ("fused": what a fused multiply-add
+    computes) or with d running downwards ("descending") - the measures of how much an input set can tell these orders apart"""
+    r = np.asarray(latents_TxH, np.float32)
+    e = e.astype(np.float32)
+    H = r.shape[1]
+    acc = np.zeros((len(r), len(e)), np.float32)
+    for d in (range(H - 1, -1, -1) if order == "descending" else range(H)):
+        t = r[:, d, None] - e[None, :, d]
+        if order == "fused":
+            t64 = t.astype(np.float64)
+            acc = (acc.astype(np.float64) + t64 * t64).astype(np.float32)
+        else:
+            acc = acc + t * t
+    return np.argmin(acc, axis=1)

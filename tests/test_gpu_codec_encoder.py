@@ -119,10 +119,7 @@ def test_latent_taps_and_decided_codes_against_hf(env, preset, n):
     codes_hf = g[f"codes_n{n}"]
     codes = ctx.codec_encode(x, 8)
     assert codes.shape == codes_hf.shape
-    margins = ref.hf_margins(z_hf.T, cbs, codes_hf)                                      # [8][T]
-    enorm = np.sqrt((cbs.astype(np.float64) ** 2).sum(-1)).max(-1)                       # [8]
-    delta = np.sqrt(((z.T.astype(np.float64) - z_hf.T) ** 2).sum(-1))                    # [T]
-    decided = (margins > 4.0 * delta[None, :] * enorm[:, None]).all(0)
+    decided = ref.decided_frames(z.T, z_hf.T, cbs, codes_hf)
     agree = float((codes == codes_hf).mean())
     print(f"{preset} n={n}: {int(decided.sum())} of {len(decided)} frames decided, overall code agreement {agree:.4f}")
     assert np.array_equal(codes[:, decided], codes_hf[:, decided])
@@ -228,11 +225,31 @@ def test_refusals_leave_the_context_usable(env, toy_model):
         y = x.copy(); y[500] = bad
         assert enc(y, len(y), 8, codes.size) == -1
         assert lib.bark_hip_codec_encode_tap(h, y.ctypes.data, len(y), 6, out.ctypes.data, out.size) == -1
+    # a finite sample whose f16 image is infinite (every convolution reads the f16 image of its input): refused at the door, by all three entry points
+    y = x.copy(); y[500] = 1e5
+    with np.errstate(over="ignore"):
+        assert np.isfinite(y).all() and not np.isfinite(y.astype(np.float16)).all()
+    assert enc(y, len(y), 8, codes.size) == -1
+    assert lib.bark_hip_codec_encode_tap(h, y.ctypes.data, len(y), 6, out.ctypes.data, out.size) == -1
+    for stage in (0, 3):
+        assert lib.bark_hip_codec_encode_tap(h, y.ctypes.data, len(y), stage, out.ctypes.data, out.size) == -1
+    for where in (0, 1):                                                                     # one bad recording of two, either place
+        pair = [x, x]; pair[where] = y
+        p2 = (__import__("ctypes").c_void_p * 2)(*[a.ctypes.data for a in pair])
+        n2 = np.full(2, len(x), np.int32)
+        assert lib.bark_hip_codec_encode_many(h, p2, n2.ctypes.data, 2, 8, codes.ctypes.data, codes.size) == -1
     assert enc(x, len(x), 8, 8 * 4 - 1) == -1                                                # capacity too small
     assert lib.bark_hip_codec_encode_tap(h, x.ctypes.data, len(x), 7, out.ctypes.data, out.size) == -1
     assert lib.bark_hip_codec_encode_tap(h, x.ctypes.data, len(x), 6, out.ctypes.data, 10) == -1
     z = np.zeros((4, 128), np.float32)
     assert lib.bark_hip_rvq_encode(h, z.ctypes.data, 4, 9, codes.ctypes.data) == -1 and lib.bark_hip_rvq_encode(h, z.ctypes.data, 0, 8, codes.ctypes.data) == -1
+    # a frame with no finite distance to any codebook row is an error, never a code (C11q): NaN / inf entries, and squares that overflow
+    for bad in (np.nan, np.inf, -np.inf, 3e19):
+        for T, t in ((4, 2), (5, 4), (1, 0)):
+            zb = np.random.default_rng(3).standard_normal((T, 128)).astype(np.float32); zb[t, 7] = bad
+            for n_q in (1, 8):
+                codes[:] = 0
+                assert lib.bark_hip_rvq_encode(h, zb.ctypes.data, T, n_q, codes.ctypes.data) == -1, (bad, T, n_q)
     ptrs = (__import__("ctypes").c_void_p * 33)(*[x.ctypes.data] * 33)
     ns = np.full(33, len(x), np.int32)
     big = np.zeros(33 * 8 * 4, np.int32)
