@@ -98,6 +98,7 @@ EXPORTS = [
     "bark_hip_set_sampling_filter", "bark_hip_generate_batch_filtered", "bark_hip_batcher_submit_filtered", "bark_hip_sample_rows_filtered", "bark_hip_time_sample_filter",
     "bark_hip_set_voice_prompt", "bark_hip_generate_batch_voiced", "bark_hip_batcher_submit_voiced", "bark_hip_pick_rows",
     "bark_hip_has_codec_encoder", "bark_hip_codec_encode", "bark_hip_codec_encode_many", "bark_hip_codec_encode_tap", "bark_hip_rvq_encode", "bark_hip_codec_encode_latents", "bark_hip_codec_encode_device_us",
+    "bark_hip_load_semantic_encoder", "bark_hip_has_semantic_encoder", "bark_hip_semantic_encode", "bark_hip_semantic_encode_tap", "bark_hip_semantic_head", "bark_hip_semantic_encode_device_us",
 ]
 
 
@@ -149,6 +150,13 @@ def load_library() -> C.CDLL:
     lib.bark_hip_codec_encode_latents.argtypes = [vp, fp, C.c_int]
     lib.bark_hip_codec_encode_device_us.restype = C.c_double
     lib.bark_hip_codec_encode_device_us.argtypes = [vp]
+    lib.bark_hip_load_semantic_encoder.argtypes = [vp, C.c_char_p]
+    lib.bark_hip_has_semantic_encoder.argtypes = [vp]
+    lib.bark_hip_semantic_encode.argtypes = [vp, fp, C.c_int, ip, C.c_int]
+    lib.bark_hip_semantic_encode_tap.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.c_int]
+    lib.bark_hip_semantic_head.argtypes = [vp, fp, C.c_int, ip, fp]
+    lib.bark_hip_semantic_encode_device_us.restype = C.c_double
+    lib.bark_hip_semantic_encode_device_us.argtypes = [vp]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
     lib.bark_hip_generate_batch_seeded.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_uint32)]
     lib.bark_hip_generate_batch_ex.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams)]
@@ -444,6 +452,52 @@ class BarkContext:
         if self._lib.bark_hip_rvq_encode(self._h, z.ctypes.data, len(z), n_q, codes.ctypes.data) < 0:
             raise RuntimeError("bark_hip_rvq_encode failed")
         return codes
+
+    # ---- semantic tokens from audio (rule C12h): HuBERT + token head, weights from a file of their own (tools/convert_hubert.py) ----
+    def load_semantic_encoder(self, path: str):
+        """bark_hip_load_semantic_encoder: this context and the clones made afterwards share the encoder.  Raises on a file the loader refuses."""
+        if self._lib.bark_hip_load_semantic_encoder(self._h, os.fsencode(path)) != 0:
+            raise RuntimeError(f"bark_hip_load_semantic_encoder failed for {path}")
+        with open(path, "rb") as f:
+            hp = np.frombuffer(f.read(48), dtype="<i4")[1:]
+        self._hub_hp = dict(zip(("C", "H", "n_head", "F", "n_layer_stored", "output_layer", "pos_kernel", "pos_groups", "D", "n_classes", "ftype"), (int(v) for v in hp)))
+
+    def has_semantic_encoder(self) -> bool:
+        return bool(self._lib.bark_hip_has_semantic_encoder(self._h))
+
+    def semantic_encode(self, pcm16k) -> np.ndarray:
+        """16 kHz mono float samples -> semantic ids [T], T = (n - 400) // 320 + 1 (bark_hip_semantic_encode)."""
+        x = np.ascontiguousarray(pcm16k, dtype=np.float32).reshape(-1)
+        ids = np.zeros(max((len(x) - 400) // 320 + 1, 1), np.int32)
+        n = self._lib.bark_hip_semantic_encode(self._h, x.ctypes.data, len(x), ids.ctypes.data, ids.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_semantic_encode failed")
+        return ids[:n].copy()
+
+    def semantic_encode_tap(self, pcm16k, stage: int) -> np.ndarray:
+        """Parity tap (bark_hip_semantic_encode_tap), time-major rows: 0 conv 0 + norm + GELU [T0][C], 1 conv stack [T][C], 2 projection [T][H],
+        3 hidden_states[0], 4 hidden_states[output_layer], 5 logits [T][n_classes]."""
+        x = np.ascontiguousarray(pcm16k, dtype=np.float32).reshape(-1)
+        hp = getattr(self, "_hub_hp", None) or {"C": 512, "H": 768, "n_classes": 10000}
+        rows = max((len(x) - 10) // 5 + 1 if stage == 0 else (len(x) - 400) // 320 + 1, 1)
+        out = np.zeros(rows * max(hp["C"], hp["H"], hp["n_classes"]), np.float32)
+        n = self._lib.bark_hip_semantic_encode_tap(self._h, x.ctypes.data, len(x), stage, out.ctypes.data, out.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_semantic_encode_tap failed")
+        return out[:n].copy().reshape(rows, -1)
+
+    def semantic_head(self, feats_TxH, want_logits: bool = False):
+        """Kernel-level hook (bark_hip_semantic_head): the token head on rows [T][H] -> ids [T] (and logits [T][n_classes])."""
+        z = np.ascontiguousarray(feats_TxH, dtype=np.float32)
+        assert z.ndim == 2
+        ids = np.zeros(max(len(z), 1), np.int32)
+        logits = np.zeros((max(len(z), 1), self._hub_hp["n_classes"]), np.float32) if want_logits else None
+        if self._lib.bark_hip_semantic_head(self._h, z.ctypes.data, len(z), ids.ctypes.data, logits.ctypes.data if want_logits else None) < 0:
+            raise RuntimeError("bark_hip_semantic_head failed")
+        return (ids[:len(z)], logits) if want_logits else ids[:len(z)]
+
+    def semantic_encode_device_us(self) -> float:
+        return float(self._lib.bark_hip_semantic_encode_device_us(self._h))
 
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""

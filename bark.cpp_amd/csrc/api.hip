@@ -310,6 +310,47 @@ int bark_hip_rvq_encode(struct bark_context * bctx, const float * latents_TxH, i
     });
 }
 
+int bark_hip_load_semantic_encoder(struct bark_context * bctx, const char * path) {
+    if (!bctx || !path) return -1;
+    return guarded("bark_hip_load_semantic_encoder", -1, [&] { engine_load_semantic_encoder(bctx, path); return 0; });
+}
+
+int bark_hip_has_semantic_encoder(struct bark_context * bctx) { return (bctx && bctx->hub) ? 1 : 0; }
+
+int bark_hip_semantic_encode(struct bark_context * bctx, const float * pcm16k, int n_samples, int32_t * ids, int capacity) {
+    if (!bctx || !pcm16k || !ids) return -1;
+    return guarded("bark_hip_semantic_encode", -1, [&] {
+        if (n_samples >= 400 && (n_samples - 400) / 320 + 1 > capacity) throw std::runtime_error("output buffer too small");      // refused before any work
+        std::vector<int32_t> r = engine_semantic_encode(bctx, pcm16k, n_samples, -1, nullptr);
+        memcpy(ids, r.data(), r.size() * 4);
+        return (int) r.size();
+    });
+}
+
+int bark_hip_semantic_encode_tap(struct bark_context * bctx, const float * pcm16k, int n_samples, int stage, float * out, int capacity) {
+    if (!bctx || !pcm16k || !out || stage < 0) return -1;
+    return guarded("bark_hip_semantic_encode_tap", -1, [&] {
+        std::vector<float> tap;
+        engine_semantic_encode(bctx, pcm16k, n_samples, stage, &tap);
+        if ((long) tap.size() > (long) capacity) return -1;
+        memcpy(out, tap.data(), tap.size() * 4);
+        return (int) tap.size();
+    });
+}
+
+int bark_hip_semantic_head(struct bark_context * bctx, const float * feats_TxH, int T, int32_t * ids, float * logits_or_null) {
+    if (!bctx || !feats_TxH || !ids) return -1;
+    return guarded("bark_hip_semantic_head", -1, [&] {
+        std::vector<float> logits;
+        std::vector<int32_t> r = engine_semantic_head(bctx, feats_TxH, T, logits_or_null ? &logits : nullptr);
+        memcpy(ids, r.data(), r.size() * 4);
+        if (logits_or_null) memcpy(logits_or_null, logits.data(), logits.size() * 4);
+        return T;
+    });
+}
+
+double bark_hip_semantic_encode_device_us(struct bark_context * bctx) { return bctx ? bctx->hub_device_us : -1.0; }
+
 struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed) {
     if (!src) return nullptr;
     return guarded("bark_hip_clone_context", (bark_context *) nullptr, [&] { return engine_clone(src, seed); });

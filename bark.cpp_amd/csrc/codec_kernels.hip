@@ -8,6 +8,8 @@
 // per output phase over tap * cin + ci).  Convolutions whose input channel count is not a multiple of 8 (toy models) keep order C9 (one fmaf
 // chain in (ci, k) order) in a plain kernel; BARK_HIP_CROSSCHECK bit 10 (1024) sends every convolution there (oracle: set_codec_mfma(False)).
 // Every kernel takes a CodecBatch: the codec of a lock-step batch costs the launches of ONE utterance.
+// At the end of the file: the semantic encoder's own kernels (rule C12h) - convolution 0 with its norm over time and the grouped positional convolution;
+// its six strided convolutions are the valid mode of conv_down_*_kernel.
 #include "kernels.h"
 
 namespace barkhip {
@@ -279,6 +281,13 @@ __device__ __forceinline__ int conv_down_src_row(int K, int stride, int kk, int 
     else if (j >= Lp) j = 2 * Lp - 2 - j;
     return (j >= 0 && j < rows) ? j : -1;
 }
+// valid mode (no padding: the feature encoder of the semantic encoder, C12h): tap kk of output row t is input row t stride + kk, always inside the recording
+__device__ __forceinline__ int conv_valid_src_row(int stride, int kk, int t, int rows) {
+    const int j = t * stride + kk;
+    return j < rows ? j : -1;
+}
+// exact (erf) GELU, formed in double precision and rounded once - as the LSTM's gate functions are (C9)
+__device__ __forceinline__ float gelu_erf_canon(float x) { return (float) (0.5 * (double) x * (1.0 + erf((double) x * 0.70710678118654752440))); }
 __device__ __forceinline__ int utt_index_of_row(const CodecBatch & cb, int row) {
     int z = 0;
     while (z + 1 < cb.B && row >= cb.Tpre[z + 1]) z++;
@@ -308,7 +317,7 @@ __global__ __launch_bounds__(256) void conv_down_mfma_kernel(const ConvDownArgs 
         for (int e = 0; e < 8; e++) bv[e] = (half_t) 0.0f;
         if (live && kdd < a.kd) {
             const int kk = kdd / a.cin, ci0 = kdd - kk * a.cin;
-            const int j = conv_down_src_row(a.K, a.stride, kk, t, rows, rows_out);
+            const int j = a.valid ? conv_valid_src_row(a.stride, kk, t, rows) : conv_down_src_row(a.K, a.stride, kk, t, rows, rows_out);
             if (j >= 0) bv = *reinterpret_cast<const half8 *>(a.xh + (size_t) (in0 + j) * a.cin + ci0);
         }
         return bv;
@@ -329,11 +338,17 @@ __global__ __launch_bounds__(256) void conv_down_mfma_kernel(const ConvDownArgs 
         #pragma unroll
         for (int e = 0; e < 4; e++) {
             if (co + e >= a.cout) break;
-            const float v = acc[4 * g + e] + a.bias[co + e];
+            float v = acc[4 * g + e];
+            if (a.bias) v = v + a.bias[co + e];
             const size_t o = (size_t) orow * a.cout + co + e;
             if (a.y) a.y[o] = v;
             if (a.yh_raw) a.yh_raw[o] = to_half(v);
             if (a.yh_elu) a.yh_elu[o] = to_half(elu_canon(v));
+            if (a.y_gelu || a.yh_gelu) {
+                const float ge = gelu_erf_canon(v);
+                if (a.y_gelu) a.y_gelu[o] = ge;
+                if (a.yh_gelu) a.yh_gelu[o] = to_half(ge);
+            }
         }
     }
 }
@@ -349,15 +364,21 @@ __global__ __launch_bounds__(256) void conv_down_chain_kernel(const ConvDownArgs
     for (int ci = 0; ci < a.cin; ci++) {
         const float * wr = a.w32 + ((size_t) co * a.cin + ci) * a.K;
         for (int k = 0; k < a.K; k++) {
-            const int j = conv_down_src_row(a.K, a.stride, k, t, rows, rows_out);
+            const int j = a.valid ? conv_valid_src_row(a.stride, k, t, rows) : conv_down_src_row(a.K, a.stride, k, t, rows, rows_out);
             const float xv = j >= 0 ? (float) a.xh[(size_t) (in0 + j) * a.cin + ci] : 0.0f;
             acc = fmaf(wr[k], xv, acc);
         }
     }
-    const float v = acc + a.bias[co];
+    float v = acc;
+    if (a.bias) v = v + a.bias[co];
     if (a.y) a.y[idx] = v;
     if (a.yh_raw) a.yh_raw[idx] = to_half(v);
     if (a.yh_elu) a.yh_elu[idx] = to_half(elu_canon(v));
+    if (a.y_gelu || a.yh_gelu) {
+        const float ge = gelu_erf_canon(v);
+        if (a.y_gelu) a.y_gelu[idx] = ge;
+        if (a.yh_gelu) a.yh_gelu[idx] = to_half(ge);
+    }
 }
 
 void launch_conv_down(hipStream_t s, const ConvDownArgs & a) {
@@ -457,6 +478,122 @@ __global__ __launch_bounds__(256) void rvq_encode_kernel(const float * codebooks
 void launch_rvq_encode(hipStream_t s, const float * codebooks, int n_bins, int Hd, const float * z, int n_q, int rows_total, int32_t * codes, const CodecBatch & cb) {
     if (Hd < 1 || Hd > kRvqMaxDim || !cb.T) kernel_fail("bark-hip: the RVQ encoder takes latents of 1..%d dimensions (got %d)", kRvqMaxDim, Hd);
     hipLaunchKernelGGL(rvq_encode_kernel, dim3((rows_total + kRvqFrames - 1) / kRvqFrames), dim3(256), 0, s, codebooks, n_bins, Hd, z, n_q, rows_total, codes, cb);
+}
+
+// ---- semantic encoder (HuBERT feature encoder and positional convolution; rule C12h) --------------------------------
+// Convolution 0 (one input channel, K taps, stride s, no bias) with its per-channel norm over time.  T0 reaches 65 615 rows: the f32 result is never
+// stored, each output is one fmaf chain over k ascending and is formed twice.  Pass 1: work-item = channel, workgroup = kHubChunk consecutive rows; sum and
+// sum of squares of its rows in double precision, rows ascending.  Pass 2: the chunks' partial sums added in ascending order (a fixed tree: chain inside a
+// chunk, chain over chunks), mean = S / T0, var = SS / T0 - mean^2 (biased), both in double; rstd = 1 / sqrt(var + 1e-5) rounded to f32 once.  Pass 3:
+// ((y - mean) rstd) g + b in f32, erf GELU, f16 image (and the f32 value for the parity tap).
+constexpr int kHubChunk = 1024, kHubMaxK0 = 16;
+__device__ __forceinline__ float hub_conv0_dot(const half_t * w, const half_t * x, int K) {
+    float acc = 0.0f;
+    for (int k = 0; k < K; k++) acc = fmaf((float) w[k], (float) x[k], acc);
+    return acc;
+}
+__global__ __launch_bounds__(128) void hub_conv0_stats_kernel(const HubConv0Args a) {
+    const int c = blockIdx.y * 128 + threadIdx.x;
+    if (c >= a.C) return;
+    half_t w[kHubMaxK0];
+    for (int k = 0; k < a.K; k++) w[k] = a.w[(size_t) c * a.K + k];
+    const int t0 = blockIdx.x * kHubChunk, t1 = min(a.T0, t0 + kHubChunk);
+    double s = 0.0, ss = 0.0;
+    for (int t = t0; t < t1; t++) {
+        const double y = (double) hub_conv0_dot(w, a.xh + (size_t) t * a.stride, a.K);
+        s = s + y; ss = ss + y * y;
+    }
+    double * p = a.part + ((size_t) blockIdx.x * a.C + c) * 2;
+    p[0] = s; p[1] = ss;
+}
+__global__ __launch_bounds__(128) void hub_conv0_final_kernel(const HubConv0Args a) {
+    const int c = blockIdx.x * 128 + threadIdx.x;
+    if (c >= a.C) return;
+    const int nchunk = (a.T0 + kHubChunk - 1) / kHubChunk;
+    double s = 0.0, ss = 0.0;
+    for (int i = 0; i < nchunk; i++) { s = s + a.part[((size_t) i * a.C + c) * 2]; ss = ss + a.part[((size_t) i * a.C + c) * 2 + 1]; }
+    const double mean = s / (double) a.T0;
+    double var = ss / (double) a.T0 - mean * mean;
+    if (var < 0.0) var = 0.0;
+    a.stats[2 * c] = (float) mean;
+    a.stats[2 * c + 1] = (float) (1.0 / sqrt(var + 1e-5));
+}
+__global__ __launch_bounds__(256) void hub_conv0_emit_kernel(const HubConv0Args a) {
+    const size_t idx = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t) a.T0 * a.C) return;
+    const int t = (int) (idx / a.C), c = (int) (idx % a.C);
+    const float y = hub_conv0_dot(a.w + (size_t) c * a.K, a.xh + (size_t) t * a.stride, a.K);
+    float v = (y - a.stats[2 * c]) * a.stats[2 * c + 1];
+    v = v * a.g[c];
+    v = v + a.b[c];
+    const float ge = gelu_erf_canon(v);
+    a.yh[idx] = to_half(ge);
+    if (a.y) a.y[idx] = ge;
+}
+void launch_hub_conv0(hipStream_t s, const HubConv0Args & a) {
+    if (a.K < 1 || a.K > kHubMaxK0 || a.stride < 1 || a.T0 < 1 || (size_t) (a.T0 - 1) * a.stride + a.K > (size_t) a.n)
+        kernel_fail("bark-hip: the first feature convolution takes 1..%d taps and rows inside the recording (got K %d, stride %d, T0 %d, n %d)", kHubMaxK0, a.K, a.stride, a.T0, a.n);
+    const int nchunk = (a.T0 + kHubChunk - 1) / kHubChunk, cg = (a.C + 127) / 128;
+    hipLaunchKernelGGL(hub_conv0_stats_kernel, dim3(nchunk, cg), dim3(128), 0, s, a);
+    hipLaunchKernelGGL(hub_conv0_final_kernel, dim3(cg), dim3(128), 0, s, a);
+    const size_t n = (size_t) a.T0 * a.C;
+    hipLaunchKernelGGL(hub_conv0_emit_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, a);
+}
+int hub_conv0_chunks(int T0) { return (T0 + kHubChunk - 1) / kHubChunk; }
+
+// Grouped positional convolution (Conv1d(H, H, Kp, padding Kp / 2, groups G), for even Kp without its last output frame) on the f16 matrix cores, order
+// C9m per group: output row t, channel g Hg + co = bias + sum over kd = k Hg + ci of w[g Hg + co][ci][k] x[t + k - Kp / 2][g Hg + ci] (rows outside the
+// recording are zero).  The operand run of tap k is the Hg-element slice of ONE time row, so a lane's 8 consecutive kd never leave a row (Hg % 8 == 0).
+// One wave = 32 rows x 32 channels of one group (the image of a group is padded to co32 rows); epilogue: erf GELU in f32 - the value joins an f32 sum.
+__global__ __launch_bounds__(256) void pos_conv_mfma_kernel(const PosConvArgs a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int t = (blockIdx.x * 4 + w) * 32 + l31;
+    const int ct = a.co32 >> 5, grp = blockIdx.y / ct, ctile = blockIdx.y - grp * ct;
+    const int Hg = a.H / a.G, pad = a.Kp >> 1;
+    const bool live = t < a.T;
+    const int nkb = a.kd16 >> 4;
+    const half_t * wrow = a.W + ((size_t) grp * a.co32 + ctile * 32 + l31) * a.kd16 + 8 * half;
+    floatx16c acc;
+    #pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
+    auto load_b = [&](int kb) {
+        const int kdd = 16 * kb + 8 * half;
+        half8 bv;
+        #pragma unroll
+        for (int e = 0; e < 8; e++) bv[e] = (half_t) 0.0f;
+        if (live && kdd < a.kd) {
+            const int kk = kdd / Hg, ci0 = kdd - kk * Hg;
+            const int j = t + kk - pad;
+            if (j >= 0 && j < a.T) bv = *reinterpret_cast<const half8 *>(a.xh + (size_t) j * a.H + grp * Hg + ci0);
+        }
+        return bv;
+    };
+    int kb = 0;
+    for (; kb + 4 <= nkb; kb += 4) {
+        half8 av[4], bv[4];
+        #pragma unroll
+        for (int i = 0; i < 4; i++) { av[i] = *reinterpret_cast<const half8 *>(wrow + 16 * (kb + i)); bv[i] = load_b(kb + i); }
+        #pragma unroll
+        for (int i = 0; i < 4; i++) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[i], acc, 0, 0, 0);
+    }
+    for (; kb < nkb; kb++) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const half8 *>(wrow + 16 * kb), load_b(kb), acc, 0, 0, 0);
+    if (!live) return;
+    #pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const int co = ctile * 32 + 8 * g + 4 * half;
+        #pragma unroll
+        for (int e = 0; e < 4; e++) {
+            if (co + e >= Hg) break;
+            const int ch = grp * Hg + co + e;
+            const float v = acc[4 * g + e] + a.bias[ch];
+            a.y[(size_t) t * a.H + ch] = gelu_erf_canon(v);
+        }
+    }
+}
+void launch_pos_conv(hipStream_t s, const PosConvArgs & a) {
+    if (a.G < 1 || a.H % a.G || ((a.H / a.G) & 7) || (a.co32 & 31) || a.co32 < a.H / a.G || a.kd != a.Kp * (a.H / a.G) || (a.kd16 & 15) || a.kd16 < a.kd || a.T < 1)
+        kernel_fail("bark-hip: the positional convolution needs groups of a multiple of 8 channels and a padded kernel image (got H %d, G %d, Kp %d)", a.H, a.G, a.Kp);
+    hipLaunchKernelGGL(pos_conv_mfma_kernel, dim3((a.T + 127) / 128, a.G * (a.co32 / 32)), dim3(256), 0, s, a);
 }
 
 }  // namespace barkhip

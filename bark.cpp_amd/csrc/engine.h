@@ -66,6 +66,33 @@ struct CodecModel {
     struct Encoder { bool present = false; int F = 0; Conv init, fin; EncBlock blocks[4]; Lstm lstm[2]; } enc;
 };
 
+// The semantic encoder (rule C12h): HuBERT's feature encoder, projection, positional convolution and first `output_layer` layers, and
+// the token head (two LSTM layers, a linear layer, argmax), loaded from a file of its own (bark_hip_load_semantic_encoder).  Immutable after load and held
+// by shared pointer: the clones of a context share the device copy.
+struct HubertModel {
+    HubertHparams hp;
+    int device = 0;
+    std::vector<void *> bufs;                           // every device allocation of the model (freed with it)
+    const half_t * conv0_w = nullptr; const float * gn_g = nullptr, * gn_b = nullptr; int k0 = 0;
+    struct Conv { const half_t * wm = nullptr; const float * w32 = nullptr; int k = 0, stride = 0; } conv[6];      // C9m images [C32][kd16], kd = k C + ci
+    const float * fp_ln_g = nullptr, * fp_ln_b = nullptr, * fp_b = nullptr; const half_t * fp_w = nullptr;
+    const half_t * pos_w = nullptr; const float * pos_b = nullptr; int pos_co32 = 0, pos_kd = 0, pos_kd16 = 0;   // [G][co32][kd16], kd = k (H / G) + ci
+    const float * enc_ln_g = nullptr, * enc_ln_b = nullptr;
+    struct Layer {
+        const half_t * qkv_w = nullptr, * o_w = nullptr, * fc1_w = nullptr, * fc2_w = nullptr;         // q, k and v rows stacked: [3 H][H]
+        const float * qkv_b = nullptr, * o_b = nullptr, * fc1_b = nullptr, * fc2_b = nullptr, * ln1_g = nullptr, * ln1_b = nullptr, * ln2_g = nullptr, * ln2_b = nullptr;
+    };
+    std::vector<Layer> layers;
+    CodecModel::Lstm lstm[2];
+    const half_t * out_w = nullptr; const float * out_b = nullptr;
+    const uint16_t * gelu_erf_lut = nullptr;            // f16(erf GELU(h)) for every f16 h: the FFN's epilogue (LinArgs::lut)
+    HubertModel() = default;
+    HubertModel(const HubertModel &) = delete;
+    HubertModel & operator=(const HubertModel &) = delete;
+    ~HubertModel();
+};
+constexpr int kHubMaxFrames = 1024;                     // T <= 1024: n <= 328 079 samples
+
 // A voice prompt (rule C10v): the speaker history the three stage loops start from, copied from a bark_hip_voice_prompt.  Held
 // by shared pointer: a context, the utterances of a job and the requests of a collector share one immutable copy.
 struct VoicePrompt { std::vector<int32_t> semantic, coarse, fine; };      // [n_sem], [Tc][2], [Tf][8]
@@ -137,6 +164,23 @@ struct bark_context {
     float * d_pcm = nullptr; size_t d_pcm_elems = 0;    // encoder: the recordings' samples back to back
     hipEvent_t enc_ev[2] = {nullptr, nullptr}; double enc_device_us = -1.0;      // events around the kernels of an encode call, and what the last call took between them
     const float * enc_latents = nullptr; int enc_latent_rows = 0;      // the latents [rows][hidden_dim] of the last encode call, until the next codec call of this context
+    LstmGraph lstm_graph_hub;                           // ... and with the token head's (semantic encoder)
+    // semantic encoder: the model (shared with clones) and this context's scratch for kHubMaxFrames frames (allocated with the first use)
+    std::shared_ptr<const barkhip::HubertModel> hub;
+    struct HubScratch {
+        bool ready = false;
+        float * pcm = nullptr; barkhip::half_t * pcm_h = nullptr;            // [n_max]
+        barkhip::half_t * a16 = nullptr, * b16 = nullptr;                   // conv stack ping-pong: [T0_max][C], [T1_max][C]
+        double * part = nullptr; float * stats = nullptr;                   // convolution 0: partial sums, statistics
+        float * feat = nullptr;                                              // [T][C] end of the conv stack
+        float * x = nullptr, * tmp = nullptr, * q = nullptr, * kc = nullptr, * vc = nullptr;     // [T][H] rows, K / V of one layer
+        barkhip::half_t * xh = nullptr, * att = nullptr, * hb = nullptr;   // [T][max(C, H)], [T][H], [T][F]
+        float * gi = nullptr, * c1 = nullptr, * c2 = nullptr, * out2 = nullptr; barkhip::half_t * h1 = nullptr, * h2 = nullptr;    // token head
+        float * logits = nullptr; int32_t * ids = nullptr;                  // [T][n_classes], [T]
+        int * rows = nullptr;                                                // [8][80] row tables of the conv stages (CodecBatch)
+        float * tap = nullptr; size_t tap_elems = 0;                        // parity tap 0 in f32 (grown on demand)
+    } hubs;
+    hipEvent_t hub_ev[2] = {nullptr, nullptr}; double hub_device_us = -1.0;
     struct CodecGraph { hipGraphExec_t exec = nullptr; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -227,6 +271,13 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * ctx, con
 // 6 the latent [H][T]).  Throws without an encoder in the file, on an empty / too long (> 4096 frames) / non-finite recording, on n_q outside the file's codebooks.
 std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * ctx, const std::vector<const float *> & pcm, const std::vector<int> & n_samples, int n_q,
                                                            int tap_stage, std::vector<float> * tap);
+// Semantic encoder (C12h).  engine_load_semantic_encoder: parse, check and upload the file (throws on a malformed / quantised / mis-shaped one); the context
+// and every clone made afterwards share it.  engine_semantic_encode: n samples of 16 kHz mono -> T = (n - 400) / 320 + 1 ids; tap_stage >= 0: *tap receives that
+// stage's rows (0 conv 0 [T0][C], 1 conv stack [T][C], 2 projection [T][H], 3 hidden_states[0], 4 hidden_states[L], 5 logits [T][n_classes]).  engine_semantic_head:
+// the token head alone on caller rows [T][H]
+void engine_load_semantic_encoder(bark_context * ctx, const char * path);
+std::vector<int32_t> engine_semantic_encode(bark_context * ctx, const float * pcm16k, int n, int tap_stage, std::vector<float> * tap);
+std::vector<int32_t> engine_semantic_head(bark_context * ctx, const float * feats_TxH, int T, std::vector<float> * logits);
 // kernel-level hook: latents [T][H] -> codes [n_q][T] by the RVQ kernel alone (C11q)
 std::vector<int32_t> engine_rvq_encode(bark_context * ctx, const float * latents, int T, int n_q);
 bool engine_generate(bark_context * ctx, const char * text);

@@ -35,31 +35,34 @@ void ensure_codec_scratch(bark_context * c, size_t need, int Ts, int D) {
 // instead of 2 T, for all utterances at once.  64 of them are captured once as a hipGraph whose nodes take their launch index from a device counter,
 // so one graph serves every T (and is re-captured only when the batch size or a buffer changes).  `slot`: the capture of THESE weights and THIS row
 // table (decoder and encoder each own one).
-void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context::LstmGraph & slot, const CodecBatch & cb, int Ts, int Tmax, float * out2) {
+// `io`: the rows and state buffers (the codec's own by default); the semantic encoder's token head brings its own, and an input width K_in != D
+struct LstmIo { const half_t * x_h; int K_in, D; float * gi, * c1, * c2; half_t * h1, * h2; };
+LstmIo codec_lstm_io(bark_context * c) { return LstmIo{c->c_xt_h, c->codec.D, c->codec.D, c->c_gi, c->c_cell, c->c_cell2, c->c_hseq_h, c->c_hseq2_h}; }
+void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context::LstmGraph & slot, const CodecBatch & cb, int Ts, int Tmax, float * out2, const LstmIo & io) {
     hipStream_t s = c->stream;
-    const int D = c->codec.D, B = cb.B;
+    const int D = io.D, B = cb.B;
     {
         LinArgs g;
-        g.W = lstm[0].w_ih; g.M = 4 * D; g.K = D; g.N = Ts; g.x_f16 = c->c_xt_h; g.epi = EPI_LOGITS; g.out = c->c_gi; g.ld_out = 4 * D;
+        g.W = lstm[0].w_ih; g.M = 4 * D; g.K = io.K_in; g.N = Ts; g.x_f16 = io.x_h; g.epi = EPI_LOGITS; g.out = io.gi; g.ld_out = 4 * D;
         launch_linear(s, g);
     }
     LstmPairArgs a;
-    a.gi1 = c->c_gi; a.w_hh1 = lstm[0].w_hh; a.b_ih1 = lstm[0].b_ih; a.b_hh1 = lstm[0].b_hh; a.c1 = c->c_cell; a.h1 = c->c_hseq_h;
-    a.w_ih2 = lstm[1].w_ih; a.w_hh2 = lstm[1].w_hh; a.b_ih2 = lstm[1].b_ih; a.b_hh2 = lstm[1].b_hh; a.c2 = c->c_cell2; a.h2 = c->c_hseq2_h;
+    a.gi1 = io.gi; a.w_hh1 = lstm[0].w_hh; a.b_ih1 = lstm[0].b_ih; a.b_hh1 = lstm[0].b_hh; a.c1 = io.c1; a.h1 = io.h1;
+    a.w_ih2 = lstm[1].w_ih; a.w_hh2 = lstm[1].w_hh; a.b_ih2 = lstm[1].b_ih; a.b_hh2 = lstm[1].b_hh; a.c2 = io.c2; a.h2 = io.h2;
     a.out2 = out2; a.T = Tmax; a.D = D; a.cb = cb;
     if (!c->use_graph) {
         for (int i = 0; i <= Tmax; i++) { a.t = i; launch_lstm_pair_step(s, a); }
         return;
     }
     constexpr int kBlock = 64;
-    if (slot.exec && (slot.out != out2 || slot.gi != c->c_gi || slot.B != B)) { (void) hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
+    if (slot.exec && (slot.out != out2 || slot.gi != io.gi || slot.B != B)) { (void) hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
     if (!slot.exec) {
         slot.exec = capture_graph(s, [&] {
             a.t_base = c->d_lstm_t;
             for (int i = 0; i < kBlock; i++) { a.t = i; launch_lstm_pair_step(s, a); }
             launch_add_int(s, c->d_lstm_t, kBlock);
         });
-        slot.out = out2; slot.gi = c->c_gi; slot.B = B;
+        slot.out = out2; slot.gi = io.gi; slot.B = B;
     }
     const int hdr[2] = {0, Tmax};
     HIP_OK(hipMemcpyAsync(c->d_lstm_t, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
@@ -136,7 +139,7 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
     launch_rvq_gather(s, cm.codebooks, cm.hp.n_bins, cm.hp.hidden_dim, c->d_codes, n_q, Tmax, Ts, A, cb);
     launch_act_round(s, A, (size_t) cm.hp.hidden_dim * Ts, 0, H0);
     conv(cm.init, H0, 1, nullptr, Bf, c->c_xt_h, nullptr);      // Bf = x [row][D]; its f16 image is the LSTM's input
-    run_lstm_pair(c, cm.lstm, c->lstm_graph, cb, Ts, Tmax, R);
+    run_lstm_pair(c, cm.lstm, c->lstm_graph, cb, Ts, Tmax, R, codec_lstm_io(c));
     // parity taps are handed out channel-major [C][T'] (one utterance)
     auto grab = [&](int stage, const float * buf, int C, size_t rows) {
         if (tap_stage != stage || !tap) return;
@@ -286,7 +289,7 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
         launch_conv_down(s, d);
         grab(1 + b, b < 3 ? A : Bf, ch[b + 1], (size_t) rows[b + 1]);
     }
-    run_lstm_pair(c, en.lstm, c->lstm_graph_enc, cb[4], Ts, Tmax, R);
+    run_lstm_pair(c, en.lstm, c->lstm_graph_enc, cb[4], Ts, Tmax, R, codec_lstm_io(c));
     launch_add(s, R, Bf, (size_t) D * Ts, A);                               // y + x
     grab(5, A, D, (size_t) Ts);
     launch_act_round(s, A, (size_t) D * Ts, 1, H0);
@@ -327,6 +330,182 @@ std::vector<int32_t> engine_rvq_encode(bark_context * c, const float * latents, 
     HIP_OK(hipStreamSynchronize(s));                            // also: hdr is a stack object
     throw_on_missing_pick(codes);
     return codes;
+}
+
+}  // namespace barkhip
+
+// ---- semantic encoder (rule C12h): 16 kHz PCM -> HuBERT hidden state -> token head -> ids ------------------------------------
+namespace {
+// the seven valid convolutions: kernels 10, 3, 3, 3, 3, 2, 2 with strides 5, 2, 2, 2, 2, 2, 2 - rows[0] samples, rows[i + 1] the rows behind convolution i
+void hub_stage_rows(const HubertModel & hm, int n, int rows[8]) {
+    rows[0] = n;
+    rows[1] = (n - hm.k0) / 5 + 1;
+    for (int i = 0; i < 6; i++) rows[i + 2] = (rows[i + 1] - hm.conv[i].k) / hm.conv[i].stride + 1;
+}
+constexpr int kHubMaxSamples = (kHubMaxFrames - 1) * 320 + 400 + 319;      // the longest input with T <= 1024: 328 079
+
+void ensure_hub_scratch(bark_context * c) {
+    bark_context::HubScratch & h = c->hubs;
+    if (h.ready) return;
+    const HubertModel & hm = *c->hub;
+    const HubertHparams & hp = hm.hp;
+    int rows[8];
+    hub_stage_rows(hm, kHubMaxSamples, rows);
+    const size_t T = kHubMaxFrames, C = hp.C, H = hp.H, F = hp.F, D = hp.D;
+    h.pcm = dev_alloc<float>(c, kHubMaxSamples); h.pcm_h = dev_alloc<half_t>(c, kHubMaxSamples);
+    h.a16 = dev_alloc<half_t>(c, (size_t) rows[1] * C); h.b16 = dev_alloc<half_t>(c, (size_t) rows[2] * C);
+    h.part = dev_alloc<double>(c, (size_t) hub_conv0_chunks(rows[1]) * C * 2); h.stats = dev_alloc<float>(c, 2 * C);
+    h.feat = dev_alloc<float>(c, T * C);
+    h.x = dev_alloc<float>(c, T * H); h.tmp = dev_alloc<float>(c, T * H); h.q = dev_alloc<float>(c, T * H);
+    h.kc = dev_alloc<float>(c, T * H); h.vc = dev_alloc<float>(c, T * H);
+    h.xh = dev_alloc<half_t>(c, T * std::max(C, H)); h.att = dev_alloc<half_t>(c, T * H); h.hb = dev_alloc<half_t>(c, T * F);
+    h.gi = dev_alloc<float>(c, T * 4 * D); h.c1 = dev_alloc<float>(c, D); h.c2 = dev_alloc<float>(c, D); h.out2 = dev_alloc<float>(c, T * D);
+    h.h1 = dev_alloc<half_t>(c, T * D); h.h2 = dev_alloc<half_t>(c, T * D);
+    h.logits = dev_alloc<float>(c, T * hp.n_classes); h.ids = dev_alloc<int32_t>(c, T);
+    h.rows = dev_alloc<int>(c, 8 * 80);
+    h.ready = true;
+}
+
+// token head on the f16 rows h.xh [T][H]: two LSTM layers (the codec's wave front), linear layer, per-row pick -> h.logits, h.ids
+void run_token_head(bark_context * c, int T) {
+    const HubertModel & hm = *c->hub;
+    bark_context::HubScratch & h = c->hubs;
+    hipStream_t s = c->stream;
+    const int D = hm.hp.D, NC = hm.hp.n_classes;
+    CodecBatch one;                                              // one recording: the launch's own T
+    run_lstm_pair(c, hm.lstm, c->lstm_graph_hub, one, T, T, h.out2, LstmIo{h.xh, hm.hp.H, D, h.gi, h.c1, h.c2, h.h1, h.h2});
+    LinArgs o;
+    o.W = hm.out_w; o.M = NC; o.K = D; o.N = T; o.x_f16 = h.h2; o.bias = hm.out_b; o.epi = EPI_LOGITS; o.out = h.logits; o.ld_out = NC;
+    launch_linear(s, o);
+    launch_argmax_rows(s, h.logits, NC, T, NC, h.ids, 1, nullptr);
+}
+}  // namespace
+
+namespace barkhip {
+
+std::vector<int32_t> engine_semantic_head(bark_context * c, const float * feats, int T, std::vector<float> * logits) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!c->hub) throw std::runtime_error("semantic encoder: none loaded");
+    if (!feats || T < 1 || T > kHubMaxFrames) throw std::runtime_error("semantic encoder: the head takes 1 .. 1024 frames");
+    const HubertHparams & hp = c->hub->hp;
+    for (size_t i = 0; i < (size_t) T * hp.H; i++) if (!std::isfinite((float) (_Float16) feats[i])) throw std::runtime_error("semantic encoder: non-finite feature (or one beyond the f16 range)");
+    ensure_hub_scratch(c);
+    bark_context::HubScratch & h = c->hubs;
+    hipStream_t s = c->stream;
+    HIP_OK(hipMemcpyAsync(h.x, feats, (size_t) T * hp.H * 4, hipMemcpyHostToDevice, s));
+    launch_act_round(s, h.x, (size_t) T * hp.H, 0, h.xh);
+    run_token_head(c, T);
+    std::vector<int32_t> ids((size_t) T);
+    if (logits) { logits->resize((size_t) T * hp.n_classes); HIP_OK(hipMemcpyAsync(logits->data(), h.logits, logits->size() * 4, hipMemcpyDeviceToHost, s)); }
+    HIP_OK(hipMemcpyAsync(ids.data(), h.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return ids;
+}
+
+std::vector<int32_t> engine_semantic_encode(bark_context * c, const float * pcm, int n, int tap_stage, std::vector<float> * tap) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!c->hub) throw std::runtime_error("semantic encoder: none loaded");
+    const HubertModel & hm = *c->hub;
+    const HubertHparams & hp = hm.hp;
+    if (tap_stage > 5) throw std::runtime_error("semantic encoder: tap stages are 0..5");
+    if (!pcm || n < 400) throw std::runtime_error("semantic encoder: a recording needs at least 400 samples (one frame)");
+    if (n > kHubMaxSamples) throw std::runtime_error("semantic encoder: more than 1024 frames (328 079 samples) are refused");
+    for (int i = 0; i < n; i++) if (!std::isfinite(pcm[i]) || !std::isfinite((float) (_Float16) pcm[i])) throw std::runtime_error("semantic encoder: non-finite sample (or one beyond the f16 range)");
+    int rows[8];
+    hub_stage_rows(hm, n, rows);
+    const int T = rows[7], T0 = rows[1], C = hp.C, H = hp.H, F = hp.F;
+    if (T != (n - 400) / 320 + 1 || T < 1 || T > kHubMaxFrames) throw std::runtime_error("semantic encoder: frame count outside 1 .. 1024");
+    ensure_hub_scratch(c);
+    bark_context::HubScratch & h = c->hubs;
+    hipStream_t s = c->stream;
+    const bool taps = tap_stage >= 0;
+    if (tap_stage == 0 && (size_t) T0 * C > h.tap_elems) { h.tap = dev_alloc<float>(c, (size_t) T0 * C); h.tap_elems = (size_t) T0 * C; }
+    {
+        int hdr[8][80] = {};
+        for (int st = 0; st < 8; st++) { hdr[st][0] = rows[st]; hdr[st][41] = rows[st]; }
+        HIP_OK(hipMemcpyAsync(h.rows, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(h.pcm, pcm, (size_t) n * 4, hipMemcpyHostToDevice, s));
+        HIP_OK(hipStreamSynchronize(s));                        // hdr is a stack object
+    }
+    auto stage_cb = [&](int st) { CodecBatch cb; cb.T = h.rows + 80 * st; cb.Tpre = h.rows + 80 * st + 40; cb.B = 1; return cb; };
+    auto grab = [&](int stage, const float * buf, size_t elems) {
+        if (tap_stage != stage || !tap) return;
+        tap->resize(elems);
+        HIP_OK(hipMemcpyAsync(tap->data(), buf, elems * 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+    };
+    for (auto & e : c->hub_ev) if (!e) HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventRecord(c->hub_ev[0], s));
+    // feature encoder: the f16 image of the samples, convolution 0 + norm + GELU, six valid convolutions on the matrix cores (a16 <-> b16)
+    launch_act_round(s, h.pcm, (size_t) n, 0, h.pcm_h);
+    {
+        HubConv0Args a;
+        a.xh = h.pcm_h; a.n = n; a.T0 = T0; a.w = hm.conv0_w; a.C = C; a.K = hm.k0; a.stride = 5;
+        a.part = h.part; a.stats = h.stats; a.g = hm.gn_g; a.b = hm.gn_b; a.yh = h.a16; a.y = tap_stage == 0 ? h.tap : nullptr;
+        launch_hub_conv0(s, a);
+    }
+    grab(0, h.tap, (size_t) T0 * C);
+    half_t * src = h.a16, * dst = h.b16;
+    for (int i = 0; i < 6; i++) {
+        const HubertModel::Conv & cv = hm.conv[i];
+        ConvDownArgs d;
+        d.W = cv.wm; d.w32 = cv.w32; d.bias = nullptr; d.cin = C; d.cout = C; d.cout32 = (C + 31) & ~31;
+        d.K = cv.k; d.stride = cv.stride; d.kd = cv.k * C; d.kd16 = (d.kd + 15) & ~15; d.valid = 1;
+        d.xh = src; d.rows_out = rows[i + 2]; d.cb_in = stage_cb(i + 1); d.cb_out = stage_cb(i + 2);
+        if (i < 5) d.yh_gelu = dst; else d.y_gelu = h.feat;     // the last one feeds a LayerNorm: f32
+        launch_conv_down(s, d);
+        std::swap(src, dst);
+    }
+    grab(1, h.feat, (size_t) T * C);
+    // projection: LayerNorm(C) -> f16 rows -> Linear(C -> H)
+    launch_add_ln_rows(s, h.feat, nullptr, T, C, hm.fp_ln_g, hm.fp_ln_b, nullptr, h.xh);
+    {
+        LinArgs p;
+        p.W = hm.fp_w; p.M = H; p.K = C; p.N = T; p.x_f16 = h.xh; p.bias = hm.fp_b; p.epi = EPI_LOGITS; p.out = h.x; p.ld_out = H;
+        launch_linear(s, p);
+    }
+    grab(2, h.x, (size_t) T * H);
+    // positional convolution on the f16 image of the projection, GELU, + projection, encoder.layer_norm -> hidden_states[0]
+    launch_act_round(s, h.x, (size_t) T * H, 0, h.xh);
+    {
+        PosConvArgs p;
+        p.W = hm.pos_w; p.bias = hm.pos_b; p.xh = h.xh; p.T = T; p.H = H; p.G = hp.pos_groups; p.Kp = hp.pos_kernel;
+        p.kd = hm.pos_kd; p.kd16 = hm.pos_kd16; p.co32 = hm.pos_co32; p.y = h.tmp;
+        launch_pos_conv(s, p);
+    }
+    launch_add_ln_rows(s, h.x, h.tmp, T, H, hm.enc_ln_g, hm.enc_ln_b, h.x, h.xh);
+    grab(3, h.x, (size_t) T * H);
+    // layers 1 .. L (post-norm): attention over all T frames, residual, LayerNorm; FFN with erf GELU, residual, LayerNorm
+    for (const HubertModel::Layer & ly : hm.layers) {
+        LinArgs qkv;
+        qkv.W = ly.qkv_w; qkv.M = 3 * H; qkv.K = H; qkv.N = T; qkv.x_f16 = h.xh; qkv.bias = ly.qkv_b; qkv.epi = EPI_QKV;
+        qkv.q = h.q; qkv.kc = h.kc; qkv.vc = h.vc; qkv.E = H; qkv.P = kHubMaxFrames; qkv.pos0 = 0;
+        launch_linear(s, qkv);
+        AttnPrefillArgs at;
+        at.q = h.q; at.ldq = H; at.kc = h.kc; at.vc = h.vc; at.H = hp.n_head; at.P = kHubMaxFrames; at.N = T; at.n_past = 0; at.causal = 0;
+        at.att = h.att; at.ld_att = H;
+        launch_attn_prefill(s, at);
+        LinArgs o;
+        o.W = ly.o_w; o.M = H; o.K = H; o.N = T; o.x_f16 = h.att; o.bias = ly.o_b; o.epi = EPI_LOGITS; o.out = h.tmp; o.ld_out = H;
+        launch_linear(s, o);
+        launch_add_ln_rows(s, h.x, h.tmp, T, H, ly.ln1_g, ly.ln1_b, h.x, h.xh);
+        LinArgs f1;
+        f1.W = ly.fc1_w; f1.M = F; f1.K = H; f1.N = T; f1.x_f16 = h.xh; f1.bias = ly.fc1_b; f1.epi = EPI_GELU; f1.out_h = h.hb; f1.lut = hm.gelu_erf_lut;
+        launch_linear(s, f1);
+        LinArgs f2;
+        f2.W = ly.fc2_w; f2.M = H; f2.K = F; f2.N = T; f2.x_f16 = h.hb; f2.bias = ly.fc2_b; f2.epi = EPI_LOGITS; f2.out = h.tmp; f2.ld_out = H;
+        launch_linear(s, f2);
+        launch_add_ln_rows(s, h.x, h.tmp, T, H, ly.ln2_g, ly.ln2_b, h.x, h.xh);
+    }
+    grab(4, h.x, (size_t) T * H);
+    run_token_head(c, T);
+    HIP_OK(hipEventRecord(c->hub_ev[1], s));
+    grab(5, h.logits, (size_t) T * hp.n_classes);
+    std::vector<int32_t> ids((size_t) T);
+    HIP_OK(hipMemcpyAsync(ids.data(), h.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (!taps) { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->hub_ev[0], c->hub_ev[1])); c->hub_device_us = 1e3 * ms; }
+    return ids;
 }
 
 }  // namespace barkhip

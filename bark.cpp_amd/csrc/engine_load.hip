@@ -87,7 +87,9 @@ bark_context::~bark_context() {
     for (auto & g : batch_graphs) if (g.second) (void) hipGraphExecDestroy(g.second);
     if (lstm_graph.exec) (void) hipGraphExecDestroy(lstm_graph.exec);
     if (lstm_graph_enc.exec) (void) hipGraphExecDestroy(lstm_graph_enc.exec);
+    if (lstm_graph_hub.exec) (void) hipGraphExecDestroy(lstm_graph_hub.exec);
     for (auto & e : enc_ev) if (e) (void) hipEventDestroy(e);
+    for (auto & e : hub_ev) if (e) (void) hipEventDestroy(e);
     if (codec_graph.exec) (void) hipGraphExecDestroy(codec_graph.exec);
     for (auto & g : fine_graphs) if (g) (void) hipGraphExecDestroy(g);
     for (void * p : allocs) (void) hipFree(p);
@@ -593,12 +595,128 @@ bark_context * engine_load(const char * path, const bark_context_params & params
     return ctx.release();
 }
 
+// ---- semantic encoder file (C12h) ------------------------------------------------------------------------------------------------------
+HubertModel::~HubertModel() {
+    (void) hipSetDevice(device);
+    for (void * p : bufs) (void) hipFree(p);
+}
+
+static float gelu_erf_host(float x) { return (float) (0.5 * (double) x * (1.0 + erf((double) x * 0.70710678118654752440))); }
+
+void engine_load_semantic_encoder(bark_context * ctx, const char * path) {
+    HIP_OK(hipSetDevice(ctx->device));
+    HubertFile hf;
+    std::string err;
+    if (!hf.open(path, err)) throw std::runtime_error("semantic encoder: " + err);
+    const HubertHparams & hp = hf.hp;
+    if (hp.ftype != 1) throw std::runtime_error("semantic encoder: ftype " + std::to_string(hp.ftype) + " is not supported (f16 files only; quantised encoder files are refused)");
+    if (hp.C < 8 || hp.C > 4096 || hp.H < 128 || hp.H > 4096 || hp.F < 128 || hp.F > 4096 || hp.n_head < 1 || hp.n_layer_stored < 1 || hp.n_layer_stored > 64 ||
+        hp.output_layer < 1 || hp.output_layer > hp.n_layer_stored || hp.pos_kernel < 1 || hp.pos_kernel > 1024 || hp.pos_groups < 1 || hp.n_classes < 4 || hp.n_classes > (1 << 20))
+        throw std::runtime_error("semantic encoder: implausible hparams");
+    if (hp.H % 128 || hp.C % 128 || hp.F % 128) throw std::runtime_error("semantic encoder: C, H and F must be multiples of 128 (got " + std::to_string(hp.C) + ", " + std::to_string(hp.H) + ", " + std::to_string(hp.F) + ")");
+    if (hp.H != 64 * hp.n_head) throw std::runtime_error("semantic encoder: heads must be 64 wide");
+    if (hp.H % hp.pos_groups || (hp.H / hp.pos_groups) % 8) throw std::runtime_error("semantic encoder: the positional convolution's groups must hold a multiple of 8 channels");
+    if (hp.D != 128 && hp.D != 256 && hp.D != 512 && hp.D != 1024) throw std::runtime_error("semantic encoder: the head's LSTM width must be 128, 256, 512 or 1024");
+    if (hp.n_classes % 4) throw std::runtime_error("semantic encoder: n_classes must be a multiple of 4");
+    for (auto & kv : hf.tensors) {
+        if (quant_format_by_type(kv.second.ttype)) throw std::runtime_error("semantic encoder: tensor '" + kv.first + "' is block-quantised; quantised encoder files are refused");
+        const int rank = kv.second.n_dims;
+        if ((rank >= 2) != (kv.second.ttype == 1)) throw std::runtime_error("semantic encoder: tensor '" + kv.first + "' must be " + (rank >= 2 ? "f16" : "f32"));
+    }
+    std::shared_ptr<HubertModel> hm(new HubertModel());
+    hm->hp = hp; hm->device = ctx->device;
+    auto up = [&](const void * src, size_t bytes) -> const void * {
+        void * d = nullptr;
+        HIP_OK(hipMalloc(&d, std::max<size_t>(bytes, 4)));
+        hm->bufs.push_back(d);
+        HIP_OK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+        return d;
+    };
+    auto vec = [&](const std::string & name, int64_t n) { return (const float *) up(need(hf.tensors, name, 0, n, 0).data, (size_t) n * 4); };
+    auto mat = [&](const std::string & name, int64_t in, int64_t out) { const TensorRef & t = need(hf.tensors, name, 1, in, out); return (const half_t *) up(t.data, t.nbytes()); };
+    auto conv3 = [&](const std::string & name, int64_t cin, int64_t cout) -> const TensorRef & {
+        const TensorRef & t = need(hf.tensors, name, 1, 0, 0);
+        if (t.n_dims != 3 || t.ne[1] != cin || t.ne[2] != cout || t.ne[0] < 1 || t.ne[0] > 1024) throw std::runtime_error("semantic encoder: tensor '" + name + "' has an unexpected shape");
+        return t;
+    };
+    const int C = hp.C, H = hp.H, F = hp.F, D = hp.D;
+    static const int kKernel[7] = {10, 3, 3, 3, 3, 2, 2}, kStride[7] = {5, 2, 2, 2, 2, 2, 2};      // C12h: 400 samples per frame, a hop of 320
+    {
+        const TensorRef & t = conv3("conv0.weight", 1, C);
+        if (t.ne[0] != kKernel[0]) throw std::runtime_error("semantic encoder: convolution 0 must have 10 taps");
+        hm->k0 = (int) t.ne[0];
+        hm->conv0_w = (const half_t *) up(t.data, t.nbytes());
+        hm->gn_g = vec("conv0.norm.weight", C); hm->gn_b = vec("conv0.norm.bias", C);
+    }
+    for (int i = 1; i < 7; i++) {
+        const TensorRef & t = conv3("conv" + std::to_string(i) + ".weight", C, C);
+        if (t.ne[0] != kKernel[i]) throw std::runtime_error("semantic encoder: convolution " + std::to_string(i) + " has the wrong number of taps");
+        HubertModel::Conv & cv = hm->conv[i - 1];
+        cv.k = kKernel[i]; cv.stride = kStride[i];
+        const int kd = cv.k * C, kd16 = (kd + 15) & ~15, c32 = (C + 31) & ~31;
+        std::vector<uint16_t> img((size_t) c32 * kd16, 0);
+        std::vector<float> f((size_t) t.nelements());
+        for (size_t j = 0; j < f.size(); j++) { uint16_t h; memcpy(&h, t.data + 2 * j, 2); f[j] = (float) __builtin_bit_cast(_Float16, h); }
+        for (int co = 0; co < C; co++) for (int ci = 0; ci < C; ci++) for (int k = 0; k < cv.k; k++)
+            memcpy(&img[(size_t) co * kd16 + (size_t) k * C + ci], t.data + 2 * (((size_t) co * C + ci) * cv.k + k), 2);
+        cv.wm = (const half_t *) up(img.data(), img.size() * 2);
+        cv.w32 = (const float *) up(f.data(), f.size() * 4);
+    }
+    hm->fp_ln_g = vec("proj.ln.weight", C); hm->fp_ln_b = vec("proj.ln.bias", C);
+    hm->fp_w = mat("proj.weight", C, H); hm->fp_b = vec("proj.bias", H);
+    {
+        const int G = hp.pos_groups, Hg = H / G, Kp = hp.pos_kernel;
+        const TensorRef & t = conv3("pos.weight", Hg, H);
+        if (t.ne[0] != Kp) throw std::runtime_error("semantic encoder: the positional convolution's kernel differs from the hparams");
+        hm->pos_kd = Kp * Hg; hm->pos_kd16 = (hm->pos_kd + 15) & ~15; hm->pos_co32 = (Hg + 31) & ~31;
+        std::vector<uint16_t> img((size_t) G * hm->pos_co32 * hm->pos_kd16, 0);
+        for (int g = 0; g < G; g++) for (int co = 0; co < Hg; co++) for (int ci = 0; ci < Hg; ci++) for (int k = 0; k < Kp; k++)
+            memcpy(&img[((size_t) g * hm->pos_co32 + co) * hm->pos_kd16 + (size_t) k * Hg + ci], t.data + 2 * ((((size_t) g * Hg + co) * Hg + ci) * Kp + k), 2);
+        hm->pos_w = (const half_t *) up(img.data(), img.size() * 2);
+        hm->pos_b = vec("pos.bias", H);
+    }
+    hm->enc_ln_g = vec("enc.ln.weight", H); hm->enc_ln_b = vec("enc.ln.bias", H);
+    hm->layers.resize((size_t) hp.output_layer);                 // layers behind output_layer are never run: not uploaded
+    for (int l = 0; l < hp.output_layer; l++) {
+        const std::string p = "layers." + std::to_string(l) + ".";
+        HubertModel::Layer & ly = hm->layers[(size_t) l];
+        ly.qkv_w = mat(p + "attn.qkv.weight", H, 3 * H); ly.qkv_b = vec(p + "attn.qkv.bias", 3 * H);
+        ly.o_w = mat(p + "attn.out.weight", H, H); ly.o_b = vec(p + "attn.out.bias", H);
+        ly.ln1_g = vec(p + "ln1.weight", H); ly.ln1_b = vec(p + "ln1.bias", H);
+        ly.fc1_w = mat(p + "fc1.weight", H, F); ly.fc1_b = vec(p + "fc1.bias", F);
+        ly.fc2_w = mat(p + "fc2.weight", F, H); ly.fc2_b = vec(p + "fc2.bias", H);
+        ly.ln2_g = vec(p + "ln2.weight", H); ly.ln2_b = vec(p + "ln2.bias", H);
+    }
+    for (int l = 0; l < 2; l++) {
+        const std::string sfx = std::to_string(l);
+        hm->lstm[l].w_ih = mat("head.lstm.weight_ih_l" + sfx, l ? D : H, 4 * D);
+        hm->lstm[l].w_hh = mat("head.lstm.weight_hh_l" + sfx, D, 4 * D);
+        hm->lstm[l].b_ih = vec("head.lstm.bias_ih_l" + sfx, 4 * D);
+        hm->lstm[l].b_hh = vec("head.lstm.bias_hh_l" + sfx, 4 * D);
+    }
+    hm->out_w = mat("head.out.weight", D, hp.n_classes); hm->out_b = vec("head.out.bias", hp.n_classes);
+    {
+        std::vector<uint16_t> lut(65536);
+        for (uint32_t i = 0; i < 65536; i++) {
+            const _Float16 h = __builtin_bit_cast(_Float16, (uint16_t) i);
+            lut[i] = __builtin_bit_cast(uint16_t, (_Float16) gelu_erf_host((float) h));
+        }
+        hm->gelu_erf_lut = (const uint16_t *) up(lut.data(), lut.size() * 2);
+    }
+    HIP_OK(hipDeviceSynchronize());
+    if (ctx->lstm_graph_hub.exec) { (void) hipGraphExecDestroy(ctx->lstm_graph_hub.exec); ctx->lstm_graph_hub.exec = nullptr; }
+    ctx->hubs = bark_context::HubScratch();                       // a second load: scratch of the new dimensions (the old buffers stay with the context until it is freed)
+    ctx->hub = hm;
+    if (ctx->description.find(", semantic encoder") == std::string::npos) ctx->description += ", semantic encoder";
+}
+
 bark_context * engine_clone(bark_context * src, uint32_t seed) {
     HIP_OK(hipSetDevice(src->device));
     std::unique_ptr<bark_context> ctx(new bark_context());
     ctx->params = src->params;
     ctx->filter = src->filter;
     ctx->voice = src->voice;
+    ctx->hub = src->hub;
     ctx->rng = std::mt19937(seed);
     ctx->vocab = src->vocab;
     for (int g = 0; g < 3; g++) {

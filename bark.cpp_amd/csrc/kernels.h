@@ -304,11 +304,38 @@ struct ConvDownArgs {
     float * y = nullptr; half_t * yh_raw = nullptr, * yh_elu = nullptr;
     int rows_out = 0;
     CodecBatch cb_in, cb_out;
+    // valid mode (the semantic encoder's feature convolutions, C12h): no padding - output row t reads input rows t stride .. t stride + K - 1, all inside
+    // the recording (rows_out = (rows_in - K) / stride + 1); bias may be null; y_gelu / yh_gelu: erf GELU of the result in f32 / as f16 image
+    int valid = 0;
+    float * y_gelu = nullptr; half_t * yh_gelu = nullptr;
 };
 void launch_conv_down(hipStream_t s, const ConvDownArgs & a);
 // Greedy residual vector quantisation (EncodecResidualVectorQuantizer.encode), order C11q: per frame and stage q, d_j = sum_d (r_d - e_jd)^2 with
 // t = r_d - e_jd; p = t * t; acc = acc + p for d ascending (every operation rounded to f32), j* = argmin_j d_j (ties: the lowest j), r <- r - e_{q,j*}.
 // z [rows_total][Hd] f32 latents, the recordings back to back (cb); codes of recording b: [n_q][T[b]] at n_q Tpre[b]
 void launch_rvq_encode(hipStream_t s, const float * codebooks, int n_bins, int Hd, const float * z, int n_q, int rows_total, int32_t * codes, const CodecBatch & cb);
+
+// ---- semantic encoder (HuBERT and its token head, rule C12h; codec_kernels.hip, misc_kernels.hip) ---------------------------
+// Convolution 0 of the feature encoder with its per-channel norm over time and erf GELU: xh [n] the f16 image of the samples, w [C][K] f16, T0 output
+// rows.  Three launches: partial sums per chunk of rows (part [chunks][C][2] doubles), statistics (stats [C][2] = mean, 1 / sqrt(var + eps)), and the
+// f16 image yh [T0][C] of GELU(norm(conv)) (y: the same values in f32, optional)
+struct HubConv0Args {
+    const half_t * xh = nullptr; int n = 0, T0 = 0;
+    const half_t * w = nullptr; int C = 0, K = 0, stride = 1;
+    double * part = nullptr; float * stats = nullptr;
+    const float * g = nullptr, * b = nullptr;
+    half_t * yh = nullptr; float * y = nullptr;
+};
+void launch_hub_conv0(hipStream_t s, const HubConv0Args & a);
+int hub_conv0_chunks(int T0);                             // rows of `part`
+// grouped positional convolution on the f16 matrix cores: W [G][co32][kd16] f16 (kd = k (H / G) + ci, zero padded), xh [T][H] f16 -> y [T][H] = GELU(conv + bias)
+struct PosConvArgs {
+    const half_t * W = nullptr; const float * bias = nullptr; const half_t * xh = nullptr;
+    int T = 0, H = 0, G = 1, Kp = 0, kd = 0, kd16 = 0, co32 = 0;
+    float * y = nullptr;
+};
+void launch_pos_conv(hipStream_t s, const PosConvArgs & a);
+// post-norm layer step: out = LayerNorm(x + y) (y may be null) as f32 rows (out32, may alias x) and as f16 rows (out16); eps 1e-5, double sums as ln_rows_kernel
+void launch_add_ln_rows(hipStream_t s, const float * x, const float * y, int N, int E, const float * g, const float * b, float * out32, half_t * out16);
 
 }  // namespace barkhip

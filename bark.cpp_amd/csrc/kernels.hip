@@ -990,6 +990,7 @@ void launch_linear(hipStream_t s, const LinArgs & a) {
         switch (nblk) {           // n_embd in {128, 256, 512, 768, 1024} and 4x those
             case 1: launch_gemv_n<1>(s, a); break;
             case 2: launch_gemv_n<2>(s, a); break;
+            case 3: launch_gemv_n<3>(s, a); break;        // K = 384: the toy semantic encoder's width
             case 4: launch_gemv_n<4>(s, a); break;
             case 6: launch_gemv_n<6>(s, a); break;
             case 8: launch_gemv_n<8>(s, a); break;

@@ -126,6 +126,34 @@ __global__ __launch_bounds__(256) void ln_rows_f32_kernel(const float * x, int N
 void launch_ln_rows_f32(hipStream_t s, const float * x, int N, int E, const float * g, const float * b, float * out) {
     hipLaunchKernelGGL(ln_rows_f32_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, N, E, g, b, out);
 }
+// post-norm step of the semantic encoder's layers (C12h): v = x + y, LayerNorm(v) with ln_rows_kernel's arithmetic, as f32 and as f16 rows.  out32 may be
+// x itself: a lane reads and writes only its own elements
+__global__ __launch_bounds__(256) void add_ln_rows_kernel(const float * x, const float * y, int N, int E, const float * g, const float * b, float * out32, half_t * out16) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const float * xr = x + (size_t) row * E;
+    const float * yr = y ? y + (size_t) row * E : nullptr;
+    double s1 = 0.0;
+    for (int e = lane; e < E; e += 64) { const float v = yr ? xr[e] + yr[e] : xr[e]; s1 += (double) v; }
+    s1 = wave_sum(s1);
+    const float mean = (float) (s1 / (double) E);
+    double s2 = 0.0;
+    for (int e = lane; e < E; e += 64) { const float v = (yr ? xr[e] + yr[e] : xr[e]) - mean; s2 += (double) (v * v); }
+    s2 = wave_sum(s2);
+    const float var = (float) (s2 / (double) E);
+    const float scale = 1.0f / sqrtf(var + 1e-5f);
+    for (int e = lane; e < E; e += 64) {
+        float v = ((yr ? xr[e] + yr[e] : xr[e]) - mean) * scale;
+        v = v * g[e];
+        v = v + b[e];
+        if (out32) out32[(size_t) row * E + e] = v;
+        if (out16) out16[(size_t) row * E + e] = to_half(v);
+    }
+}
+void launch_add_ln_rows(hipStream_t s, const float * x, const float * y, int N, int E, const float * g, const float * b, float * out32, half_t * out16) {
+    hipLaunchKernelGGL(add_ln_rows_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, y, N, E, g, b, out32, out16);
+}
 // E = 256 NV: the row stays in registers (one 16-byte load per 256 elements and lane), statistics and output from the same copy -
 // one trip to memory instead of three dependent ones.  Same operations per element as ln_rows_kernel; the double sums are formed over a
 // different partition of the row (they are exact or off by 2^-53 relative either way, long before the rounding to float).

@@ -11,6 +11,7 @@ namespace barkhip {
 
 namespace {
 constexpr uint32_t kMagic = 0x67676d6c;   // bark.cpp:1095-1102
+constexpr uint32_t kHubertMagic = 0x68756273;
 
 struct Cursor {
     const uint8_t * base; size_t size; size_t pos = 0; bool ok = true;
@@ -113,6 +114,32 @@ bool ModelFile::open(const char * path, std::string & err) {
         std::string name; TensorRef t;
         if (!read_record(c, name, t, err)) return false;
         codec[name] = t;
+    }
+    return true;
+}
+
+HubertFile::~HubertFile() {
+    if (map) munmap((void *) map, map_size);
+}
+
+bool HubertFile::open(const char * path, std::string & err) {
+    int fd = ::open(path, O_RDONLY);
+    if (fd < 0) { err = std::string("cannot open '") + path + "'"; return false; }
+    struct stat st;
+    if (fstat(fd, &st) != 0 || st.st_size < 48) { close(fd); err = "semantic encoder file is too short"; return false; }
+    void * p = mmap(nullptr, (size_t) st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (p == MAP_FAILED) { err = "mmap failed"; return false; }
+    map = (const uint8_t *) p; map_size = (size_t) st.st_size;
+    Cursor c{map, map_size};
+    if (c.get<uint32_t>() != kHubertMagic) { err = "bad magic (not a semantic encoder file)"; return false; }
+    int32_t * f = &hp.C;
+    for (int i = 0; i < 11; i++) f[i] = c.get<int32_t>();
+    if (!c.ok) { err = "truncated semantic encoder hparams"; return false; }
+    while (c.pos < c.size) {
+        std::string name; TensorRef t;
+        if (!read_record(c, name, t, err)) return false;
+        tensors[name] = t;
     }
     return true;
 }

@@ -62,6 +62,23 @@ struct ModelFile {
     bool open(const char * path, std::string & err);
 };
 
+// The semantic encoder's file (HuBERT + token head, rule C12h of DESIGN.md; written by tools/convert_hubert.py), a file of its own beside the model file:
+//   u32 magic 0x68756273 | 11 x i32 hparams | records until EOF (the record format above; f16 for rank >= 2, f32 otherwise)
+struct HubertHparams {
+    int32_t C = 0, H = 0, n_head = 0, F = 0, n_layer_stored = 0, output_layer = 0, pos_kernel = 0, pos_groups = 0, D = 0, n_classes = 0, ftype = 0;
+};
+struct HubertFile {
+    const uint8_t * map = nullptr;
+    size_t map_size = 0;
+    HubertHparams hp;
+    std::map<std::string, TensorRef> tensors;
+    HubertFile() = default;
+    HubertFile(const HubertFile &) = delete;
+    HubertFile & operator=(const HubertFile &) = delete;
+    ~HubertFile();
+    bool open(const char * path, std::string & err);      // container only; shapes are checked by the engine's loader
+};
+
 // bark_model_quantize (bark.cpp:2300-2377): f16/f32 file -> Q4_0 file (quantize.cpp)
 bool model_quantize(const char * fname_inp, const char * fname_out, int ftype, std::string & err);
 

@@ -69,9 +69,42 @@ def from_generation(ctx) -> VoicePrompt:
     return v
 
 
-def from_audio(ctx, pcm, semantic) -> VoicePrompt:
+def resample_24k_to_16k(pcm) -> np.ndarray:
+    """24 kHz -> 16 kHz (ratio 2 / 3), polyphase, in numpy: output sample m sits at input time t = 1.5 m and is
+        y[m] = sum_j x[j] h(t - j),   h(u) = c sinc(c u) w(u),   c = 0.99 * 2 / 3 (cut-off at 0.99 of the new Nyquist frequency, in cycles per input sample),
+        w(u) = cos^2(pi u / (2 W)) for |u| < W, else 0 (Hann),   W = 6 / c input samples (6 zero crossings of the sinc on either side),
+    over the input samples with |t - j| < W; samples outside the recording are zero.  Even m take the taps of phase 0, odd m those of phase 1/2.  The output
+    has ceil(2 n / 3) samples."""
+    x = np.ascontiguousarray(pcm, dtype=np.float64).reshape(-1)
+    n = len(x)
+    n_out = (2 * n + 2) // 3
+    c = 0.99 * 2.0 / 3.0
+    W = 6.0 / c
+    half = int(np.ceil(W)) + 1
+    out = np.zeros(n_out, np.float64)
+    xp = np.concatenate([np.zeros(half), x, np.zeros(half + 2)])
+    for phase in (0, 1):                                  # t = 1.5 m: integer for even m, integer + 1/2 for odd m
+        m = np.arange(phase, n_out, 2)
+        if not len(m):
+            continue
+        base = (3 * m) // 2                               # floor(t)
+        frac = 0.5 * phase
+        j = np.arange(-half + 1, half + 1)                # taps at floor(t) + j
+        u = frac - j
+        h = c * np.sinc(c * u) * np.where(np.abs(u) < W, np.cos(np.pi * u / (2.0 * W)) ** 2, 0.0)
+        idx = base[:, None] + j[None, :] + half
+        out[m] = xp[idx] @ h
+    return out.astype(np.float32)
+
+
+def from_audio(ctx, pcm, semantic=None) -> VoicePrompt:
     """A voice prompt from a recording of the speaker (24 kHz mono float samples): the coarse and fine streams are the first 2 / 8 codebooks of the
-    EnCodec encoder's codes (ctx.codec_encode; the model file must carry the encoder).  The semantic ids come from the caller: Bark derives them from
-    the audio with a HuBERT model and its quantiser, which this library does not include."""
+    EnCodec encoder's codes (ctx.codec_encode; the model file must carry the encoder).  The semantic ids are the caller's when given; with None the
+    recording is resampled to 16 kHz (resample_24k_to_16k) and run through the context's semantic encoder (ctx.load_semantic_encoder: HuBERT and its token
+    head, rule C12h) - ValueError when none is loaded."""
+    if semantic is None:
+        if not ctx.has_semantic_encoder():
+            raise ValueError("from_audio: no semantic ids given and no semantic encoder loaded (ctx.load_semantic_encoder)")
+        semantic = ctx.semantic_encode(resample_24k_to_16k(pcm))
     codes = ctx.codec_encode(pcm, 8)                  # [8][T]
     return VoicePrompt(semantic, codes[:2].T, codes[:8].T)

@@ -107,6 +107,24 @@ BARK_API double bark_hip_codec_encode_device_us(struct bark_context * bctx);
  * with no finite distance to any codebook row (a NaN or infinite entry). */
 BARK_API int bark_hip_rvq_encode(struct bark_context * bctx, const float * latents_TxH, int T, int n_q, int32_t * codes);
 
+/* Semantic tokens from audio (rule C12h): HuBERT's feature encoder, positional convolution and first `output_layer` layers, then the
+ * token head (two LSTM layers, a linear layer, argmax) - the third stream of a voice prompt.  The weights come from a file of their own, written by
+ * tools/convert_hubert.py.  Load: 0, or -1 with a message (unreadable, truncated, wrong magic, quantised, dimensions the kernels do not take); the context
+ * and the clones made AFTERWARDS share the device copy. */
+BARK_API int bark_hip_load_semantic_encoder(struct bark_context * bctx, const char * path);
+BARK_API int bark_hip_has_semantic_encoder(struct bark_context * bctx);
+/* pcm16k: n_samples floats, 16 kHz mono, not normalised -> ids [T], T = (n_samples - 400) / 320 + 1.  Returns T, or -1: no encoder loaded, n_samples < 400,
+ * T > 1024 (n_samples > 328 079), a sample that is not finite or whose f16 image is not (|x| >= 65520), capacity < T.  The context stays usable. */
+BARK_API int bark_hip_semantic_encode(struct bark_context * bctx, const float * pcm16k, int n_samples, int32_t * ids, int capacity);
+/* Parity tap, time-major rows: stage 0 convolution 0 + norm + GELU [T0][C]; 1 end of the conv stack [T][C]; 2 projection [T][H]; 3 hidden_states[0] [T][H];
+ * 4 hidden_states[output_layer] [T][H]; 5 logits [T][n_classes].  Returns the element count or -1 (as above; stage outside 0..5; capacity in floats too small). */
+BARK_API int bark_hip_semantic_encode_tap(struct bark_context * bctx, const float * pcm16k, int n_samples, int stage, float * out, int capacity);
+/* Kernel-level hook (tests): the token head alone on caller rows feats [T][H], T <= 1024 -> ids [T] and, when logits_or_null is given, logits [T][n_classes].
+ * Returns T or -1. */
+BARK_API int bark_hip_semantic_head(struct bark_context * bctx, const float * feats_TxH, int T, int32_t * ids, float * logits_or_null);
+/* Time on the context's stream between the first and the last kernel of its last bark_hip_semantic_encode call, in microseconds (hipEvents); < 0: no call yet. */
+BARK_API double bark_hip_semantic_encode_device_us(struct bark_context * bctx);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);

@@ -512,8 +512,136 @@ def main_encoder(preset: str):
     print("wrote", dst, os.path.getsize(dst), "bytes")
 
 
+def build_hf_hubert(hp, W):
+    """HuggingFace HubertModel (group norm, post-norm layers, no conv bias) and a torch nn.LSTM + nn.Linear head carrying the tensors of a semantic encoder
+    file (tools/convert_hubert.py; W: name -> f32 torch tensor)."""
+    import torch
+    from transformers import HubertConfig, HubertModel
+    cfg = HubertConfig(hidden_size=hp["H"], num_hidden_layers=hp["n_layer_stored"], num_attention_heads=hp["n_head"], intermediate_size=hp["F"],
+                       conv_dim=(hp["C"],) * 7, conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_bias=False,
+                       num_conv_pos_embeddings=hp["pos_kernel"], num_conv_pos_embedding_groups=hp["pos_groups"], feat_extract_norm="group",
+                       do_stable_layer_norm=False, hidden_act="gelu", hidden_dropout=0.0, activation_dropout=0.0, attention_dropout=0.0,
+                       feat_proj_dropout=0.0, final_dropout=0.0, layerdrop=0.0, mask_time_prob=0.0, feat_proj_layer_norm=True, layer_norm_eps=1e-5,
+                       vocab_size=32, attn_implementation="eager")
+    m = HubertModel(cfg).eval()
+    pc = m.encoder.pos_conv_embed.conv
+    if hasattr(pc, "parametrizations"):
+        torch.nn.utils.parametrize.remove_parametrizations(pc, "weight")
+    else:
+        torch.nn.utils.remove_weight_norm(pc)
+    H = hp["H"]
+    sd = {}
+    for i in range(7):
+        sd[f"feature_extractor.conv_layers.{i}.conv.weight"] = W[f"conv{i}.weight"]
+    sd["feature_extractor.conv_layers.0.layer_norm.weight"] = W["conv0.norm.weight"]
+    sd["feature_extractor.conv_layers.0.layer_norm.bias"] = W["conv0.norm.bias"]
+    sd["feature_projection.layer_norm.weight"] = W["proj.ln.weight"]; sd["feature_projection.layer_norm.bias"] = W["proj.ln.bias"]
+    sd["feature_projection.projection.weight"] = W["proj.weight"]; sd["feature_projection.projection.bias"] = W["proj.bias"]
+    sd["encoder.pos_conv_embed.conv.weight"] = W["pos.weight"]; sd["encoder.pos_conv_embed.conv.bias"] = W["pos.bias"]
+    sd["encoder.layer_norm.weight"] = W["enc.ln.weight"]; sd["encoder.layer_norm.bias"] = W["enc.ln.bias"]
+    for l in range(hp["n_layer_stored"]):
+        p, q = f"encoder.layers.{l}.", f"layers.{l}."
+        for j, n in enumerate("qkv"):
+            sd[p + f"attention.{n}_proj.weight"] = W[q + "attn.qkv.weight"][j * H:(j + 1) * H]
+            sd[p + f"attention.{n}_proj.bias"] = W[q + "attn.qkv.bias"][j * H:(j + 1) * H]
+        sd[p + "attention.out_proj.weight"] = W[q + "attn.out.weight"]; sd[p + "attention.out_proj.bias"] = W[q + "attn.out.bias"]
+        sd[p + "layer_norm.weight"] = W[q + "ln1.weight"]; sd[p + "layer_norm.bias"] = W[q + "ln1.bias"]
+        sd[p + "feed_forward.intermediate_dense.weight"] = W[q + "fc1.weight"]; sd[p + "feed_forward.intermediate_dense.bias"] = W[q + "fc1.bias"]
+        sd[p + "feed_forward.output_dense.weight"] = W[q + "fc2.weight"]; sd[p + "feed_forward.output_dense.bias"] = W[q + "fc2.bias"]
+        sd[p + "final_layer_norm.weight"] = W[q + "ln2.weight"]; sd[p + "final_layer_norm.bias"] = W[q + "ln2.bias"]
+    missing, unexpected = m.load_state_dict(sd, strict=False)
+    assert not unexpected and all(k.startswith("masked_spec_embed") for k in missing), (missing, unexpected)
+    lstm = torch.nn.LSTM(H, hp["D"], 2, batch_first=True).eval()
+    lstm.load_state_dict({f"{n}_l{l}": W[f"head.lstm.{n}_l{l}"] for l in range(2) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")})
+    fc = torch.nn.Linear(hp["D"], hp["n_classes"]).eval()
+    fc.load_state_dict({"weight": W["head.out.weight"], "bias": W["head.out.bias"]})
+    return m, lstm, fc
+
+
+TAP0_ROW_STEP = 16      # tap 0 of the longest toy input is stored for every 16th row and the last one: the whole array would not fit a committed file
+
+
+def main_hubert(preset: str):
+    """tests/golden/hf_<preset>_s0.npz for the semantic encoder (rule C12h): HuggingFace HubertModel + nn.LSTM + nn.Linear on the synthetic `preset` file
+    (tools/make_synth_hubert.py), on the first n samples of tests/semantic_encoder_ref.fixture_signal.  hub_toy, per length: the six taps of
+    bark_hip_semantic_encode_tap (tap 0 of n = 16000 only for the rows tap0_rows_n16000), ids, top-two margins and ids; hub_base: hidden_states[7], ids, margins,
+    top-two ids.  <tap>_f16emu_maxabs_n<n>: the largest deviation from itself of the same stack with the input of every Conv1d, Linear and LSTM rounded to f16
+    by a forward pre-hook (the file's weights already are f16 values).  Asserts what the tests rely on: at n = 16000 at least 8 distinct ids and at least
+    half of the frames decided (margin > 8 x the logits' f16emu_maxabs), and the f16-emulated run carries HF's id on every decided frame of every length."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import semantic_encoder_ref as sref
+    from tools.make_synth_hubert import ensure_hubert
+    torch.set_num_threads(8)
+    hp, W = sref.load(ensure_hubert(preset, 0))
+    model, lstm, fc = build_hf_hubert(hp, W)
+    L = hp["output_layer"]
+    lengths = sref.TOY_LENGTHS if preset == "hub_toy" else sref.BASE_LENGTHS
+    out = {"lengths": np.array(lengths, np.int32)}
+
+    def run(x):
+        keep = {}
+        hooks = [model.feature_extractor.conv_layers[0].register_forward_hook(lambda m, a, o: keep.__setitem__("conv0", o[0].T)),
+                 model.feature_extractor.register_forward_hook(lambda m, a, o: keep.__setitem__("conv", o[0].T)),
+                 model.feature_projection.projection.register_forward_hook(lambda m, a, o: keep.__setitem__("proj", o[0]))]
+        hs = model(input_values=torch.from_numpy(x)[None], output_hidden_states=True).hidden_states
+        for hk in hooks:
+            hk.remove()
+        keep["h0"], keep["hL"] = hs[0][0], hs[L][0]
+        keep["logits"] = fc(lstm(hs[L])[0])[0]
+        return {k: v.detach().numpy().astype(np.float32).copy() for k, v in keep.items()}
+
+    def round_input(mod, args):
+        return tuple(a.half().float() if torch.is_tensor(a) and a.is_floating_point() else a for a in args)
+
+    with torch.no_grad():
+        for n in lengths:
+            x = sref.fixture_signal(n)
+            taps = run(x)
+            mods = [m for net in (model, lstm, fc) for m in net.modules() if isinstance(m, (torch.nn.Conv1d, torch.nn.Linear, torch.nn.LSTM))]
+            hooks = [m.register_forward_pre_hook(round_input) for m in mods]
+            taps16 = run(x)
+            for hk in hooks:
+                hk.remove()
+            ids = np.argmax(taps["logits"], axis=1).astype(np.int32)
+            ids16 = np.argmax(taps16["logits"], axis=1).astype(np.int32)
+            margin, top2 = sref.margins(taps["logits"])
+            emu = {k: float(np.abs(taps16[k] - taps[k]).max()) for k in sref.TAPS}
+            decided = margin > 8.0 * emu["logits"]
+            assert len(ids) == sref.frame_count(n)
+            assert np.array_equal(ids[decided], ids16[decided]), f"n {n}: the f16-emulated run leaves HF's id on a decided frame"
+            if n == 16000:
+                assert len(set(ids.tolist())) >= 8, f"only {len(set(ids.tolist()))} distinct ids at 16000 samples: change the recipe"
+                assert 2 * int(decided.sum()) >= len(ids), f"only {int(decided.sum())} of {len(ids)} frames decided at 16000 samples: change the recipe"
+            for k in sref.TAPS:
+                out[f"{k}_f16emu_maxabs_n{n}"] = np.float64(emu[k])
+            out[f"ids_n{n}"] = ids
+            out[f"margin_n{n}"] = margin
+            out[f"top2_n{n}"] = top2
+            if preset == "hub_toy":
+                for k in sref.TAPS:
+                    a = taps[k]
+                    if k == "conv0" and n == 16000:
+                        rows = np.unique(np.concatenate([np.arange(0, len(a), TAP0_ROW_STEP), [len(a) - 1]])).astype(np.int32)
+                        out[f"tap0_rows_n{n}"] = rows
+                        a = a[rows]
+                    out[f"{k}_n{n}"] = a
+            else:
+                out[f"hL_n{n}"] = taps["hL"]
+            print(n, "T", len(ids), "distinct", len(set(ids.tolist())), "decided", int(decided.sum()), " f16emu max abs:", {k: "%.2e" % v for k, v in emu.items()})
+    dst = os.path.join(ROOT, "tests", "golden", f"hf_{preset}_s0.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+    assert os.path.getsize(dst) < (1 << 20)
+
+
 def main():
     import torch
+
+    if len(sys.argv) > 1 and sys.argv[1] == "hubert":
+        for preset in (sys.argv[2:] or ["hub_toy", "hub_base"]):
+            main_hubert(preset)
+        return
 
     if len(sys.argv) > 1 and sys.argv[1] == "encoder":
         for preset in (sys.argv[2:] or ["toy_enc", "small"]):
