@@ -82,6 +82,7 @@ def build_library(force: bool = False) -> str:
 
 
 _LIB = None
+VOICE_AUDIO_MAX_SAMPLES = 480000          # BARK_HIP_VOICE_AUDIO_MAX_SAMPLES (include/bark_mi355x.h)
 
 EXPORTS = [
     # bark.h
@@ -99,6 +100,7 @@ EXPORTS = [
     "bark_hip_set_voice_prompt", "bark_hip_generate_batch_voiced", "bark_hip_batcher_submit_voiced", "bark_hip_pick_rows",
     "bark_hip_has_codec_encoder", "bark_hip_codec_encode", "bark_hip_codec_encode_many", "bark_hip_codec_encode_tap", "bark_hip_rvq_encode", "bark_hip_codec_encode_latents", "bark_hip_codec_encode_device_us",
     "bark_hip_load_semantic_encoder", "bark_hip_has_semantic_encoder", "bark_hip_semantic_encode", "bark_hip_semantic_encode_tap", "bark_hip_semantic_head", "bark_hip_semantic_encode_device_us",
+    "bark_hip_resample_taps", "bark_hip_resample_24k_to_16k", "bark_hip_voice_from_audio", "bark_hip_set_voice_from_audio", "bark_hip_time_resample",
 ]
 
 
@@ -157,6 +159,12 @@ def load_library() -> C.CDLL:
     lib.bark_hip_semantic_head.argtypes = [vp, fp, C.c_int, ip, fp]
     lib.bark_hip_semantic_encode_device_us.restype = C.c_double
     lib.bark_hip_semantic_encode_device_us.argtypes = [vp]
+    lib.bark_hip_resample_taps.argtypes = [fp]
+    lib.bark_hip_resample_24k_to_16k.argtypes = [vp, fp, C.c_int, fp, C.c_int]
+    lib.bark_hip_voice_from_audio.argtypes = [vp, fp, C.c_int, ip, C.c_int, ip, ip, C.c_int, ip, ip]
+    lib.bark_hip_set_voice_from_audio.argtypes = [vp, fp, C.c_int]
+    lib.bark_hip_time_resample.restype = C.c_double
+    lib.bark_hip_time_resample.argtypes = [vp, C.c_int, C.c_int]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
     lib.bark_hip_generate_batch_seeded.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_uint32)]
     lib.bark_hip_generate_batch_ex.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams)]
@@ -498,6 +506,41 @@ class BarkContext:
 
     def semantic_encode_device_us(self) -> float:
         return float(self._lib.bark_hip_semantic_encode_device_us(self._h))
+
+    # ---- voice prompts from a recording (rule C13r): the device resampler and the three streams in one native call ----
+    def resample_24k_to_16k(self, pcm) -> np.ndarray:
+        """24 kHz mono float samples -> (2 n + 2) // 3 samples at 16 kHz (bark_hip_resample_24k_to_16k: f32, one fmaf chain per output)."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        out = np.zeros(max((2 * len(x) + 2) // 3, 1), np.float32)
+        n = self._lib.bark_hip_resample_24k_to_16k(self._h, x.ctypes.data, len(x), out.ctypes.data, out.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_resample_24k_to_16k failed")
+        return out[:n].copy()
+
+    def voice_from_audio(self, pcm):
+        """A recording of the speaker (24 kHz mono; its last 480 000 samples are used) -> (semantic [n], coarse [T][2], fine [T][8]) by bark_hip_voice_from_audio."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        used = min(len(x), VOICE_AUDIO_MAX_SAMPLES)
+        sem = np.zeros(max(((2 * used + 2) // 3 - 400) // 320 + 1, 1), np.int32)
+        rows = max((used + 319) // 320, 1)
+        coarse, fine = np.zeros((rows, 2), np.int32), np.zeros((rows, 8), np.int32)
+        n_sem, n_frames = C.c_int32(0), C.c_int32(0)
+        if self._lib.bark_hip_voice_from_audio(self._h, x.ctypes.data, len(x), sem.ctypes.data, sem.size, coarse.ctypes.data, fine.ctypes.data, rows,
+                                               C.addressof(n_sem), C.addressof(n_frames)) != 0:
+            raise ValueError("bark_hip_voice_from_audio refused the recording (no encoder, too short, non-finite samples, or a voice prompt the engine refuses)")
+        return sem[:n_sem.value].copy(), coarse[:n_frames.value].copy(), fine[:n_frames.value].copy()
+
+    def set_voice_from_audio(self, pcm):
+        """bark_hip_set_voice_from_audio: the voice prompt of the recording becomes the context's."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        if self._lib.bark_hip_set_voice_from_audio(self._h, x.ctypes.data, len(x)) != 0:
+            raise ValueError("bark_hip_set_voice_from_audio refused the recording")
+
+    def time_resample(self, n: int, iters: int) -> float:
+        us = self._lib.bark_hip_time_resample(self._h, int(n), int(iters))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_resample failed")
+        return us
 
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""

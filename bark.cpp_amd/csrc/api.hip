@@ -351,6 +351,66 @@ int bark_hip_semantic_head(struct bark_context * bctx, const float * feats_TxH, 
 
 double bark_hip_semantic_encode_device_us(struct bark_context * bctx) { return bctx ? bctx->hub_device_us : -1.0; }
 
+int bark_hip_resample_taps(float * out44) {
+    if (!out44) return -1;
+    memcpy(out44, resample_taps(), 44 * sizeof(float));
+    return 44;
+}
+
+int bark_hip_resample_24k_to_16k(struct bark_context * bctx, const float * pcm24k, int n, float * out16k, int capacity) {
+    if (!bctx || !pcm24k || !out16k) return -1;
+    return guarded("bark_hip_resample_24k_to_16k", -1, [&] {
+        if (n >= 1 && n <= kResampleMaxSamples && (2 * n + 2) / 3 > capacity) throw std::runtime_error("output buffer too small");      // refused before any work
+        std::vector<float> r = engine_resample_24k_16k(bctx, pcm24k, n);
+        memcpy(out16k, r.data(), r.size() * 4);
+        return (int) r.size();
+    });
+}
+
+double bark_hip_time_resample(struct bark_context * bctx, int n, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_resample", -1.0, [&] { return engine_time_resample(bctx, n, iters); });
+}
+
+namespace {
+// the part of a recording that bark_hip_voice_from_audio uses, and the sizes of what it makes of it
+struct VoiceAudioCounts { int n_used, n_sem, n_frames; };
+VoiceAudioCounts voice_audio_counts(int n_samples) {
+    VoiceAudioCounts k;
+    k.n_used = std::min(n_samples, BARK_HIP_VOICE_AUDIO_MAX_SAMPLES);
+    k.n_sem = ((2 * k.n_used + 2) / 3 - 400) / 320 + 1;
+    k.n_frames = (k.n_used + 319) / 320;
+    return k;
+}
+}  // namespace
+
+int bark_hip_voice_from_audio(struct bark_context * bctx, const float * pcm24k, int n_samples, int32_t * semantic, int semantic_capacity, int32_t * coarse_Tx2,
+                              int32_t * fine_Tx8, int capacity_rows, int32_t * n_semantic, int32_t * n_frames) {
+    if (!bctx || !pcm24k || !semantic || !coarse_Tx2 || !fine_Tx8 || !n_semantic || !n_frames) return -1;
+    return guarded("bark_hip_voice_from_audio", -1, [&] {
+        if (n_samples >= 599) {                                     // refused before any work: a result that does not fit
+            const VoiceAudioCounts k = voice_audio_counts(n_samples);
+            if (k.n_sem > semantic_capacity || k.n_frames > capacity_rows) throw std::runtime_error("output buffer too small");
+        }
+        const VoicePtr v = engine_voice_from_audio(bctx, pcm24k, n_samples);
+        memcpy(semantic, v->semantic.data(), v->semantic.size() * 4);
+        memcpy(coarse_Tx2, v->coarse.data(), v->coarse.size() * 4);
+        memcpy(fine_Tx8, v->fine.data(), v->fine.size() * 4);
+        *n_semantic = (int32_t) v->semantic.size();
+        *n_frames = (int32_t) (v->fine.size() / 8);
+        return 0;
+    });
+}
+
+int bark_hip_set_voice_from_audio(struct bark_context * bctx, const float * pcm24k, int n_samples) {
+    if (!bctx || !pcm24k) return -1;
+    return guarded("bark_hip_set_voice_from_audio", -1, [&] {
+        VoicePtr v = engine_voice_from_audio(bctx, pcm24k, n_samples);      // throws on a refusal: the context keeps what it had
+        bctx->voice = v;
+        return 0;
+    });
+}
+
 struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed) {
     if (!src) return nullptr;
     return guarded("bark_hip_clone_context", (bark_context *) nullptr, [&] { return engine_clone(src, seed); });

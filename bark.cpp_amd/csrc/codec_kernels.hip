@@ -596,4 +596,67 @@ void launch_pos_conv(hipStream_t s, const PosConvArgs & a) {
     hipLaunchKernelGGL(pos_conv_mfma_kernel, dim3((a.T + 127) / 128, a.G * (a.co32 / 32)), dim3(256), 0, s, a);
 }
 
+// ---- 24 kHz -> 16 kHz resampler (rule C13r) ----------------------------------------------------------------------------------
+// Output m sits at input time t = 1.5 m: base = floor(t), phase = m % 2, y[m] = the fmaf chain acc = fmaf(x[base + j], h[phase][j + 10], acc) over j = -10 .. 11
+// ascending from acc = +0, zero taps included, samples outside the recording +0, no renormalisation.  The taps are the f32 roundings of the double-precision
+// values of c sinc(c u) cos^2(pi u / (2 W)) (|u| < W, else 0) at u = phase / 2 - j, c = 0.99 * 2 / 3, W = 6 / c (bark.cpp_amd/voice.py resample_24k_to_16k): a
+// committed table, never computed at load time - a libm's sin / cos may differ from numpy's in the last place.
+// One workgroup = 512 consecutive outputs = 768 input samples + 10 in front + 12 behind, staged once in LDS as 198 16-byte loads from the 16-byte boundary
+// 12 samples in front of the tile; work-item t forms the pair m = 2 k, 2 k + 1 (k = 256 blockIdx.x + t) from the 23 samples x[3 k - 10 .. 3 k + 12] (LDS
+// stride 3 between lanes: no bank conflict) and writes it as one 8-byte store.  The taps travel as a kernel argument (scalar registers).
+constexpr int kRsTile = 512, kRsIn = 768, kRsLead = 12, kRsWin4 = (kRsIn + 2 * kRsLead) / 4;
+struct ResampleTaps { float h[44]; };
+static const float kResampleTaps[44] = {
+    // phase 0 (even m), j = -10 .. 11
+    0.000000000e+00f, -1.635075932e-06f, -1.076447428e-03f, 5.282599479e-03f, -1.722944784e-03f, -2.172333933e-02f, 4.274801165e-02f, -5.026828963e-03f,
+    -1.189598665e-01f, 2.706918120e-01f, 6.600000262e-01f, 2.706918120e-01f, -1.189598665e-01f, -5.026828963e-03f, 4.274801165e-02f, -2.172333933e-02f,
+    -1.722944784e-03f, 5.282599479e-03f, -1.076447428e-03f, -1.635075932e-06f, 0.000000000e+00f, -0.000000000e+00f,
+    // phase 1 (odd m), j = -10 .. 11
+    0.000000000e+00f, 0.000000000e+00f, -3.660349757e-04f, 4.891819553e-04f, 7.250521332e-03f, -1.795493253e-02f, 3.380680922e-03f, 5.090378597e-02f,
+    -9.356202930e-02f, 6.227747072e-03f, 5.438855886e-01f, 5.438855886e-01f, 6.227747072e-03f, -9.356202930e-02f, 5.090378597e-02f, 3.380680922e-03f,
+    -1.795493253e-02f, 7.250521332e-03f, 4.891819553e-04f, -3.660349757e-04f, 0.000000000e+00f, 0.000000000e+00f,
+};
+const float * resample_taps() { return kResampleTaps; }
+
+__global__ __launch_bounds__(256) void resample_24k_16k_kernel(const float * x, int n, float * y, int n_out, int vec, const ResampleTaps taps) {
+    __shared__ float4 win4[kRsWin4];
+    const int t = (int) threadIdx.x;
+    if (t < kRsWin4) {
+        const int g = (int) blockIdx.x * kRsIn - kRsLead + 4 * t;       // first of this work-item's four samples; a multiple of 4
+        float4 v;
+        if (vec && g >= 0 && g + 3 < n) v = *reinterpret_cast<const float4 *>(x + g);
+        else {
+            v.x = (g >= 0 && g < n) ? x[g] : 0.0f;
+            v.y = (g + 1 >= 0 && g + 1 < n) ? x[g + 1] : 0.0f;
+            v.z = (g + 2 >= 0 && g + 2 < n) ? x[g + 2] : 0.0f;
+            v.w = (g + 3 >= 0 && g + 3 < n) ? x[g + 3] : 0.0f;
+        }
+        win4[t] = v;
+    }
+    __syncthreads();
+    const int m = (int) blockIdx.x * kRsTile + 2 * t;
+    if (m >= n_out) return;
+    const float * w = reinterpret_cast<const float *>(win4) + 3 * t + (kRsLead - 10);      // x[3 k - 10]
+    float xv[23];
+    #pragma unroll
+    for (int i = 0; i < 23; i++) xv[i] = w[i];
+    float a0 = 0.0f, a1 = 0.0f;
+    #pragma unroll
+    for (int i = 0; i < 22; i++) {
+        a0 = fmaf(xv[i], taps.h[i], a0);                 // base 3 k:     x[3 k - 10 + i]
+        a1 = fmaf(xv[i + 1], taps.h[22 + i], a1);        // base 3 k + 1: x[3 k - 9 + i]
+    }
+    if (m + 1 >= n_out) y[m] = a0;
+    else if (vec) *reinterpret_cast<float2 *>(y + m) = make_float2(a0, a1);
+    else { y[m] = a0; y[m + 1] = a1; }
+}
+void launch_resample_24k_16k(hipStream_t s, const float * x, int n, float * y, int n_out) {
+    if (!x || !y || n < 1 || n > kResampleMaxSamples || n_out != (2 * n + 2) / 3)
+        kernel_fail("bark-hip: the resampler takes 1 .. %d samples and writes (2 n + 2) / 3 (got n %d, n_out %d)", kResampleMaxSamples, n, n_out);
+    ResampleTaps taps;
+    for (int i = 0; i < 44; i++) taps.h[i] = kResampleTaps[i];
+    const int vec = (((size_t) x & 15) == 0 && ((size_t) y & 7) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(resample_24k_16k_kernel, dim3((n_out + kRsTile - 1) / kRsTile), dim3(256), 0, s, x, n, y, n_out, vec, taps);
+}
+
 }  // namespace barkhip

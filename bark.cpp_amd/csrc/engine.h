@@ -181,6 +181,7 @@ struct bark_context {
         float * tap = nullptr; size_t tap_elems = 0;                        // parity tap 0 in f32 (grown on demand)
     } hubs;
     hipEvent_t hub_ev[2] = {nullptr, nullptr}; double hub_device_us = -1.0;
+    float * rs_in = nullptr, * rs_out = nullptr; size_t rs_elems = 0;      // resampler (C13r): the recording and its 16 kHz form (grown on demand)
     struct CodecGraph { hipGraphExec_t exec = nullptr; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -278,6 +279,13 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * ctx, c
 void engine_load_semantic_encoder(bark_context * ctx, const char * path);
 std::vector<int32_t> engine_semantic_encode(bark_context * ctx, const float * pcm16k, int n, int tap_stage, std::vector<float> * tap);
 std::vector<int32_t> engine_semantic_head(bark_context * ctx, const float * feats_TxH, int T, std::vector<float> * logits);
+// Resampler (C13r): n samples at 24 kHz (1 .. 4096 codec frames, all finite) -> (2 n + 2) / 3 samples at 16 kHz.  engine_voice_from_audio: the whole voice prompt
+// of a recording - its last kVoiceAudioMaxSamples samples through the resampler and the semantic encoder, and through the codec encoder (8 codebooks; the
+// first two are the coarse stream) - checked as engine_make_voice checks one; throws where any of the steps or that check refuses.
+constexpr int kVoiceAudioMaxSamples = 480000;
+std::vector<float> engine_resample_24k_16k(bark_context * ctx, const float * pcm24k, int n);
+VoicePtr engine_voice_from_audio(bark_context * ctx, const float * pcm24k, int n);
+double engine_time_resample(bark_context * ctx, int n, int iters);
 // kernel-level hook: latents [T][H] -> codes [n_q][T] by the RVQ kernel alone (C11q)
 std::vector<int32_t> engine_rvq_encode(bark_context * ctx, const float * latents, int T, int n_q);
 bool engine_generate(bark_context * ctx, const char * text);

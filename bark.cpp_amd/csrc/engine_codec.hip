@@ -508,4 +508,51 @@ std::vector<int32_t> engine_semantic_encode(bark_context * c, const float * pcm,
     return ids;
 }
 
+// ---- voice prompts from a recording: the resampler (rule C13r) and the composition of the three streams ----------------------------------------------
+std::vector<float> engine_resample_24k_16k(bark_context * c, const float * pcm, int n) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!pcm || n < 1 || n > kResampleMaxSamples) throw std::runtime_error("resampler: a recording needs 1 .. 1 310 720 samples (4096 codec frames)");
+    for (int i = 0; i < n; i++) if (!std::isfinite(pcm[i])) throw std::runtime_error("resampler: non-finite sample");
+    const int n_out = (2 * n + 2) / 3;
+    if ((size_t) n > c->rs_elems) { c->rs_in = dev_alloc<float>(c, (size_t) n); c->rs_out = dev_alloc<float>(c, ((size_t) 2 * n + 2) / 3); c->rs_elems = (size_t) n; }
+    hipStream_t s = c->stream;
+    HIP_OK(hipMemcpyAsync(c->rs_in, pcm, (size_t) n * 4, hipMemcpyHostToDevice, s));
+    launch_resample_24k_16k(s, c->rs_in, n, c->rs_out, n_out);
+    std::vector<float> out((size_t) n_out);
+    HIP_OK(hipMemcpyAsync(out.data(), c->rs_out, out.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return out;
+}
+
+double engine_time_resample(bark_context * c, int n, int iters) {
+    HIP_OK(hipSetDevice(c->device));
+    if (n < 1 || n > kResampleMaxSamples) throw std::runtime_error("time_resample: 1 .. 1 310 720 samples");
+    const int n_out = (2 * n + 2) / 3;
+    if ((size_t) n > c->rs_elems) { c->rs_in = dev_alloc<float>(c, (size_t) n); c->rs_out = dev_alloc<float>(c, ((size_t) 2 * n + 2) / 3); c->rs_elems = (size_t) n; }
+    HIP_OK(hipMemsetAsync(c->rs_in, 0, (size_t) n * 4, c->stream));      // the time does not depend on the values
+    iters = std::max(1, iters);
+    for (int i = 0; i < 2; i++) launch_resample_24k_16k(c->stream, c->rs_in, n, c->rs_out, n_out);
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_resample_24k_16k(c->stream, c->rs_in, n, c->rs_out, n_out); }) / iters;
+}
+
+VoicePtr engine_voice_from_audio(bark_context * c, const float * pcm, int n) {
+    if (!c->hub) throw std::runtime_error("voice from audio: no semantic encoder loaded (bark_hip_load_semantic_encoder)");
+    if (!c->codec.enc.present) throw std::runtime_error("voice from audio: the model file holds no codec encoder");
+    if (!pcm || n < 599) throw std::runtime_error("voice from audio: a recording needs at least 599 samples (400 at 16 kHz: one semantic frame)");
+    // every sample is looked at, also those in front of the part that is used: a recording with a hole in it is refused as a whole
+    for (int i = 0; i < n; i++) if (!std::isfinite(pcm[i]) || !std::isfinite((float) (_Float16) pcm[i])) throw std::runtime_error("voice from audio: non-finite sample (or one beyond the f16 range)");
+    if (n > kVoiceAudioMaxSamples) { pcm += n - kVoiceAudioMaxSamples; n = kVoiceAudioMaxSamples; }      // every stage reads the END of its history stream
+    const std::vector<float> x16 = engine_resample_24k_16k(c, pcm, n);
+    const std::vector<int32_t> sem = engine_semantic_encode(c, x16.data(), (int) x16.size(), -1, nullptr);
+    const std::vector<int32_t> codes = std::move(engine_codec_encode_many(c, {pcm}, {n}, 8, -1, nullptr)[0]);      // [8][T]
+    const int T = (int) (codes.size() / 8);
+    std::vector<int32_t> coarse((size_t) T * 2), fine((size_t) T * 8);
+    for (int t = 0; t < T; t++) for (int q = 0; q < 8; q++) {
+        fine[(size_t) t * 8 + q] = codes[(size_t) q * T + t];
+        if (q < 2) coarse[(size_t) t * 2 + q] = codes[(size_t) q * T + t];
+    }
+    const bark_hip_voice_prompt v{sem.data(), (int32_t) sem.size(), coarse.data(), T, fine.data(), T};
+    return engine_make_voice(c, &v);
+}
+
 }  // namespace barkhip

@@ -338,4 +338,11 @@ void launch_pos_conv(hipStream_t s, const PosConvArgs & a);
 // post-norm layer step: out = LayerNorm(x + y) (y may be null) as f32 rows (out32, may alias x) and as f16 rows (out16); eps 1e-5, double sums as ln_rows_kernel
 void launch_add_ln_rows(hipStream_t s, const float * x, const float * y, int N, int E, const float * g, const float * b, float * out32, half_t * out16);
 
+// ---- 24 kHz -> 16 kHz resampler (rule C13r; codec_kernels.hip) -----------------------------------------
+// y[m] = one fmaf chain over the 22 taps of phase m % 2 in ascending order over x[floor(1.5 m) - 10 .. + 11], samples outside [0, n) are +0; n_out = (2 n + 2) / 3.
+// resample_taps(): the committed table, [phase][22]
+constexpr int kResampleMaxSamples = 4096 * 320;
+const float * resample_taps();
+void launch_resample_24k_16k(hipStream_t s, const float * x, int n, float * y, int n_out);
+
 }  // namespace barkhip

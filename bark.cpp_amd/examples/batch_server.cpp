@@ -9,9 +9,18 @@
 // a field left out takes the server's --top-k / --top-p, an invalid one is answered 400.
 // "voice": "name" gives the request the voice prompt (speaker history, bark_hip_voice_prompt) loaded with --voice name=file (repeatable; the file format
 // of bark.cpp_amd/voice.py); an unknown name is answered 400, a request without the field has no voice.
+// Voices from a recording (--semantic-encoder file loads HuBERT and its token head, bark_hip_load_semantic_encoder; the model file must carry the codec
+// encoder): --voice-audio name=file.wav at start-up, and while the server runs
+//   POST /voices?name=NAME   body: a mono 24 kHz WAV (16-bit PCM or 32-bit float, at most 4 MiB) -> 200 {"name": ..., "n_semantic": ..., "n_frames": ...};
+//                            400 a bad name, a bad WAV, another rate, a recording the engine refuses; 409 no semantic or codec encoder; 413 too large.
+//                            An existing name is replaced; a request in flight keeps the voice it started with.
+//   GET /voices              {"voices": ["NAME", ...]}
+//   GET /voices/NAME         the voice as a voice prompt file (what --voice name=file reads)
+// The recording is encoded by bark_hip_voice_from_audio on a clone kept for that purpose behind its own mutex: the contexts the collector owns are never
+// touched by a connection thread.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -21,12 +30,16 @@
 #include <sys/socket.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -44,6 +57,8 @@ struct Options {
     float temp = -1.0f, fine_temp = -1.0f;
     int32_t top_k = 0; float top_p = 1.0f;         // --top-k / --top-p: the filter of requests that carry no "top_k" / "top_p" of their own
     std::vector<std::string> voices;               // --voice name=file
+    std::string semantic_encoder;                  // --semantic-encoder file
+    std::vector<std::string> voice_audio;          // --voice-audio name=file.wav
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -64,7 +79,36 @@ void respond(int fd, int status, const char * reason, const char * type, const s
 std::atomic<uint32_t> next_seed{0};
 bark_hip_request_params request_defaults{};            // the context's sampling parameters (a request with its own filter carries them explicitly)
 bark_hip_sampling_filter filter_defaults{0, 1.0f};
-std::map<std::string, VoiceFile> voice_table;          // --voice name=file, read-only once the server listens
+// the voices by name: read by every /bark request, written by POST /voices.  An entry is never changed, only replaced: a request that has looked its
+// voice up keeps it alive through its shared_ptr while a later POST puts another one under the same name
+std::shared_mutex voice_mutex;
+std::map<std::string, std::shared_ptr<const VoiceFile>> voice_table;
+std::shared_ptr<const VoiceFile> find_voice(const std::string & name) {
+    std::shared_lock<std::shared_mutex> lock(voice_mutex);
+    const auto it = voice_table.find(name);
+    return it == voice_table.end() ? nullptr : it->second;
+}
+void put_voice(const std::string & name, VoiceFile && v) {
+    auto p = std::make_shared<const VoiceFile>(std::move(v));
+    std::unique_lock<std::shared_mutex> lock(voice_mutex);
+    voice_table[name] = std::move(p);
+}
+// the context that encodes recordings (a clone made after the semantic encoder was loaded, so it shares the device copy); null: no encoder available
+bark_context * encoder_ctx = nullptr;
+std::mutex encoder_mutex;
+constexpr size_t kMaxBody = 1u << 20, kMaxVoiceBody = 4u << 20;
+// 24 kHz mono samples -> voice; false: the engine refused the recording (its message is on stderr)
+bool voice_from_recording(const std::vector<float> & pcm, VoiceFile & out) {
+    const int used = (int) std::min<size_t>(pcm.size(), BARK_HIP_VOICE_AUDIO_MAX_SAMPLES);
+    const int rows = (used + 319) / 320, sem_cap = std::max(1, ((2 * used + 2) / 3 - 400) / 320 + 1);
+    out.semantic.assign((size_t) sem_cap, 0); out.coarse.assign((size_t) rows * 2, 0); out.fine.assign((size_t) rows * 8, 0);
+    int32_t n_sem = 0, n_frames = 0;
+    std::lock_guard<std::mutex> lock(encoder_mutex);
+    if (pcm.size() > 0x7fffffffu || bark_hip_voice_from_audio(encoder_ctx, pcm.data(), (int) pcm.size(), out.semantic.data(), sem_cap, out.coarse.data(), out.fine.data(), rows, &n_sem, &n_frames) != 0)
+        return false;
+    out.semantic.resize((size_t) n_sem); out.coarse.resize((size_t) n_frames * 2); out.fine.resize((size_t) n_frames * 8);
+    return true;
+}
 std::atomic<int> open_connections{0};
 constexpr int kMaxConnections = 512;                     // beyond that a connection is answered 503 at once
 
@@ -90,14 +134,48 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
         const size_t p = lower.find("content-length:");
         if (p != std::string::npos) content_length = (size_t) strtoul(head.c_str() + p + 15, nullptr, 10);
     }
-    if (content_length > (1u << 20)) { respond(fd, 413, "Payload Too Large", "text/plain", "too large"); ::close(fd); return; }
+    const std::string target = head.substr(0, head.find("\r\n"));      // the request line
+    const bool post_voice = target.compare(0, 13, "POST /voices ") == 0 || target.compare(0, 13, "POST /voices?") == 0;
+    if (content_length > (post_voice ? kMaxVoiceBody : kMaxBody)) { respond(fd, 413, "Payload Too Large", "text/plain", "too large"); ::shutdown(fd, SHUT_RDWR); ::close(fd); return; }
     std::string body = req.substr(head_end + 4);
     while (body.size() < content_length) {
         const ssize_t k = ::recv(fd, buf, sizeof(buf), 0);
         if (k <= 0) break;
         body.append(buf, (size_t) k);
     }
-    if (head.compare(0, 4, "GET ") == 0) {
+    if (post_voice) {
+        // checked in the order: what the server can do at all, the name, the recording
+        const size_t sp = target.rfind(' ');                  // "POST /voices?name=a HTTP/1.1" -> "/voices?name=a"
+        const std::string path = target.substr(5, sp != std::string::npos && sp > 5 ? sp - 5 : std::string::npos);
+        std::string name, err;
+        std::vector<float> pcm;
+        int rate = 0;
+        VoiceFile vf;
+        if (!encoder_ctx) respond(fd, 409, "Conflict", "text/plain", "no semantic encoder (--semantic-encoder) or no codec encoder in the model file");
+        else if (!barkhttp::query_param(path, "name", name) || !barkhttp::valid_voice_name(name)) respond(fd, 400, "Bad Request", "text/plain", "expected ?name=NAME with 1 .. 64 of [A-Za-z0-9_.-]");
+        else if (body.size() != content_length || !barkhttp::parse_wav(body, pcm, rate, err)) respond(fd, 400, "Bad Request", "text/plain", err.empty() ? "incomplete body" : err);
+        else if (rate != 24000) respond(fd, 400, "Bad Request", "text/plain", "the recording must be sampled at 24000 Hz");
+        else if (!voice_from_recording(pcm, vf)) respond(fd, 400, "Bad Request", "text/plain", "the engine refused the recording (too short, or samples that are not finite)");
+        else {
+            char js[256];
+            snprintf(js, sizeof(js), "{\"name\": \"%s\", \"n_semantic\": %zu, \"n_frames\": %zu}", name.c_str(), vf.semantic.size(), vf.fine.size() / 8);
+            put_voice(name, std::move(vf));
+            respond(fd, 200, "OK", "application/json", js);
+        }
+    } else if (target.compare(0, 12, "GET /voices ") == 0 || target.compare(0, 12, "GET /voices?") == 0) {
+        std::string js = "{\"voices\": [";
+        {
+            std::shared_lock<std::shared_mutex> lock(voice_mutex);
+            bool first = true;
+            for (const auto & kv : voice_table) { js += std::string(first ? "\"" : ", \"") + kv.first + "\""; first = false; }      // names from --voice may hold anything but '='
+        }
+        respond(fd, 200, "OK", "application/json", js + "]}");
+    } else if (target.compare(0, 12, "GET /voices/") == 0) {
+        const size_t e = target.find_first_of(" ?", 12);
+        const std::shared_ptr<const VoiceFile> v = find_voice(target.substr(12, e == std::string::npos ? std::string::npos : e - 12));
+        if (v) respond(fd, 200, "OK", "application/octet-stream", barkhttp::voice_file_bytes(*v));
+        else respond(fd, 404, "Not Found", "text/plain", "no such voice");
+    } else if (head.compare(0, 4, "GET ") == 0) {
         respond(fd, 200, "OK", "text/html", "<html>bark batch server: POST /bark {\"text\": \"...\"}</html>");
     } else if (head.compare(0, 11, "POST /bark ") == 0 || head.compare(0, 11, "POST /bark?") == 0) {
         std::string text;
@@ -115,9 +193,15 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 ::close(fd);
                 return;
             }
-            const VoiceFile * vf = nullptr;
-            if (barkhttp::request_voice(body, voice_table, &vf) < 0) {
-                respond(fd, 400, "Bad Request", "text/plain", "\"voice\" must name a voice loaded with --voice name=file");
+            // "voice": absent - no voice; otherwise a string that names a voice of the table (held until the answer is sent)
+            std::shared_ptr<const VoiceFile> vf;
+            int has_voice = 0;
+            {
+                std::shared_lock<std::shared_mutex> lock(voice_mutex);
+                has_voice = barkhttp::request_voice(body, voice_table, &vf);
+            }
+            if (has_voice < 0) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"voice\" must name a voice loaded with --voice name=file, --voice-audio or POST /voices");
                 ::shutdown(fd, SHUT_RDWR);
                 ::close(fd);
                 return;
@@ -151,7 +235,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)]\n", argv0);
 }
 
 }  // namespace
@@ -174,12 +258,18 @@ int main(int argc, char ** argv) {
         else if (a == "--top-k") o.top_k = (int32_t) atoi(next("--top-k"));
         else if (a == "--top-p") o.top_p = (float) atof(next("--top-p"));
         else if (a == "--voice") o.voices.push_back(next("--voice"));
+        else if (a == "--semantic-encoder") o.semantic_encoder = next("--semantic-encoder");
+        else if (a == "--voice-audio") o.voice_audio.push_back(next("--voice-audio"));
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
-    for (const std::string & v : o.voices) {
-        std::string err;
-        if (!barkhttp::add_voice(voice_table, v, err)) { fprintf(stderr, "%s: %s\n", argv[0], err.c_str()); return 1; }
+    {
+        std::map<std::string, VoiceFile> files;
+        for (const std::string & v : o.voices) {
+            std::string err;
+            if (!barkhttp::add_voice(files, v, err)) { fprintf(stderr, "%s: %s\n", argv[0], err.c_str()); return 1; }
+        }
+        for (auto & kv : files) put_voice(kv.first, std::move(kv.second));
     }
     signal(SIGPIPE, SIG_IGN);
     bark_context_params params = bark_context_default_params();
@@ -198,12 +288,39 @@ int main(int argc, char ** argv) {
     // a voice the engine would refuse (ids out of range, empty trimmed history, too long for the coarse context) is refused here, not at the first
     // request that names it; the contexts themselves keep no voice: a request without the field has none
     for (const auto & kv : voice_table) {
-        const VoiceFile & vf = kv.second;
+        const VoiceFile & vf = *kv.second;
         const bark_hip_voice_prompt vp{vf.semantic.data(), (int32_t) vf.semantic.size(), vf.coarse.data(), (int32_t) (vf.coarse.size() / 2), vf.fine.data(), (int32_t) (vf.fine.size() / 8)};
         if (bark_hip_set_voice_prompt(ctxs[0], &vp) != 0) { fprintf(stderr, "%s: voice '%s' was refused\n", argv[0], kv.first.c_str()); for (bark_context * x : ctxs) bark_free(x); return 1; }
     }
     (void) bark_hip_set_voice_prompt(ctxs[0], nullptr);
     bark_context * ctx = ctxs[0];
+    // the semantic encoder goes into context 0 BEFORE any clone is made: the clones made afterwards (the encoder's below, the collector's streams) share
+    // the device copy.  One further clone encodes recordings; the collector owns the others
+    auto fail = [&](const std::string & why) { fprintf(stderr, "%s: %s\n", argv[0], why.c_str()); if (encoder_ctx) bark_free(encoder_ctx); for (bark_context * x : ctxs) bark_free(x); return 1; };
+    if (!o.semantic_encoder.empty() && bark_hip_load_semantic_encoder(ctx, o.semantic_encoder.c_str()) != 0) return fail("could not load the semantic encoder " + o.semantic_encoder);
+    if (bark_hip_has_semantic_encoder(ctx) && bark_hip_has_codec_encoder(ctx)) {
+        encoder_ctx = bark_hip_clone_context(ctx, o.seed);
+        if (!encoder_ctx) return fail("could not clone a context for the encoders");
+    }
+    for (const std::string & arg : o.voice_audio) {
+        const size_t eq = arg.find('=');
+        if (eq == std::string::npos || eq + 1 >= arg.size() || !barkhttp::valid_voice_name(arg.substr(0, eq))) return fail("--voice-audio expects name=file.wav, the name 1 .. 64 of [A-Za-z0-9_.-]");
+        if (!encoder_ctx) return fail("--voice-audio needs --semantic-encoder and a model file with the codec encoder");
+        std::string body, err;
+        std::vector<float> pcm;
+        int rate = 0;
+        VoiceFile vf;
+        FILE * f = fopen(arg.substr(eq + 1).c_str(), "rb");
+        if (!f) return fail("cannot open " + arg.substr(eq + 1));
+        char buf[65536];
+        for (size_t k; body.size() <= kMaxVoiceBody && (k = fread(buf, 1, sizeof(buf), f)) > 0;) body.append(buf, k);
+        fclose(f);
+        if (body.size() > kMaxVoiceBody) return fail(arg.substr(eq + 1) + ": larger than 4 MiB");
+        if (!barkhttp::parse_wav(body, pcm, rate, err)) return fail(arg.substr(eq + 1) + ": " + err);
+        if (rate != 24000) return fail(arg.substr(eq + 1) + ": the recording must be sampled at 24000 Hz");
+        if (!voice_from_recording(pcm, vf)) return fail(arg.substr(eq + 1) + ": the engine refused the recording");
+        put_voice(arg.substr(0, eq), std::move(vf));
+    }
     bark_hip_batcher * batcher = ctxs.size() > 1 ? bark_hip_batcher_create_multi(ctxs.data(), (int) ctxs.size(), o.max_batch, o.max_wait_ms)
                                                  : bark_hip_batcher_create_ex(ctx, o.max_batch, o.max_wait_ms, o.streams);
     if (!batcher) { fprintf(stderr, "%s: could not create the request collector\n", argv[0]); for (bark_context * x : ctxs) bark_free(x); return 1; }

@@ -1,11 +1,12 @@
-// http_util.h - the request-side helpers of batch_server.cpp (flat-JSON field access, 32-bit float WAV framing), header-only so that a CPU test
-// can drive them without a device (tests/test_host_frontend.py).
+// http_util.h - the request-side helpers of batch_server.cpp (flat-JSON field access, 32-bit float WAV framing, WAV parsing, voice prompt files), header-only
+// so that a CPU test can drive them without a device (tests/test_host_frontend.py, tests/test_voice_audio_frontend.py).
 #pragma once
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -142,6 +143,103 @@ inline int request_voice(const std::string & js, const std::map<std::string, Voi
     const auto it = table.find(name);
     if (it == table.end()) return -1;
     *out = &it->second;
+    return 1;
+}
+
+// the inverse of read_voice_file: the bytes of the file (what bark.cpp_amd/voice.py save() writes), and the file itself
+inline std::string voice_file_bytes(const VoiceFile & v) {
+    const int32_t n[3] = {(int32_t) v.semantic.size(), (int32_t) (v.coarse.size() / 2), (int32_t) (v.fine.size() / 8)};
+    std::string s = "BVP1";
+    s.append(reinterpret_cast<const char *>(n), 12);
+    s.append(reinterpret_cast<const char *>(v.semantic.data()), (size_t) n[0] * 4);
+    s.append(reinterpret_cast<const char *>(v.coarse.data()), (size_t) n[1] * 8);
+    s.append(reinterpret_cast<const char *>(v.fine.data()), (size_t) n[2] * 32);
+    return s;
+}
+inline bool write_voice_file(const std::string & path, const VoiceFile & v, std::string & err) {
+    if (v.coarse.size() % 2 || v.fine.size() % 8 || v.semantic.size() > (1u << 20) || v.coarse.size() / 2 > (1u << 20) || v.fine.size() / 8 > (1u << 20)) {
+        err = "voice prompt: bad array sizes"; return false;
+    }
+    FILE * f = fopen(path.c_str(), "wb");
+    if (!f) { err = "cannot write " + path; return false; }
+    const std::string s = voice_file_bytes(v);
+    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
+    if (fclose(f) != 0 || !ok) { err = "cannot write " + path; return false; }
+    return true;
+}
+// a voice name as a route and a --voice-audio argument take it: 1 .. 64 of [A-Za-z0-9_.-], not starting with a dot
+inline bool valid_voice_name(const std::string & name) {
+    if (name.empty() || name.size() > 64 || name[0] == '.') return false;
+    for (char ch : name) if (!((ch >= 'a' && ch <= 'z') || (ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '.' || ch == '-')) return false;
+    return true;
+}
+// the value of `key` in the query string of a request target ("/voices?name=a&x=y" -> "a"); false when the key is absent
+inline bool query_param(const std::string & target, const char * key, std::string & out) {
+    size_t p = target.find('?');
+    while (p != std::string::npos && p + 1 < target.size()) {
+        const size_t b = p + 1, e = target.find('&', b), eq = target.find('=', b);
+        const size_t end = e == std::string::npos ? target.size() : e;
+        if (eq != std::string::npos && eq < end && target.compare(b, eq - b, key) == 0) { out = target.substr(eq + 1, end - eq - 1); return true; }
+        p = e;
+    }
+    return false;
+}
+
+// A RIFF / WAVE body -> mono float samples.  Taken: `fmt ` tag 1 (PCM) with 16 bits (x / 32768.0f) or tag 3 (IEEE float) with 32 bits, or tag 0xFFFE
+// (extensible) whose sub-format is one of those two; one channel.  Chunks other than `fmt ` and `data` are skipped (an odd size is followed by a pad byte);
+// the first `data` chunk is the recording.  Refused with a message: no RIFF / WAVE header, a missing `fmt ` or `data` chunk, a `fmt ` chunk cut short, a
+// `data` chunk longer than the body, an empty `data` chunk, more than one channel, any other format.  Nothing is read beyond body.size().
+inline bool parse_wav(const std::string & body, std::vector<float> & pcm, int & rate, std::string & err) {
+    const size_t size = body.size();
+    const unsigned char * d = reinterpret_cast<const unsigned char *>(body.data());
+    auto u16 = [&](size_t p) { return (uint32_t) d[p] | ((uint32_t) d[p + 1] << 8); };
+    auto u32 = [&](size_t p) { return (uint32_t) d[p] | ((uint32_t) d[p + 1] << 8) | ((uint32_t) d[p + 2] << 16) | ((uint32_t) d[p + 3] << 24); };
+    pcm.clear(); rate = 0;
+    if (size < 12 || memcmp(d, "RIFF", 4) != 0 || memcmp(d + 8, "WAVE", 4) != 0) { err = "not a RIFF/WAVE file"; return false; }
+    bool have_fmt = false, have_data = false;
+    uint32_t tag = 0, channels = 0, bits = 0, srate = 0;
+    size_t data_at = 0, data_bytes = 0;
+    for (size_t pos = 12; pos + 8 <= size && !(have_fmt && have_data);) {
+        const size_t at = pos + 8, sz = u32(pos + 4);
+        if (memcmp(d + pos, "fmt ", 4) == 0 && !have_fmt) {
+            if (sz < 16 || sz > size - at) { err = "the fmt chunk is cut short"; return false; }
+            tag = u16(at); channels = u16(at + 2); srate = u32(at + 4); bits = u16(at + 14);
+            if (tag == 0xFFFE) {
+                static const unsigned char guid_tail[14] = {0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71};
+                if (sz < 40 || u16(at + 16) < 22 || memcmp(d + at + 26, guid_tail, 14) != 0) { err = "unsupported extensible format"; return false; }
+                tag = u16(at + 24);
+            }
+            have_fmt = true;
+        } else if (memcmp(d + pos, "data", 4) == 0 && !have_data) {
+            if (sz > size - at) { err = "the data chunk is longer than the body"; return false; }
+            data_at = at; data_bytes = sz; have_data = true;
+        }
+        if (sz > size - at) break;                              // an unknown chunk that runs past the body: nothing behind it
+        pos = at + sz + (sz & 1);
+    }
+    if (!have_fmt) { err = "no fmt chunk"; return false; }
+    if (!have_data) { err = "no data chunk"; return false; }
+    if (channels != 1) { err = "only mono recordings are taken"; return false; }
+    if (!((tag == 1 && bits == 16) || (tag == 3 && bits == 32))) { err = "only 16-bit PCM and 32-bit float samples are taken"; return false; }
+    if (srate == 0 || srate > 768000) { err = "bad sample rate"; return false; }
+    const size_t n = data_bytes / (bits / 8);
+    if (n == 0) { err = "the data chunk is empty"; return false; }
+    pcm.resize(n);
+    if (tag == 1) for (size_t i = 0; i < n; i++) pcm[i] = (float) (int16_t) (uint16_t) u16(data_at + 2 * i) / 32768.0f;
+    else memcpy(pcm.data(), d + data_at, n * 4);
+    rate = (int) srate;
+    return true;
+}
+
+// the same over a table whose entries are shared (a server that replaces voices while requests are in flight): *out keeps the voice alive
+inline int request_voice(const std::string & js, const std::map<std::string, std::shared_ptr<const VoiceFile>> & table, std::shared_ptr<const VoiceFile> * out) {
+    out->reset();
+    if (js.find("\"voice\"") == std::string::npos) return 0;
+    std::string name;
+    if (!json_string(js, "voice", name)) return -1;
+    const auto it = table.find(name);
+    if (it == table.end()) return -1;
+    *out = it->second;
     return 1;
 }
 

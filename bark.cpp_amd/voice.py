@@ -108,3 +108,10 @@ def from_audio(ctx, pcm, semantic=None) -> VoicePrompt:
         semantic = ctx.semantic_encode(resample_24k_to_16k(pcm))
     codes = ctx.codec_encode(pcm, 8)                  # [8][T]
     return VoicePrompt(semantic, codes[:2].T, codes[:8].T)
+
+
+def from_audio_native(ctx, pcm) -> VoicePrompt:
+    """The same voice prompt made by ONE native call (ctx.voice_from_audio, bark_hip_voice_from_audio): the resampler runs on the device in f32 under rule
+    C13r instead of resample_24k_to_16k above, so the semantic ids may differ from from_audio's on undecided frames; a recording longer than 20 s is used
+    from its last 480 000 samples on.  ValueError where the call refuses."""
+    return VoicePrompt(*ctx.voice_from_audio(pcm))

@@ -125,6 +125,33 @@ BARK_API int bark_hip_semantic_head(struct bark_context * bctx, const float * fe
 /* Time on the context's stream between the first and the last kernel of its last bark_hip_semantic_encode call, in microseconds (hipEvents); < 0: no call yet. */
 BARK_API double bark_hip_semantic_encode_device_us(struct bark_context * bctx);
 
+/* Voice prompts from a recording (rule C13r): the 24 kHz -> 16 kHz resampler between a recording and the semantic encoder, and one call
+ * that makes all three streams of a voice prompt.
+ * Resampler: ratio 2 / 3, output m at input time 1.5 m, Hann-windowed sinc (cut-off 0.99 of the new Nyquist frequency, 6 zero crossings on either side), two
+ * phases of 22 taps, f32, one fmaf chain per output in ascending tap order, samples outside the recording are zero - the filter of voice.resample_24k_to_16k
+ * (bark.cpp_amd/voice.py, float64 in numpy's own summation order) under a stated order; the two agree within a few f32 roundings per output, not bit for bit.
+ * bark_hip_resample_taps: the committed table, out[22 phase + (j + 10)] = the tap of x[floor(1.5 m) + j], j = -10 .. 11; returns 44.
+ * bark_hip_resample_24k_to_16k: n samples -> n_out = (2 n + 2) / 3 samples; returns n_out, or -1: n < 1, n > 1 310 720 (4096 codec frames), a sample that
+ * is not finite, capacity < n_out.  Needs neither encoder. */
+BARK_API int bark_hip_resample_taps(float * out44);
+BARK_API int bark_hip_resample_24k_to_16k(struct bark_context * bctx, const float * pcm24k, int n, float * out16k, int capacity);
+/* A recording longer than this (20 s) is used from its LAST 480 000 samples on: every stage reads the end of its history stream, and the limits of both
+ * encoders (1024 HuBERT frames, 4096 codec frames) hold by construction. */
+#define BARK_HIP_VOICE_AUDIO_MAX_SAMPLES 480000
+/* pcm24k: n_samples floats, 24 kHz mono -> semantic ids [*n_semantic] (the used samples through the resampler, then bark_hip_semantic_encode), fine rows
+ * [*n_frames][8] (bark_hip_codec_encode with 8 codebooks, time-major) and coarse rows [*n_frames][2] (their first two codebooks); with n the used sample
+ * count, *n_semantic = ((2 n + 2) / 3 - 400) / 320 + 1 and *n_frames = ceil(n / 320).  The result has passed the checks of bark_hip_set_voice_prompt.
+ * Returns 0, or -1 with a message: no semantic encoder loaded, no codec encoder in the file, n_samples < 599 (fewer than 400 samples at 16 kHz), a sample
+ * anywhere in the recording that is not finite or whose f16 image is not, semantic_capacity < *n_semantic or capacity_rows < *n_frames, or a result
+ * bark_hip_set_voice_prompt would refuse (a recording too short to leave a history; an id of a token head with more classes than the model's semantic
+ * vocabulary).  The context stays usable.  The semantic ids may differ from voice.from_audio's on undecided frames: the two resamplers differ in the last bits. */
+BARK_API int bark_hip_voice_from_audio(struct bark_context * bctx, const float * pcm24k, int n_samples, int32_t * semantic, int semantic_capacity,
+                                       int32_t * coarse_Tx2, int32_t * fine_Tx8, int capacity_rows, int32_t * n_semantic, int32_t * n_frames);
+/* bark_hip_voice_from_audio, then bark_hip_set_voice_prompt with the result; on -1 the context keeps the voice it had. */
+BARK_API int bark_hip_set_voice_from_audio(struct bark_context * bctx, const float * pcm24k, int n_samples);
+/* Device time (us) of ONE resampler launch over n samples, averaged over `iters` launches (hipEvents on the context's stream).  Returns < 0 on error. */
+BARK_API double bark_hip_time_resample(struct bark_context * bctx, int n, int iters);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);
