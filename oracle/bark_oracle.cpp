@@ -483,11 +483,13 @@ struct Numerics {
     int codec_mfma = 1;
 };
 
+struct Hubert;
 struct Oracle {
     const uint8_t * map = nullptr; size_t map_size = 0;
     std::map<std::string, int32_t> token_to_id;
     Gpt sem, coarse, fine;
     Codec codec;
+    Hubert * hub = nullptr;                 // semantic encoder, loaded on request (orc_load_semantic_encoder); freed by orc_close
     Numerics num;
     std::vector<uint16_t> gelu_table;
     std::mt19937 rng;
@@ -1511,6 +1513,36 @@ static std::vector<float> convtr1d(const Oracle & o, const ConvT & cv, const std
     return y;
 }
 
+// ---- near-midpoint census of the canonical transcendentals -------------------------------------------------------------------------------------
+// Every canonical transcendental here (LSTM gates, erf GELU) is a double-precision libm value rounded to f32 once.  The device's libm may differ from the
+// host's in the last place of the DOUBLE, which changes the f32 only when the double lies next to the midpoint of two floats.  near_mid counts the values
+// whose double result lies within 8 double-ulps of such a midpoint since the last reset: an input whose count is zero along its whole path is decidable
+// bit for bit whatever libm either side links (tests/test_oracle_semantic_encoder.py holds every input of the bit-exact GPU tests to a count of zero).
+static int64_t g_near_mid = 0;
+static inline bool near_f32_midpoint(double r) {
+    if (!std::isfinite(r)) return false;
+    const float f = (float) r;
+    if (!std::isfinite(f)) return false;
+    float lo, hi;
+    if ((double) f <= r) { lo = f; hi = nextafterf(f, INFINITY); } else { hi = f; lo = nextafterf(f, -INFINITY); }
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return false;
+    const double mid = 0.5 * ((double) lo + (double) hi);       // exact
+    const double a = fabs(r);
+    const double ulp = nextafter(a, INFINITY) - a;
+    return fabs(r - mid) <= 8.0 * ulp;
+}
+static inline float round_counted(double r) {
+    if (near_f32_midpoint(r)) {
+        #pragma omp atomic
+        g_near_mid++;
+    }
+    return (float) r;
+}
+static inline float sigmoid_canon(float x) { return 1.f / (1.f + round_counted(exp((double) (-x)))); }
+static inline float tanh_canon(float x) { return round_counted(tanh((double) x)); }
+// exact (erf) GELU formed in double precision and rounded once (codec_kernels.hip: gelu_erf_canon)
+static inline float gelu_erf_canon(float x) { return round_counted(0.5 * (double) x * (1.0 + erf((double) x * 0.70710678118654752440))); }
+
 // one LSTM layer over [D][T] (modeling_encodec.py:236-249; PyTorch gate order i,f,g,o)
 static std::vector<float> lstm_layer(const Oracle & o, const Lstm & L, const std::vector<float> & x, int D, int T, int nth) {
     std::vector<float> hs((size_t) D * T), h(D, 0.f), c(D, 0.f), xt(D), hr(D), gi(4 * D), gh(4 * D);
@@ -1521,12 +1553,12 @@ static std::vector<float> lstm_layer(const Oracle & o, const Lstm & L, const std
         gemm_w(const_cast<Oracle &>(o), L.w_hh, hr.data(), D, gh.data(), 4 * D, 4 * D, 1, D, nth);
         for (int d = 0; d < D; d++) {
             auto gate = [&](int g) { return (gi[g * D + d] + L.b_ih[g * D + d]) + (gh[g * D + d] + L.b_hh[g * D + d]); };
-            const float i_t = 1.f / (1.f + (float) exp((double) (-gate(0))));
-            const float f_t = 1.f / (1.f + (float) exp((double) (-gate(1))));
-            const float g_t = (float) tanh((double) gate(2));
-            const float o_t = 1.f / (1.f + (float) exp((double) (-gate(3))));
+            const float i_t = sigmoid_canon(gate(0));
+            const float f_t = sigmoid_canon(gate(1));
+            const float g_t = tanh_canon(gate(2));
+            const float o_t = sigmoid_canon(gate(3));
             c[d] = f_t * c[d] + i_t * g_t;
-            h[d] = o_t * (float) tanh((double) c[d]);
+            h[d] = o_t * tanh_canon(c[d]);
             hs[(size_t) d * T + t] = h[d];
         }
     }
@@ -1659,6 +1691,340 @@ static bool codec_encode(Oracle & o, const float * pcm, int n, int n_q, std::vec
     return rvq_encode(o.codec, zt.data(), T, n_q, codes.data());
 }
 
+// ------------------------------------------------------------------------------------
+// semantic encoder (rule C12h): HuBERT's feature encoder, projection, positional convolution and first `output_layer` post-norm layers,
+// then the token head - the restatement of engine_semantic_encode / engine_semantic_head (bark.cpp_amd/csrc/engine_codec.hip), kernel by kernel, in the order
+// each kernel's comment states.  File format: tools/convert_hubert.py (read as tests/semantic_encoder_ref.py::load documents it).  Activations are
+// time-major [row][channel], as in the engine.
+// ------------------------------------------------------------------------------------
+struct HubLayer {
+    CanonW qkv_w, o_w, fc1_w, fc2_w;
+    std::vector<float> qkv_b, o_b, fc1_b, fc2_b, ln1_g, ln1_b, ln2_g, ln2_b;
+};
+struct Hubert {
+    int C = 0, H = 0, n_head = 0, F = 0, n_layer_stored = 0, output_layer = 0, Kp = 0, G = 0, D = 0, n_classes = 0, ftype = 0;
+    std::vector<uint8_t> file;                                   // the tensors' bytes (CanonW::raw points into it)
+    std::vector<float> conv0_w, gn_g, gn_b;                      // conv0_w [C][k0]
+    int k0 = 0;
+    Conv conv[6];                                                // valid, no bias; w [cout][cin][k]
+    int stride[6] = {2, 2, 2, 2, 2, 2};
+    std::vector<float> fp_ln_g, fp_ln_b, fp_b; CanonW fp_w;
+    std::vector<uint16_t> pos_bits; std::vector<CanonW> pos_wm;  // per group [Hg][k * Hg + ci] f16
+    std::vector<float> pos_b, enc_ln_g, enc_ln_b;
+    std::vector<HubLayer> layers;
+    Lstm lstm[2]; CanonW out_w; std::vector<float> out_b;
+    std::vector<uint16_t> gelu_lut;                              // f16(erf GELU(h)) for every f16 h, built as engine_load.hip builds it
+    // what the last run left: taps 0..5 and the ids
+    std::vector<float> tap[6]; std::vector<int32_t> ids; int tap_rows[6] = {0, 0, 0, 0, 0, 0};
+};
+
+static Hubert * load_hubert(const char * path) {
+    FILE * f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "oracle: cannot open %s\n", path); return nullptr; }
+    std::unique_ptr<Hubert> hb(new Hubert());
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    hb->file.resize((size_t) std::max(sz, 0L));
+    const bool read_ok = sz >= 48 && fread(hb->file.data(), 1, (size_t) sz, f) == (size_t) sz;
+    fclose(f);
+    if (!read_ok) { fprintf(stderr, "oracle: %s is not a semantic encoder file\n", path); return nullptr; }
+    Reader r{hb->file.data(), hb->file.size()};
+    if (r.get<uint32_t>() != 0x68756273) { fprintf(stderr, "oracle: bad semantic encoder magic\n"); return nullptr; }
+    Hubert & h = *hb;
+    h.C = r.get<int32_t>(); h.H = r.get<int32_t>(); h.n_head = r.get<int32_t>(); h.F = r.get<int32_t>(); h.n_layer_stored = r.get<int32_t>();
+    h.output_layer = r.get<int32_t>(); h.Kp = r.get<int32_t>(); h.G = r.get<int32_t>(); h.D = r.get<int32_t>(); h.n_classes = r.get<int32_t>(); h.ftype = r.get<int32_t>();
+    if (h.ftype != 1 || h.C < 8 || h.C % 8 || h.H != 64 * h.n_head || h.G < 1 || h.H % h.G || (h.H / h.G) % 8 || h.output_layer < 1 || h.output_layer > h.n_layer_stored ||
+        h.Kp < 1 || h.D < 1 || h.n_classes < 1) { fprintf(stderr, "oracle: semantic encoder hparams are not restated\n"); return nullptr; }
+    std::map<std::string, Tensor> tens;
+    while (r.ok && r.pos < r.size) {
+        std::string name; Tensor t;
+        if (!read_tensor_record(r, name, t)) return nullptr;
+        tens[name] = t;
+    }
+    bool ok = true;
+    auto vec = [&](const std::string & n, std::vector<float> & out, int64_t cnt) {
+        auto it = tens.find(n);
+        if (it == tens.end() || it->second.nelements() != cnt) { fprintf(stderr, "oracle: semantic encoder tensor %s missing or misshaped\n", n.c_str()); ok = false; return; }
+        out = to_f32(it->second);
+    };
+    auto mat = [&](const std::string & n, CanonW & out, int64_t in, int64_t outn) {
+        auto it = tens.find(n);
+        if (it == tens.end() || it->second.ttype != 1 || it->second.ne[0] != in || it->second.ne[1] != outn) { fprintf(stderr, "oracle: semantic encoder tensor %s missing or misshaped\n", n.c_str()); ok = false; return; }
+        out.build(it->second.data, true, (int) outn, (int) in);
+    };
+    static const int kKernel[7] = {10, 3, 3, 3, 3, 2, 2};
+    const int C = h.C, H = h.H, F = h.F, D = h.D, Hg = H / h.G;
+    h.k0 = kKernel[0];
+    vec("conv0.weight", h.conv0_w, (int64_t) C * h.k0); vec("conv0.norm.weight", h.gn_g, C); vec("conv0.norm.bias", h.gn_b, C);
+    for (int i = 1; i < 7 && ok; i++) {
+        Conv & cv = h.conv[i - 1];
+        cv.k = kKernel[i]; cv.cin = C; cv.cout = C;
+        vec("conv" + std::to_string(i) + ".weight", cv.w, (int64_t) C * C * cv.k);
+    }
+    vec("proj.ln.weight", h.fp_ln_g, C); vec("proj.ln.bias", h.fp_ln_b, C); mat("proj.weight", h.fp_w, C, H); vec("proj.bias", h.fp_b, H);
+    {
+        std::vector<float> pw;
+        vec("pos.weight", pw, (int64_t) H * Hg * h.Kp); vec("pos.bias", h.pos_b, H);
+        if (ok) {
+            const int kd = h.Kp * Hg;
+            h.pos_bits.resize((size_t) H * kd);
+            for (int co = 0; co < H; co++) for (int ci = 0; ci < Hg; ci++) for (int k = 0; k < h.Kp; k++)
+                h.pos_bits[(size_t) co * kd + (size_t) k * Hg + ci] = f2h(pw[((size_t) co * Hg + ci) * h.Kp + k]);
+            h.pos_wm.resize((size_t) h.G);
+            for (int g = 0; g < h.G; g++) { CanonW & W = h.pos_wm[(size_t) g]; W.M = Hg; W.K = kd; W.f16 = true; W.mfma = true; W.raw = (const uint8_t *) (h.pos_bits.data() + (size_t) g * Hg * kd); }
+        }
+    }
+    vec("enc.ln.weight", h.enc_ln_g, H); vec("enc.ln.bias", h.enc_ln_b, H);
+    h.layers.resize((size_t) h.output_layer);
+    for (int l = 0; l < h.output_layer && ok; l++) {
+        const std::string p = "layers." + std::to_string(l) + ".";
+        HubLayer & L = h.layers[(size_t) l];
+        mat(p + "attn.qkv.weight", L.qkv_w, H, 3 * H); vec(p + "attn.qkv.bias", L.qkv_b, 3 * H);
+        mat(p + "attn.out.weight", L.o_w, H, H); vec(p + "attn.out.bias", L.o_b, H);
+        vec(p + "ln1.weight", L.ln1_g, H); vec(p + "ln1.bias", L.ln1_b, H);
+        mat(p + "fc1.weight", L.fc1_w, H, F); vec(p + "fc1.bias", L.fc1_b, F);
+        mat(p + "fc2.weight", L.fc2_w, F, H); vec(p + "fc2.bias", L.fc2_b, H);
+        vec(p + "ln2.weight", L.ln2_g, H); vec(p + "ln2.bias", L.ln2_b, H);
+    }
+    for (int l = 0; l < 2 && ok; l++) {
+        const std::string s = std::to_string(l);
+        mat("head.lstm.weight_ih_l" + s, h.lstm[l].w_ih, l ? D : H, 4 * D); mat("head.lstm.weight_hh_l" + s, h.lstm[l].w_hh, D, 4 * D);
+        vec("head.lstm.bias_ih_l" + s, h.lstm[l].b_ih, 4 * D); vec("head.lstm.bias_hh_l" + s, h.lstm[l].b_hh, 4 * D);
+    }
+    mat("head.out.weight", h.out_w, D, h.n_classes); vec("head.out.bias", h.out_b, h.n_classes);
+    if (!ok) return nullptr;
+    // the FFN's erf-GELU table: entry i = f16(gelu_erf(f32(h_i))) with the host's erf, as engine_load.hip builds it (a table, so no census)
+    h.gelu_lut.resize(65536);
+    for (uint32_t i = 0; i < 65536; i++) {
+        const float x = h2f((uint16_t) i);
+        h.gelu_lut[i] = f2h((float) (0.5 * (double) x * (1.0 + erf((double) x * 0.70710678118654752440))));
+    }
+    return hb.release();
+}
+
+// rows behind every stage of the feature encoder: rows[0] samples, rows[i + 1] behind convolution i (engine_codec.hip: hub_stage_rows)
+static void hub_stage_rows(const Hubert & h, int n, int rows[8]) {
+    rows[0] = n;
+    rows[1] = (n - h.k0) / 5 + 1;
+    for (int i = 0; i < 6; i++) rows[i + 2] = (rows[i + 1] - h.conv[i].k) / h.stride[i] + 1;
+}
+
+// Convolution 0 with its norm over time (hub_conv0_*_kernel): x = the f16 image of the samples; y[t][c] = one fmaf chain over k ascending from +0; sum and sum
+// of squares in double, rows ascending inside a chunk of 1024 rows, then chunks ascending; mean = S / T0, var = SS / T0 - mean^2 clamped at 0, the mean rounded
+// to f32, rstd = (float) (1 / sqrt(var + 1e-5)); ((y - mean) rstd) g + b with one rounding per operation; erf GELU.  -> [T0][C] f32 (its f16 image feeds conv 1)
+static std::vector<float> hub_conv0(const Hubert & h, const std::vector<float> & xh, int T0, int nth) {
+    const int C = h.C, K = h.k0;
+    std::vector<float> out((size_t) T0 * C);
+    #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1)
+    for (int c = 0; c < C; c++) {
+        const float * w = h.conv0_w.data() + (size_t) c * K;
+        auto dot = [&](int t) { float acc = 0.0f; for (int k = 0; k < K; k++) acc = fmaf(w[k], xh[(size_t) t * 5 + k], acc); return acc; };
+        double s = 0.0, ss = 0.0;
+        for (int t0 = 0; t0 < T0; t0 += 1024) {
+            double cs = 0.0, css = 0.0;
+            for (int t = t0; t < std::min(T0, t0 + 1024); t++) { const double y = (double) dot(t); cs = cs + y; css = css + y * y; }
+            s = s + cs; ss = ss + css;
+        }
+        const double mean = s / (double) T0;
+        double var = ss / (double) T0 - mean * mean;
+        if (var < 0.0) var = 0.0;
+        const float meanf = (float) mean, rstd = (float) (1.0 / sqrt(var + 1e-5));
+        for (int t = 0; t < T0; t++) {
+            float v = (dot(t) - meanf) * rstd;
+            v = v * h.gn_g[c];
+            v = v + h.gn_b[c];
+            out[(size_t) t * C + c] = gelu_erf_canon(v);
+        }
+    }
+    return out;
+}
+
+// One valid strided convolution (conv_down_*_kernel with valid = 1): tap k of output row t is input row t stride + k, no reflection, no bias.  x [rows][cin]
+// holds f16 values.  C9m (gemm_mfma over kd = k cin + ci) or, with codec_mfma off - BARK_HIP_CROSSCHECK bit 1024 sends these launches to
+// conv_down_chain_kernel too - C9: one fmaf chain per output in (ci, k) order.  -> erf GELU of the sum, [rows_out][cout] f32
+static std::vector<float> hub_conv_valid(const Oracle & o, const Conv & cv, int stride, const std::vector<float> & x, int rows_out, int nth) {
+    const int kd = cv.k * cv.cin;
+    std::vector<float> Y((size_t) rows_out * cv.cout);
+    if (conv_uses_mfma(o, cv.cin)) {
+        if (cv.wm.empty()) {
+            cv.wm_bits.resize((size_t) cv.cout * kd);
+            for (int co = 0; co < cv.cout; co++) for (int ci = 0; ci < cv.cin; ci++) for (int k = 0; k < cv.k; k++)
+                cv.wm_bits[(size_t) co * kd + (size_t) k * cv.cin + ci] = f2h(cv.w[((size_t) co * cv.cin + ci) * cv.k + k]);
+            cv.wm.resize(1);
+            CanonW & W = cv.wm[0]; W.M = cv.cout; W.K = kd; W.f16 = true; W.mfma = true; W.raw = (const uint8_t *) cv.wm_bits.data();
+        }
+        if (stride * cv.cin == 0) return Y;
+        // row t of the operand matrix = input rows t stride .. t stride + k - 1 back to back: a window of the input itself
+        gemm_mfma(cv.wm[0], x.data(), (size_t) stride * cv.cin, Y.data(), cv.cout, cv.cout, rows_out, kd, nth);
+    } else {
+        #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1)
+        for (int t = 0; t < rows_out; t++) for (int co = 0; co < cv.cout; co++) {
+            float acc = 0.0f;
+            for (int ci = 0; ci < cv.cin; ci++) {
+                const float * wr = cv.w.data() + ((size_t) co * cv.cin + ci) * cv.k;
+                for (int k = 0; k < cv.k; k++) acc = fmaf(wr[k], x[((size_t) t * stride + k) * cv.cin + ci], acc);
+            }
+            Y[(size_t) t * cv.cout + co] = acc;
+        }
+    }
+    #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1)
+    for (size_t i = 0; i < Y.size(); i++) Y[i] = gelu_erf_canon(Y[i]);
+    return Y;
+}
+
+// add_ln_rows_kernel: v = x + y (y may be absent), LayerNorm(v) with layer_norm_row's arithmetic -> f32 rows (the caller takes their f16 image where it is consumed)
+static void hub_add_ln_rows(const float * x, const float * y, int N, int E, const std::vector<float> & g, const std::vector<float> & b, float * out, int nth) {
+    #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1 && N >= 16)
+    for (int i = 0; i < N; i++) {
+        std::vector<float> v((size_t) E);
+        for (int e = 0; e < E; e++) v[(size_t) e] = y ? x[(size_t) i * E + e] + y[(size_t) i * E + e] : x[(size_t) i * E + e];
+        layer_norm_row(v.data(), out + (size_t) i * E, E, g.data(), b.data());
+    }
+}
+
+// Grouped positional convolution (pos_conv_mfma_kernel): per group, C9m over kd = k Hg + ci of w[g Hg + co][ci][k] x[t + k - Kp / 2][g Hg + ci], rows outside the
+// recording zero; the group image's padding (co32 rows, kd16 columns) is zeros: all-zero groups leave the accumulator alone.  Epilogue: + bias, erf GELU in f32.
+// T output frames (for even Kp the convolution's last frame is dropped).  xh [T][H] f16 values -> [T][H] f32
+static std::vector<float> hub_pos_conv(const Hubert & h, const std::vector<float> & xh, int T, int nth) {
+    const int H = h.H, G = h.G, Hg = H / G, Kp = h.Kp, pad = Kp / 2, kd = Kp * Hg;
+    std::vector<float> out((size_t) T * H), X((size_t) T * kd), Y((size_t) T * Hg);
+    for (int g = 0; g < G; g++) {
+        #pragma omp parallel for schedule(static) num_threads(nth) if (nth > 1)
+        for (int t = 0; t < T; t++) for (int k = 0; k < Kp; k++) {
+            const int j = t + k - pad;
+            for (int ci = 0; ci < Hg; ci++) X[(size_t) t * kd + (size_t) k * Hg + ci] = (j >= 0 && j < T) ? xh[(size_t) j * H + g * Hg + ci] : 0.0f;
+        }
+        gemm_mfma(h.pos_wm[(size_t) g], X.data(), kd, Y.data(), Hg, Hg, T, kd, nth);
+        for (int t = 0; t < T; t++) for (int co = 0; co < Hg; co++) {
+            const float v = Y[(size_t) t * Hg + co] + h.pos_b[(size_t) g * Hg + co];
+            out[(size_t) t * H + g * Hg + co] = gelu_erf_canon(v);
+        }
+    }
+    return out;
+}
+
+// the FFN's epilogue (device_utils.h: gelu_lut_apply): the table over the f16 image of the pre-activation, 0 at and below -10, the f16 image itself from 10 on
+static inline float hub_gelu_lut(const Hubert & h, float v) {
+    if (v <= -10.0f) return 0.0f;
+    if (v >= 10.0f) return round_h(v);
+    return h2f(h.gelu_lut[f2h(v)]);
+}
+
+// One LSTM layer of the token head over time-major f16-valued rows x [T][K_in] (run_lstm_pair / lstm_pair_step_kernel): gi = W_ih x_t as C1 dots without bias,
+// gh = W_hh f16(h_{t-1}) likewise, pre = (gi + b_ih) + (gh + b_hh), gates in double rounded once, c in f32, h kept as f32 (out) and consumed as its f16 image.
+static std::vector<float> hub_lstm_rows(Oracle & o, const Lstm & L, const std::vector<float> & x, int K_in, int D, int T, int nth) {
+    std::vector<float> gi((size_t) T * 4 * D), hs((size_t) T * D), c((size_t) D, 0.f), hr((size_t) D, 0.f), gh((size_t) 4 * D);
+    gemm_w(o, L.w_ih, x.data(), K_in, gi.data(), 4 * D, 4 * D, T, K_in, nth);
+    for (int t = 0; t < T; t++) {
+        gemm_w(o, L.w_hh, hr.data(), D, gh.data(), 4 * D, 4 * D, 1, D, nth);
+        const float * g0 = gi.data() + (size_t) t * 4 * D;
+        for (int d = 0; d < D; d++) {
+            auto gate = [&](int g) { return (g0[g * D + d] + L.b_ih[g * D + d]) + (gh[g * D + d] + L.b_hh[g * D + d]); };
+            const float i_t = sigmoid_canon(gate(0));
+            const float f_t = sigmoid_canon(gate(1));
+            const float g_t = tanh_canon(gate(2));
+            const float o_t = sigmoid_canon(gate(3));
+            c[d] = f_t * c[d] + i_t * g_t;
+            const float hn = o_t * tanh_canon(c[d]);
+            hs[(size_t) t * D + d] = hn;
+            hr[d] = round_h(hn);
+        }
+    }
+    return hs;
+}
+
+// the per-row pick (argmax_rows_kernel): s_i = l_i / 0.7f, the lowest i whose s_i - max s is >= -2^-25 - the row argmax with the lowest id on ties (two logits
+// whose quotients round to the same float tie as well)
+static int32_t hub_pick_row(const float * l, int n) {
+    float mx = -INFINITY;
+    for (int i = 0; i < n; i++) mx = std::max(mx, l[i] / 0.7f);
+    for (int i = 0; i < n; i++) if (l[i] / 0.7f - mx >= -2.98023223876953125e-08f) return i;
+    return 0;
+}
+
+// token head on f16-valued rows xh [T][H] -> logits [T][n_classes], ids [T]
+static void hub_head(Oracle & o, const Hubert & h, const std::vector<float> & xh, int T, std::vector<float> & logits, std::vector<int32_t> & ids, int nth) {
+    std::vector<float> y = hub_lstm_rows(o, h.lstm[0], xh, h.H, h.D, T, nth);
+    for (float & v : y) v = round_h(v);
+    y = hub_lstm_rows(o, h.lstm[1], y, h.D, h.D, T, nth);
+    for (float & v : y) v = round_h(v);
+    logits.assign((size_t) T * h.n_classes, 0.f);
+    gemm_w(o, h.out_w, y.data(), h.D, logits.data(), h.n_classes, h.n_classes, T, h.D, nth);
+    add_bias_rows(logits.data(), h.n_classes, T, h.n_classes, h.out_b, nth);
+    ids.resize((size_t) T);
+    for (int t = 0; t < T; t++) ids[(size_t) t] = hub_pick_row(logits.data() + (size_t) t * h.n_classes, h.n_classes);
+}
+
+static bool hub_pcm_ok(const float * pcm, int n) {
+    for (int i = 0; i < n; i++) if (!std::isfinite(pcm[i]) || !std::isfinite(round_h(pcm[i]))) return false;
+    return true;
+}
+
+// engine_semantic_head: f32 rows [T][H] -> their f16 image -> head
+static bool semantic_head(Oracle & o, Hubert & h, const float * feats, int T, std::vector<float> & logits, std::vector<int32_t> & ids, int nth) {
+    if (!feats || T < 1 || T > 1024 || !hub_pcm_ok(feats, T * h.H)) return false;
+    g_near_mid = 0;
+    std::vector<float> xh(feats, feats + (size_t) T * h.H);
+    for (float & v : xh) v = round_h(v);
+    hub_head(o, h, xh, T, logits, ids, nth);
+    return true;
+}
+
+// engine_semantic_encode: taps 0..5 (as bark_hip_semantic_encode_tap numbers them) and the ids stay in h.tap / h.ids; keep_tap0 = false drops tap 0 (65 615 x C
+// values at the longest input)
+static bool semantic_encode(Oracle & o, Hubert & h, const float * pcm, int n, bool keep_tap0, int nth) {
+    if (!pcm || n < 400 || n > 1023 * 320 + 400 + 319 || !hub_pcm_ok(pcm, n)) return false;
+    g_near_mid = 0;
+    int rows[8];
+    hub_stage_rows(h, n, rows);
+    const int T = rows[7], C = h.C, H = h.H, F = h.F;
+    if (T != (n - 400) / 320 + 1 || T < 1 || T > 1024) return false;
+    for (auto & t : h.tap) t.clear();
+    auto rounded = [](std::vector<float> v) { for (float & e : v) e = round_h(e); return v; };
+    // feature encoder
+    std::vector<float> x = hub_conv0(h, rounded(std::vector<float>(pcm, pcm + n)), rows[1], nth);
+    if (keep_tap0) h.tap[0] = x;
+    h.tap_rows[0] = rows[1];
+    for (int i = 0; i < 6; i++) x = hub_conv_valid(o, h.conv[i], h.stride[i], rounded(std::move(x)), rows[i + 2], nth);
+    h.tap[1] = x; h.tap_rows[1] = T;                                          // [T][C] f32: the last convolution feeds a LayerNorm
+    // projection
+    std::vector<float> xn((size_t) T * C), proj((size_t) T * H);
+    hub_add_ln_rows(x.data(), nullptr, T, C, h.fp_ln_g, h.fp_ln_b, xn.data(), nth);
+    xn = rounded(std::move(xn));
+    gemm_w(o, h.fp_w, xn.data(), C, proj.data(), H, H, T, C, nth);
+    add_bias_rows(proj.data(), H, T, H, h.fp_b, nth);
+    h.tap[2] = proj; h.tap_rows[2] = T;
+    // positional convolution, residual, encoder.layer_norm
+    std::vector<float> pc = hub_pos_conv(h, rounded(proj), T, nth);
+    std::vector<float> cur((size_t) T * H), tmp((size_t) T * H), qkv((size_t) T * 3 * H), kc((size_t) T * H), vc((size_t) T * H), att((size_t) T * H), ff((size_t) T * F);
+    hub_add_ln_rows(proj.data(), pc.data(), T, H, h.enc_ln_g, h.enc_ln_b, cur.data(), nth);
+    h.tap[3] = cur; h.tap_rows[3] = T;
+    for (const HubLayer & L : h.layers) {
+        std::vector<float> xh = rounded(cur);
+        gemm_w(o, L.qkv_w, xh.data(), H, qkv.data(), 3 * H, 3 * H, T, H, nth);
+        add_bias_rows(qkv.data(), 3 * H, T, 3 * H, L.qkv_b, nth);
+        for (int i = 0; i < T; i++) {
+            memcpy(kc.data() + (size_t) i * H, qkv.data() + (size_t) i * 3 * H + H, (size_t) H * 4);
+            memcpy(vc.data() + (size_t) i * H, qkv.data() + (size_t) i * 3 * H + 2 * H, (size_t) H * 4);
+        }
+        attention(o, qkv.data(), 3 * H, kc.data(), vc.data(), att.data(), T, T, 0, false, H, h.n_head, nth);
+        att = rounded(std::move(att));
+        gemm_w(o, L.o_w, att.data(), H, tmp.data(), H, H, T, H, nth);
+        add_bias_rows(tmp.data(), H, T, H, L.o_b, nth);
+        hub_add_ln_rows(cur.data(), tmp.data(), T, H, L.ln1_g, L.ln1_b, cur.data(), nth);
+        xh = rounded(cur);
+        gemm_w(o, L.fc1_w, xh.data(), H, ff.data(), F, F, T, H, nth);
+        add_bias_rows(ff.data(), F, T, F, L.fc1_b, nth);
+        for (float & v : ff) v = hub_gelu_lut(h, v);
+        gemm_w(o, L.fc2_w, ff.data(), F, tmp.data(), H, H, T, F, nth);
+        add_bias_rows(tmp.data(), H, T, H, L.fc2_b, nth);
+        hub_add_ln_rows(cur.data(), tmp.data(), T, H, L.ln2_g, L.ln2_b, cur.data(), nth);
+    }
+    h.tap[4] = cur; h.tap_rows[4] = T;
+    hub_head(o, h, rounded(cur), T, h.tap[5], h.ids, nth);
+    h.tap_rows[5] = T;
+    return true;
+}
+
 static Oracle * oracle_open(const char * path) {
     int fd = open(path, O_RDONLY);
     if (fd < 0) { fprintf(stderr, "oracle: cannot open %s\n", path); return nullptr; }
@@ -1693,7 +2059,7 @@ static Oracle * oracle_open(const char * path) {
 extern "C" {
 
 void * orc_open(const char * path) { return oracle_open(path); }
-void   orc_close(void * h) { delete (Oracle *) h; }
+void   orc_close(void * h) { if (h) delete ((Oracle *) h)->hub; delete (Oracle *) h; }
 void   orc_set_numerics(void * h, int act_round_f16, int gelu_mode) { auto * o = (Oracle *) h; o->num.act_round_f16 = act_round_f16; o->num.gelu_mode = gelu_mode; }
 void   orc_set_dot_order(void * h, int dot_order) { ((Oracle *) h)->num.dot_order = dot_order; }      // study modes, see Numerics
 void   orc_set_codec_mfma(void * h, int on) { ((Oracle *) h)->num.codec_mfma = on; }                      // 0: the codec's convolutions as (ci, k) fmaf chains (Numerics::codec_mfma)
@@ -1830,6 +2196,54 @@ int orc_rvq_encode(void * h, const float * latents_TxH, int T, int n_q, int32_t 
     if (!o->codec.enc.present || !latents_TxH || !codes) return -1;
     return rvq_encode(o->codec, latents_TxH, T, n_q, codes) ? T : -1;
 }
+
+// ---- semantic encoder (rule C12h) ----------------------------------------------------------------------------------------------------------------
+int orc_load_semantic_encoder(void * h, const char * path) {
+    Oracle * o = (Oracle *) h;
+    Hubert * hb = load_hubert(path);
+    if (!hb) return -1;
+    delete o->hub; o->hub = hb;
+    return 0;
+}
+int orc_has_semantic_encoder(void * h) { return ((Oracle *) h)->hub ? 1 : 0; }
+// out[11]: C, H, n_head, F, n_layer_stored, output_layer, pos_kernel, pos_groups, D, n_classes, ftype
+int orc_semantic_hparams(void * h, int32_t * out) {
+    const Hubert * b = ((Oracle *) h)->hub;
+    if (!b) return -1;
+    const int32_t v[11] = {b->C, b->H, b->n_head, b->F, b->n_layer_stored, b->output_layer, b->Kp, b->G, b->D, b->n_classes, b->ftype};
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+// one pass: ids [T] out, taps 0..5 kept for orc_semantic_tap (tap 0 only when keep_tap0); returns T or -1
+int orc_semantic_encode(void * h, const float * pcm, int n, int32_t * ids, int keep_tap0, int nth) {
+    Oracle * o = (Oracle *) h;
+    if (!o->hub || !semantic_encode(*o, *o->hub, pcm, n, keep_tap0 != 0, nth)) return -1;
+    if (ids) memcpy(ids, o->hub->ids.data(), o->hub->ids.size() * sizeof(int32_t));
+    return (int) o->hub->ids.size();
+}
+// tap `stage` of the last orc_semantic_encode, [rows][channels]; returns the element count (out == nullptr: the count alone), -1: not there.  *rows: its row count
+int64_t orc_semantic_tap(void * h, int stage, float * out, int64_t capacity, int32_t * rows) {
+    const Hubert * b = ((Oracle *) h)->hub;
+    if (!b || stage < 0 || stage > 5 || b->tap[stage].empty()) return -1;
+    if (rows) *rows = b->tap_rows[stage];
+    if (!out) return (int64_t) b->tap[stage].size();
+    if ((int64_t) b->tap[stage].size() > capacity) return -1;
+    memcpy(out, b->tap[stage].data(), b->tap[stage].size() * sizeof(float));
+    return (int64_t) b->tap[stage].size();
+}
+// token head alone on rows [T][H]: ids [T], logits [T][n_classes] (may be null); returns T or -1
+int orc_semantic_head(void * h, const float * feats, int T, int32_t * ids, float * logits, int nth) {
+    Oracle * o = (Oracle *) h;
+    std::vector<float> lg; std::vector<int32_t> id;
+    if (!o->hub || !ids || !semantic_head(*o, *o->hub, feats, T, lg, id, nth)) return -1;
+    memcpy(ids, id.data(), id.size() * sizeof(int32_t));
+    if (logits) memcpy(logits, lg.data(), lg.size() * sizeof(float));
+    return T;
+}
+// canonical transcendentals (LSTM gates, erf GELU) of the calls since the last reset - every semantic_encode / semantic_head call resets first - whose double
+// result lay within 8 double-ulps of the midpoint of two floats (see near_f32_midpoint)
+int64_t orc_near_midpoints(void) { return g_near_mid; }
+void orc_reset_near_midpoints(void) { g_near_mid = 0; }
 
 struct orc_result {
     int32_t n_semantic, n_frames, n_samples;

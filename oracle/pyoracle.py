@@ -88,6 +88,15 @@ class Oracle:
         lib.orc_codec_encode_tap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
         lib.orc_codec_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         lib.orc_rvq_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.orc_load_semantic_encoder.argtypes = [C.c_void_p, C.c_char_p]
+        lib.orc_has_semantic_encoder.argtypes = [C.c_void_p]
+        lib.orc_semantic_hparams.argtypes = [C.c_void_p, C.c_void_p]
+        lib.orc_semantic_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        lib.orc_semantic_tap.restype = C.c_int64
+        lib.orc_semantic_tap.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.orc_semantic_head.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        lib.orc_near_midpoints.restype = C.c_int64
+        lib.orc_near_midpoints.argtypes = []
         lib.orc_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self.h = lib.orc_open(model_path.encode())
         if not self.h:
@@ -253,6 +262,64 @@ class Oracle:
         if self.lib.orc_rvq_encode(self.h, z.ctypes.data, len(z), n_q, codes.ctypes.data) < 0:
             raise RuntimeError("oracle rvq encode failed")
         return codes
+
+    # -- semantic encoder (rule C12h) --------------------------------------------------
+    def load_semantic_encoder(self, path: str):
+        """A semantic-encoder file (tools/convert_hubert.py) into this oracle; a second load replaces the first."""
+        if self.lib.orc_load_semantic_encoder(self.h, path.encode()) != 0:
+            raise RuntimeError(f"oracle: failed to load the semantic encoder {path}")
+
+    def has_semantic_encoder(self) -> bool:
+        return bool(self.lib.orc_has_semantic_encoder(self.h))
+
+    def semantic_hparams(self) -> dict:
+        out = np.zeros(11, np.int32)
+        if self.lib.orc_semantic_hparams(self.h, out.ctypes.data) != 0:
+            raise RuntimeError("oracle: no semantic encoder loaded")
+        keys = ["C", "H", "n_head", "F", "n_layer_stored", "output_layer", "pos_kernel", "pos_groups", "D", "n_classes", "ftype"]
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def semantic_encode_taps(self, pcm, stages=(0, 1, 2, 3, 4, 5)):
+        """One pass over 16 kHz samples -> ({stage: [rows][channels] f32}, ids [T]); stages as bark_hip_semantic_encode_tap numbers them (0 convolution 0 with
+        its norm, 1 the feature encoder, 2 the projection, 3 hidden_states[0], 4 the last layer run, 5 the head's logits)."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        ids = np.zeros(1024, np.int32)
+        T = self.lib.orc_semantic_encode(self.h, x.ctypes.data, len(x), ids.ctypes.data, int(0 in stages), self.n_threads)
+        if T < 0:
+            raise RuntimeError("oracle semantic encode failed")
+        taps = {}
+        for st in stages:
+            rows = C.c_int32(0)
+            n = self.lib.orc_semantic_tap(self.h, st, None, 0, C.byref(rows))
+            if n < 0:
+                raise RuntimeError(f"oracle semantic encode: no tap {st}")
+            out = np.zeros(n, np.float32)
+            self.lib.orc_semantic_tap(self.h, st, out.ctypes.data, n, None)
+            taps[st] = out.reshape(rows.value, -1)
+        return taps, ids[:T].copy()
+
+    def semantic_encode_tap(self, pcm, stage: int) -> np.ndarray:
+        if not 0 <= stage <= 5:
+            raise RuntimeError("oracle semantic encode: tap stages are 0..5")
+        return self.semantic_encode_taps(pcm, (stage,))[0][stage]
+
+    def semantic_encode(self, pcm) -> np.ndarray:
+        return self.semantic_encode_taps(pcm, ())[1]
+
+    def semantic_head(self, feats):
+        """Token head alone on rows [T][H] -> (ids [T], logits [T][n_classes])."""
+        f = np.ascontiguousarray(feats, dtype=np.float32)
+        assert f.ndim == 2
+        ids = np.zeros(len(f), np.int32)
+        logits = np.zeros((len(f), self.semantic_hparams()["n_classes"]), np.float32)
+        if f.shape[1] != self.semantic_hparams()["H"] or self.lib.orc_semantic_head(self.h, f.ctypes.data, len(f), ids.ctypes.data, logits.ctypes.data, self.n_threads) < 0:
+            raise RuntimeError("oracle semantic head failed")
+        return ids, logits
+
+    def near_midpoints(self) -> int:
+        """Canonical transcendentals (LSTM gates, erf GELU) of the last semantic_encode* / semantic_head call - and of codec LSTM calls since - whose
+        double-precision value lay within 8 double-ulps of the midpoint of two floats: where a device libm may legitimately round to the other float."""
+        return int(self.lib.orc_near_midpoints())
 
     def generate(self, text: str, p: OrcParams) -> dict:
         sem = np.zeros(1024, np.int32)

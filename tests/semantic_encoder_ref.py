@@ -139,3 +139,77 @@ def margins(logits: np.ndarray):
     order = np.argsort(-logits, axis=1, kind="stable")[:, :2]
     rows = np.arange(len(logits))
     return (logits[rows, order[:, 0]] - logits[rows, order[:, 1]]).astype(np.float32), order.astype(np.int32)
+
+
+# ---- inputs of the bit-exact tests against the CPU oracle (tests/test_gpu_semantic_encoder_oracle.py; their conditions: tests/test_oracle_semantic_encoder.py) ----
+# S1: every length is the smallest input that reaches the edge its test names; 2580 samples give 515 / 257 / 128 / 63 / 31 / 15 / 7 rows behind the seven convolutions
+ORACLE_S1 = (400, 719, 720, 2580, 2640, 2960, 5129, 5130, 5200, 5520, 10000, 10320, 10640, 20240, 20560, 20880, 40720, 41040, 41360, 327759, 327760, 328079)
+ORACLE_LONG = 327759                 # from here on tap 0 (65 550 rows and more) is not compared
+ORACLE_S2_N = 5200
+ORACLE_S2_SIGNALS = ("zeros", "half", "alternating")
+ORACLE_S3 = (("alternating09", 328079), ("fixture", 400), ("fixture", 10000), ("fixture", 10320), ("fixture", 10640), ("fixture", 20880))
+ORACLE_S4_MASKS = (512, 1, 1024)     # BARK_HIP_CROSSCHECK: attn_rows_kernel at 1024 frames, gemv_rows_kernel for the products, the convolutions' C9 chains
+ORACLE_S4_LENGTHS = (720, 10640, 327760)
+ORACLE_S5_T = (1, 2, 63, 64, 65, 128, 129, 1024)
+ORACLE_S6 = (16000, 48000)
+# The seed of fixture_signal per (preset, length): 0 unless the oracle's near-midpoint census (Oracle.near_midpoints) of seed 0 is not zero along the input's path
+# - then the first seed whose census is zero, in both convolution orders where S4 runs the input in both.  Held by tests/test_oracle_semantic_encoder.py.
+ORACLE_SEEDS = {("hub_toy", 41040): 1, ("hub_toy", 41360): 1, ("hub_toy", 327759): 1, ("hub_toy", 327760): 2, ("hub_base", 48000): 4}
+ORACLE_HEAD_SEEDS = {}               # the same for the seeded rows of S5, per T
+
+
+def oracle_signal(n: int, kind: str = "fixture", preset: str = "hub_toy") -> np.ndarray:
+    if kind == "fixture":
+        return fixture_signal(n, ORACLE_SEEDS.get((preset, n), 0))
+    if kind == "zeros":
+        return np.zeros(n, np.float32)
+    if kind == "half":
+        return np.full(n, 0.5, np.float32)
+    alt = np.where(np.arange(n) % 2 == 0, 1.0, -1.0).astype(np.float32)
+    if kind == "alternating":
+        return alt
+    if kind == "alternating09":
+        return (np.float32(0.9) * alt).astype(np.float32)
+    raise ValueError(kind)
+
+
+def head_rows(T: int, H: int) -> np.ndarray:
+    return np.random.default_rng([7, T, ORACLE_HEAD_SEEDS.get(T, 0)]).standard_normal((T, H)).astype(np.float32)
+
+
+def tie_pairs(ids: np.ndarray, n_classes: int):
+    """Two (low, high, source) triples for write_tie_hubert from the ids a head picks on some rows: for the most frequent id w1 its neighbour, (w1, w1 + 1, w1) -
+    neighbouring lanes of the pick; for the second most frequent id w2 the class 64 below it, (w2 - 64, w2, w2) - the same lane one trip earlier, so the frames that
+    picked w2 must now answer w2 - 64 - or, for w2 < 64, (w2, w2 + 64, w2).  `source` is the class whose row both receive: the one that is picked."""
+    vals, counts = np.unique(ids, return_counts=True)
+    order = vals[np.argsort(-counts, kind="stable")]
+    w1, w2 = int(order[0]), int(order[1])
+    a = (w1, w1 + 1, w1) if w1 + 1 < n_classes and w1 + 1 != w2 else (w1 - 1, w1, w1)
+    b = (w2 - 64, w2, w2) if w2 >= 64 else (w2, w2 + 64, w2)
+    if len({*a[:2], *b[:2]}) != 4:
+        raise ValueError(f"tie pairs collide: {a} {b}")
+    return a, b
+
+
+def write_tie_hubert(src: str, dst: str, pairs):
+    """Copy of a semantic-encoder file with duplicated classes: for every (low, high, source) of `pairs` row `source` (one of the two) of head.out.weight and
+    its entry of head.out.bias are written to both `low` and `high`, so the two classes have equal logits in every frame (as codec_encoder_ref.write_tie_model
+    duplicates codebook rows)."""
+    data = bytearray(open(src, "rb").read())
+    pos, where = 48, {}
+    while pos < len(data):
+        n_dims, name_len, ttype = struct.unpack_from("<3i", data, pos); pos += 12
+        dims = struct.unpack_from(f"<{n_dims}i", data, pos); pos += 4 * n_dims
+        name = bytes(data[pos:pos + name_len]).decode(); pos += name_len
+        es = 2 if ttype == 1 else 4
+        where[name] = (pos, dims, es)
+        pos += int(np.prod(dims)) * es
+    wpos, wdims, wes = where["head.out.weight"]
+    bpos, _, bes = where["head.out.bias"]
+    D = wdims[0]
+    for low, high, source in pairs:
+        for dstrow in (low, high):
+            data[wpos + dstrow * D * wes:wpos + (dstrow + 1) * D * wes] = data[wpos + source * D * wes:wpos + (source + 1) * D * wes]
+            data[bpos + dstrow * bes:bpos + (dstrow + 1) * bes] = data[bpos + source * bes:bpos + (source + 1) * bes]
+    with open(dst, "wb") as f:
+        f.write(bytes(data))
