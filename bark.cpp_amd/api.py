@@ -101,6 +101,7 @@ EXPORTS = [
     "bark_hip_has_codec_encoder", "bark_hip_codec_encode", "bark_hip_codec_encode_many", "bark_hip_codec_encode_tap", "bark_hip_rvq_encode", "bark_hip_codec_encode_latents", "bark_hip_codec_encode_device_us",
     "bark_hip_load_semantic_encoder", "bark_hip_has_semantic_encoder", "bark_hip_semantic_encode", "bark_hip_semantic_encode_tap", "bark_hip_semantic_head", "bark_hip_semantic_encode_device_us",
     "bark_hip_resample_taps", "bark_hip_resample_24k_to_16k", "bark_hip_voice_from_audio", "bark_hip_set_voice_from_audio", "bark_hip_time_resample",
+    "bark_hip_batch_lock_steps",
 ]
 
 
@@ -173,6 +174,8 @@ def load_library() -> C.CDLL:
     lib.bark_hip_profile_lock_step.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.bark_hip_batch_audio.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_float))]
     lib.bark_hip_batch_tokens.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int]
+    lib.bark_hip_batch_lock_steps.restype = C.c_int
+    lib.bark_hip_batch_lock_steps.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.bark_hip_clone_context.restype = vp
     lib.bark_hip_clone_context.argtypes = [vp, C.c_uint32]
     lib.bark_hip_generate_audio_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int]
@@ -602,6 +605,13 @@ class BarkContext:
                 d[name] = buf[:max(k, 0)].copy().reshape(-1, w) if w > 1 else buf[:max(k, 0)].copy()
             out.append(d)
         return out
+
+    def batch_lock_steps(self):
+        """(semantic, coarse) lock steps of the context's last job (bark_hip_batch_lock_steps); (0, 0): the sequential fallback served it; None: no job yet."""
+        out = (C.c_int32 * 2)()
+        if self._lib.bark_hip_batch_lock_steps(self._h, out) != 0:
+            return None
+        return int(out[0]), int(out[1])
 
     def clone(self, seed: int = 0) -> "BarkContext":
         h = self._lib.bark_hip_clone_context(self._h, seed)

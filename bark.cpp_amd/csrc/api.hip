@@ -526,6 +526,11 @@ int bark_hip_batch_tokens(struct bark_context * bctx, int i, int stage, int32_t 
     if (!v.empty()) memcpy(out, v.data(), v.size() * 4);
     return (int) v.size();
 }
+int bark_hip_batch_lock_steps(struct bark_context * bctx, int32_t out2[2]) {
+    if (!bctx || !out2 || bctx->job_lock_steps[0] < 0) return -1;
+    out2[0] = bctx->job_lock_steps[0]; out2[1] = bctx->job_lock_steps[1];
+    return 0;
+}
 
 static int copy_out(const std::vector<int32_t> & v, int per_row, int32_t * out, int capacity_rows) {
     const int rows = (int) v.size() / per_row;

@@ -219,6 +219,9 @@ struct bark_context {
     } fine_batch;
     struct BatchResult { std::vector<int32_t> semantic, coarse, fine; std::vector<float> audio; bool ok = false; };
     std::vector<BatchResult> batch_results;
+    // lock steps (batch_step calls) of the last bark_hip_generate_batch job: [0] semantic stage, [1] coarse stage; {0, 0}: the sequential fallback took
+    // the job; -1: no job has run (bark_hip_batch_lock_steps)
+    int32_t job_lock_steps[2] = {-1, -1};
     bark_context * tail = nullptr;                      // clone that runs the fine passes / codec of a lock-step job beside its decode chain (engine_batch.hip: JobTail)
 
 #ifdef BARK_TRACE

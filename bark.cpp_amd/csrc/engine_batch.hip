@@ -366,7 +366,9 @@ double engine_time_slots(bark_context * c, int which, int op, int B, int kind, i
     if (which < 0 || which > 1 || op < 0 || op > 5 || B < 1 || B > kMaxSlots) throw std::runtime_error("time_slots: bad arguments");
     HIP_OK(hipSetDevice(c->device));
     GptModel & m = c->gpt[which];
-    if (m.q4 || c->any_w32) throw std::runtime_error("time_slots: f16 model files only");
+    if (m.q4 && !m.w32) throw std::runtime_error("time_slots: f16 and f32 model files only");
+    // f32 files: the products are gemv_w32_slots_kernel on f32 rows (kind 0); there are no matrix-core kinds and no f16 rows to normalise (op 4)
+    if (m.w32 && (op == 4 || (kind != 0 && op != 5))) throw std::runtime_error("time_slots: an f32 model file has the VALU products (kind 0) of ops 0 - 3 and the attention (op 5) only");
     ensure_batch(c, c->batch.cap ? c->batch.cap : std::max(B, 8));
     bark_context::Batch & bb = c->batch;
     if (B > bb.cap) throw std::runtime_error("time_slots: batch larger than the capacity fixed by the first call");
@@ -381,6 +383,7 @@ double engine_time_slots(bark_context * c, int which, int op, int B, int kind, i
     HIP_OK(hipMemsetAsync(bb.h, 0, (size_t) B * 4 * E * 2, c->stream));
     HIP_OK(hipMemsetAsync(bb.ln_stats, 0, (size_t) B * 2 * 4, c->stream));
     HIP_OK(hipMemsetAsync(c->xn, 0, (size_t) B * 4 * E * 2, c->stream));
+    if (m.q4) { HIP_OK(hipMemsetAsync(bb.att32, 0, (size_t) B * E * 4, c->stream)); HIP_OK(hipMemsetAsync(bb.h32, 0, (size_t) B * 4 * E * 4, c->stream)); }
     if (op == 5) {
         HIP_OK(hipMemsetAsync(bb.kc[which], 0, bb.slot_stride[which] * (size_t) B * 4, c->stream));
         HIP_OK(hipMemsetAsync(bb.vc[which], 0, bb.slot_stride[which] * (size_t) B * 4, c->stream));
@@ -393,7 +396,7 @@ double engine_time_slots(bark_context * c, int which, int op, int B, int kind, i
         if (op == 5) {
             AttnDecodeArgs at;
             at.q = bb.q; at.kc = kl; at.vc = vl; at.H = H; at.P = P; at.st = bb.state; at.att = bb.att;
-            at.nbatch = B; at.kv_slot_stride = slot;
+            at.nbatch = B; at.kv_slot_stride = slot; at.att32 = m.q4 ? bb.att32 : nullptr;
             if (kind != 0) at.sc = bb.sc;                        // kind 0: the one-workgroup-per-(head, slot) kernel, for the A/B
             launch_attn_decode(c->stream, at);
             return;
@@ -402,12 +405,12 @@ double engine_time_slots(bark_context * c, int which, int op, int B, int kind, i
         a.batched = 1; a.nbatch = B; a.kv_slot_stride = slot; a.N = 1;
         switch (op) {
             case OP_QKV:  a.q = bb.q; a.kc = kl; a.vc = vl; a.st = bb.state; break;
-            case OP_PROJ: a.x_f16 = bb.att; a.res = bb.x; break;
-            case OP_FC:   a.out_h = bb.h; break;
-            default:      a.x_f16 = bb.h; a.res = bb.x; break;
+            case OP_PROJ: if (m.q4) a.x_f32 = bb.att32; else a.x_f16 = bb.att; a.res = bb.x; break;
+            case OP_FC:   a.out_h = bb.h; a.out_h32 = m.q4 ? bb.h32 : nullptr; break;
+            default:      if (m.q4) a.x_f32 = bb.h32; else a.x_f16 = bb.h; a.res = bb.x; break;
         }
         if (a.ln_g) {
-            if (kind == 0) { a.x_f32 = bb.x; a.ln_stats = B >= 24 ? bb.ln_stats : nullptr; }
+            if (kind == 0) { a.x_f32 = bb.x; a.ln_stats = B >= 24 && !m.q4 ? bb.ln_stats : nullptr; }
             else if (kind == 6) a.x_f32 = bb.x;                          // LayerNorm fused into the matrix-core product
             else { a.x_f16 = c->xn; a.ln_g = a.ln_b = nullptr; }         // rows normalised already (op 4 is that launch)
         }
@@ -484,7 +487,7 @@ namespace { bool ensure_tail_context(bark_context * c); bool tail_stream_enabled
 void engine_reserve_batch(bark_context * c, int slots) {
     HIP_OK(hipSetDevice(c->device));
     if (slots < 1 || slots > kMaxSlots) throw std::runtime_error("reserve_batch: 1..64 slots");
-    if (c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd || c->any_w32) return;          // these contexts run batches sequentially
+    if (c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd) return;          // these contexts run batches sequentially
     ensure_batch(c, std::max(slots, 8));
     // the clone the tail of a job runs on: made here, off the hot path, instead of inside the first job
     if (slots > 1 && tail_stream_enabled() && !c->host_sampling) (void) ensure_tail_context(c);
@@ -727,7 +730,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
     const JobScope job(c);
     const bark_context_params & p = c->params;
     if (n <= 0 || n > 4096) throw std::runtime_error("generate_batch: 1..4096 utterances per call");
-    if (admit && (c->host_sampling || c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd || c->any_w32)) admit = nullptr;     // the sequential fallback takes the job as given
+    if (admit && (c->host_sampling || c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd)) admit = nullptr;     // the sequential fallback takes the job as given
     c->batch_results.assign((size_t) n, bark_context::BatchResult());
     // one generator per utterance (bark.cpp:1179 seeds one per context): utterance i of a batch is what a fresh context with
     // seed seeds[i] would generate.  Without explicit seeds they are drawn from the context's generator, in order.
@@ -744,8 +747,9 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
         u.voice = voices && voices[i] ? voices[i] : c->voice;
         u.rng = std::mt19937(u.rp.seed);
     }
-    if (c->host_sampling || c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd || c->any_w32) {
-        // host-side sampling and f32 model files keep one utterance in flight: fall back to the sequential loop
+    c->job_lock_steps[0] = c->job_lock_steps[1] = 0;
+    if (c->host_sampling || c->gpt[0].hp.n_embd != c->gpt[1].hp.n_embd) {
+        // host-side sampling and models of unequal width keep one utterance in flight: fall back to the sequential loop
         int good = 0;
         const bark_context_params saved = c->params;
         const bark_hip_sampling_filter saved_flt = c->filter;
@@ -851,6 +855,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             for (int b = 0; b < B; b++) { const Utt & u = us[(size_t) slot_utt[(size_t) b]]; least_left = std::min(least_left, u.cap - u.issued); }
             const int k = B ? std::max(0, std::min(32, least_left)) : 0;
             for (int j = 0; j < k; j++) batch_step(c, s, B);
+            c->job_lock_steps[0] += k;
             for (int b = 0; b < B; b++) us[(size_t) slot_utt[(size_t) b]].issued += k;
             std::vector<StepState> st;
             read_back(c, B, nullptr, st);
@@ -977,6 +982,7 @@ int engine_generate_batch(bark_context * c, const char * const * texts, int n, c
             // a slot whose last window is shorter than the others' keeps stepping to the end of the window (its further ids are discarded;
             // window prompt + sliding_window_size rows fit the context by the check above, as every window is even the parity stays shared)
             for (int j = 0; j < lock_steps; j++) batch_step(c, s, B);
+            c->job_lock_steps[1] += std::max(lock_steps, 0);
             // the window's ids of all slots in ONE copy (rows of 2048 per slot, 512 KB at 64 slots) and their states
             std::vector<int32_t> ids_all;
             std::vector<StepState> st;

@@ -543,8 +543,9 @@ void launch_linear_q(hipStream_t s, const LinArgs & a) {
 // ------------------------------------------------------------------------------------------------
 // f32 weights (model files converted without --use-f16).  ggml converts the activation only when the weight type asks for
 // it, so both operands are f32 here; the summation order is C1 unchanged (8-element chunks, chunk q -> chain q mod 16, fmaf).
-// These are plain kernels - the format is a compatibility path, not a tuned one: decode stages the (LayerNorm-ed) row in
-// LDS once per 16 output rows, rows (N > 1) re-read the weights from L2 for every eight activation rows.
+// Three kernels: the decode step of one utterance stages the (LayerNorm-ed) row in LDS once per 16 output rows (gemv_w32_kernel); rows
+// (N > 1) re-read the weights from L2 for every eight activation rows (gemm_w32_rows_kernel); the lock step of a job multiplies every
+// weight chunk into a group of eight slots (gemv_w32_slots_kernel), bit for bit gemv_w32_kernel slot by slot.
 // ------------------------------------------------------------------------------------------------
 template <bool LN, bool LNB>
 __global__ __launch_bounds__(256) void gemv_w32_kernel(const LinArgs a) {
@@ -641,9 +642,241 @@ __global__ __launch_bounds__(64) void gemm_w32_rows_kernel(const LinArgs a) {
         if (live && c == 0 && n0 + i < a.N) linear_epilogue(a, n0 + i, m, r, 0);
     }
 }
+// lock steps (a.batched: row b of every input and output is slot b): a workgroup owns 16 output rows - wave w rows 4 w .. 4 w + 3, lane c of a
+// row chain c, as gemv_w32_kernel - and a GROUP of G = 8 slots.  A weight chunk is loaded once and multiplied into the group's G accumulators
+// (acc[G] per lane); the group's rows wait in LDS, LayerNorm-ed first where the operator has one.  Per slot the arithmetic is gemv_w32_kernel's:
+//   product    chain c walks q = c, c + 16, ... ascending (across the K tiles too), eight fmaf per chunk, C1 tree over the 16 lanes;
+//   LayerNorm  gemv_w32_kernel's thread t owns elements [16 t, 16 t + 16), sums them in order in double, its wave reduces (wave_sum) and the four
+//              waves join as (r0 + r1) + (r2 + r3).  Here ONE wave normalises a slot's row: lane L plays the threads L + 64 vw (vw < K / 1024
+//              rounded up, the waves of that kernel that own elements), wave_sum per vw gives r_vw, waves without elements contribute the same
+//              +0.0, then the same join, the same f32 mean / variance / 1 / sqrtf(var + 1e-5f), scale, then gain, then bias - no barrier per slot;
+//              wave w takes the slots w and w + 4 of the group side by side.
+// Weights: PF = 8 / 6 chunks per lane in flight (a register ring; the first turn is requested in front of the LayerNorm / the staging of the rows).
+// A partial group computes its own slots only (uniform guards per slot).
+// LDS is static: G rows of KT = K (K <= 2048) or K / 2 elements - at most 68 KB, so that two workgroups fit the 160 KB of a CU at every shape
+// (W32Slots asserts it: a shape that does not fit does not compile).  Rows are stored with 4 floats of padding per 64: chunks c and c + 8 of a
+// 128-bit LDS read would otherwise meet in the same banks.
+// Grid order (1-D, speed only): workgroup id -> XCD id & 7 (round-robin dispatch), and inside an XCD the sequence number id >> 3 walks the slot
+// groups of one row block before it moves to the next row block: groups 1 .. of a row block re-read its 16 weight rows from the XCD's L2 right
+// after group 0 fetched them, so the bytes that leave HBM per launch are the weight matrix once, whatever the number of slots.
+// parity_rows (coarse LM head): every slot selects its rows by its OWN step parity; a group whose slots disagree runs the product once per
+// parity present and stores each slot from the pass of its parity (the engine keeps a job's slots at one parity, so this is the rare path).
+constexpr int W32S_G = 8;
+template <int NBLK> struct W32Slots {
+    static constexpr int K = NBLK * 128;
+    static constexpr int KT = K <= 2048 ? K : K / 2;           // elements of a row staged at a time
+    static constexpr int NT = K / KT;
+    static constexpr int KTP = KT + KT / 16;                   // padded row: 4 floats behind every 64
+    static constexpr int lds_bytes = W32S_G * KTP * 4;
+    static constexpr int NI = KT / 128;                        // chunks of a lane per K tile
+    static constexpr int PF = NI % 8 == 0 ? 8 : NI % 6 == 0 ? 6 : NI;      // weight chunks in flight per lane: divides NI (the ring index does not depend on the tile)
+    static_assert(KT % 128 == 0, "a K tile is a whole number of rounds of the 16 chains");
+    static_assert(lds_bytes <= 80 * 1024 - 1024, "two workgroups of the f32 slot product must fit the 160 KB of LDS of a CU");
+};
+DEVINL int w32s_lds(int e) { return e + ((e >> 6) << 2); }
+template <int NBLK, bool LN, bool LNB>
+__global__ __launch_bounds__(256, NBLK <= 8 ? 2 : 1) void gemv_w32_slots_kernel(const LinArgs a, const int nrb, const int ngrp) {
+    using T = W32Slots<NBLK>;
+    constexpr int K = T::K, KT = T::KT, NT = T::NT, KTP = T::KTP, NI = T::NI, PF = T::PF, G = W32S_G;
+    static_assert(!LN || NT == 1, "LayerNorm-fused f32 slot product: n_embd <= 2048");
+    __shared__ __attribute__((aligned(16))) float xs[G * KTP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, rg = lane >> 4;
+    const int seq = (int) blockIdx.x >> 3;
+    const int rb = (seq / ngrp) * 8 + ((int) blockIdx.x & 7), s0 = (seq % ngrp) * G;
+    if (rb >= nrb) return;                                     // whole workgroups: the grid is rounded up to 8 row blocks
+    const int m = rb * 16 + wave * 4 + rg;
+    const int ng = min(G, a.nbatch - s0);                      // slots of this group (the last group may be partial): nothing is computed for the others
+    const bool live = m < a.M;
+    const float * wbase = reinterpret_cast<const float *>(a.wq.qs) + (size_t) (live ? m : 0) * K + (c << 3);
+    // step parity of the group's slots (bit g) and which parities are present
+    int par_bits = 0, par_mask = 1;
+    if (a.parity_rows) {
+        par_mask = 0;
+        #pragma unroll
+        for (int g = 0; g < G; g++)
+            if (g < ng) { const int p = a.st[s0 + g].step & 1; par_bits |= p << g; par_mask |= 1 << p; }
+    }
+    // ---- the weight stream: lane c of a row walks the chunks c + 16 j, j < NBLK; PF of them are in flight per lane (a register ring), the first PF are
+    // requested here, in front of the LayerNorm / the staging of the rows, so that the latency of HBM overlaps them
+    float4 wb[PF][2];
+    auto request = [&](const float * wrow, int j, float4 (&dst)[2]) {
+        dst[0] = *reinterpret_cast<const float4 *>(wrow + 128 * j); dst[1] = *reinterpret_cast<const float4 *>(wrow + 128 * j + 4);
+    };
+    const int p_first = (par_mask & 1) ? 0 : 1;
+    #pragma unroll
+    for (int j = 0; j < PF; j++) request(wbase + (size_t) a.parity_rows * p_first * K, j, wb[j]);
+    // ---- the rows of the group into LDS (K tile t of a product without LayerNorm; the whole LayerNorm-ed rows otherwise)
+    // every load of a round is requested before the first one is used (a loop of load / store pairs would pay one round trip to L2 per pair)
+    auto copy_tile = [&](int t) {
+        constexpr int CB = PF;                                 // G rows of KT / 4 = 32 NI float4: NI per thread, CB of them in flight
+        #pragma unroll
+        for (int k0 = 0; k0 < NI; k0 += CB) {
+            float4 f[CB];
+            #pragma unroll
+            for (int k = 0; k < CB; k++) {
+                const int i = tid + 256 * (k0 + k), g = i / (32 * NI);
+                f[k] = *reinterpret_cast<const float4 *>(a.x_f32 + (size_t) (s0 + min(g, ng - 1)) * K + t * KT + 4 * (i - g * (32 * NI)));
+            }
+            #pragma unroll
+            for (int k = 0; k < CB; k++) {
+                const int i = tid + 256 * (k0 + k), g = i / (32 * NI);
+                if (g < ng) *reinterpret_cast<float4 *>(xs + g * KTP + w32s_lds(4 * (i - g * (32 * NI)))) = f[k];
+            }
+        }
+    };
+    if constexpr (LN) {
+        // wave w normalises the slots w and w + 4 of the group side by side: two independent chains of loads and reductions instead of one after the other
+        constexpr int NVW = (K + 1023) / 1024, S = G / 4;
+        float v[S][NVW][16];
+        float mean[S], scale[S];
+        #pragma unroll
+        for (int s = 0; s < S; s++) {
+            const float * xrow = a.x_f32 + (size_t) (s0 + min(wave + 4 * s, ng - 1)) * K;
+            #pragma unroll
+            for (int vw = 0; vw < NVW; vw++) {
+                const int t = 64 * vw + lane;
+                const float4 * xp = reinterpret_cast<const float4 *>(xrow + (16 * t < K ? 16 * t : 0));
+                #pragma unroll
+                for (int i = 0; i < 4; i++) { const float4 f = xp[i]; v[s][vw][4 * i] = f.x; v[s][vw][4 * i + 1] = f.y; v[s][vw][4 * i + 2] = f.z; v[s][vw][4 * i + 3] = f.w; }
+            }
+        }
+        #pragma unroll
+        for (int s = 0; s < S; s++) {
+            double r1[4] = {0.0, 0.0, 0.0, 0.0};
+            #pragma unroll
+            for (int vw = 0; vw < NVW; vw++) {
+                double s1 = 0.0;
+                if (16 * (64 * vw + lane) < K) {
+                    #pragma unroll
+                    for (int j = 0; j < 16; j++) s1 += (double) v[s][vw][j];
+                }
+                r1[vw] = wave_sum(s1);
+            }
+            mean[s] = (float) (((r1[0] + r1[1]) + (r1[2] + r1[3])) / (double) K);
+        }
+        #pragma unroll
+        for (int s = 0; s < S; s++) {
+            double r2[4] = {0.0, 0.0, 0.0, 0.0};
+            #pragma unroll
+            for (int vw = 0; vw < NVW; vw++) {
+                const bool mine = 16 * (64 * vw + lane) < K;
+                double s2 = 0.0;
+                #pragma unroll
+                for (int j = 0; j < 16; j++) { const float u = v[s][vw][j] - mean[s]; v[s][vw][j] = u; if (mine) s2 += (double) (u * u); }
+                r2[vw] = wave_sum(s2);
+            }
+            const float var = (float) (((r2[0] + r2[1]) + (r2[2] + r2[3])) / (double) K);
+            scale[s] = 1.0f / sqrtf(var + 1e-5f);
+        }
+        #pragma unroll
+        for (int vw = 0; vw < NVW; vw++) {
+            const int k0 = 16 * (64 * vw + lane);
+            if (k0 < K) {
+                float gn[16], bs[16];
+                #pragma unroll
+                for (int j = 0; j < 16; j++) { gn[j] = a.ln_g[k0 + j]; if constexpr (LNB) bs[j] = a.ln_b[k0 + j]; else bs[j] = 0.0f; }
+                #pragma unroll
+                for (int s = 0; s < S; s++) {
+                    const int g = wave + 4 * s;
+                    if (g < ng) {
+                        #pragma unroll
+                        for (int j = 0; j < 16; j++) {
+                            float u = v[s][vw][j] * scale[s];
+                            u = u * gn[j];
+                            if constexpr (LNB) u = u + bs[j];
+                            v[s][vw][j] = u;
+                        }
+                        #pragma unroll
+                        for (int i = 0; i < 4; i++)
+                            *reinterpret_cast<float4 *>(xs + g * KTP + w32s_lds(k0 + 4 * i)) = make_float4(v[s][vw][4 * i], v[s][vw][4 * i + 1], v[s][vw][4 * i + 2], v[s][vw][4 * i + 3]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    } else if constexpr (NT == 1) {
+        copy_tile(0);
+        __syncthreads();
+    }
+    for (int p = p_first; p < 2; p++) {
+        if (!((par_mask >> p) & 1)) continue;                  // uniform over the workgroup
+        const int row_off = a.parity_rows * p;
+        const float * wrow = wbase + (size_t) row_off * K;
+        if (p != p_first) {                                    // second pass of a group with both parities: its requests start here
+            #pragma unroll
+            for (int j = 0; j < PF; j++) request(wrow, j, wb[j]);
+        }
+        EpiPre pre[G];
+        #pragma unroll
+        for (int g = 0; g < G; g++)
+            if (g < ng) pre[g] = epilogue_prefetch(a, s0 + g, live ? m : 0, row_off);
+        float acc[G];
+        #pragma unroll
+        for (int g = 0; g < G; g++) acc[g] = 0.0f;
+        #pragma unroll 1
+        for (int t = 0; t < NT; t++) {
+            if constexpr (NT > 1) { __syncthreads(); copy_tile(t); __syncthreads(); }
+            #pragma unroll 1
+            for (int i0 = 0; i0 < NI; i0 += PF) {              // one turn of the ring per trip: the ring index is static, the code stays PF chunks long
+                #pragma unroll
+                for (int r = 0; r < PF; r++) {
+                    const float4 w0 = wb[r][0], w1 = wb[r][1];
+                    const int nxt = t * NI + i0 + r + PF;      // the chunk that takes the ring slot over
+                    if (nxt < NBLK) request(wrow, nxt, wb[r]);
+                    const float * xq = xs + w32s_lds((c + 16 * (i0 + r)) << 3);
+                    #pragma unroll
+                    for (int g = 0; g < G; g++) {
+                        if (g < ng) {
+                            const float4 x0 = *reinterpret_cast<const float4 *>(xq + g * KTP), x1 = *reinterpret_cast<const float4 *>(xq + g * KTP + 4);
+                            float v = acc[g];
+                            v = fmaf(w0.x, x0.x, v); v = fmaf(w0.y, x0.y, v); v = fmaf(w0.z, x0.z, v); v = fmaf(w0.w, x0.w, v);
+                            v = fmaf(w1.x, x1.x, v); v = fmaf(w1.y, x1.y, v); v = fmaf(w1.z, x1.z, v); v = fmaf(w1.w, x1.w, v);
+                            acc[g] = v;
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);         // LDS reads are not hoisted across chunks: 8 x 8 floats of rows in registers at most
+                }
+            }
+        }
+        #pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (g < ng) {                                      // uniform: every lane of the wave takes part in the tree
+                const float r = wave_xor_add16(acc[g]);
+                if (live && c == 0 && (!a.parity_rows || ((par_bits >> g) & 1) == p)) linear_epilogue_pre(a, s0 + g, m, r, pre[g]);
+            }
+        }
+    }
+}
+template <int NBLK>
+static void launch_w32_slots_n(hipStream_t s, const LinArgs & a) {
+    const int nrb = (a.M + 15) / 16, ngrp = (a.nbatch + W32S_G - 1) / W32S_G;
+    const dim3 grid((nrb + 7) / 8 * 8 * ngrp), block(256);
+    if (a.ln_g) {
+        if constexpr (W32Slots<NBLK>::NT == 1) {
+            if (a.ln_b) hipLaunchKernelGGL((gemv_w32_slots_kernel<NBLK, true, true>), grid, block, 0, s, a, nrb, ngrp);
+            else        hipLaunchKernelGGL((gemv_w32_slots_kernel<NBLK, true, false>), grid, block, 0, s, a, nrb, ngrp);
+        } else { kernel_fail("bark-hip: LayerNorm-fused f32 lock-step product supports n_embd <= 2048"); }
+    } else hipLaunchKernelGGL((gemv_w32_slots_kernel<NBLK, false, false>), grid, block, 0, s, a, nrb, ngrp);
+}
 void launch_linear_w32(hipStream_t s, const LinArgs & a) {
     if ((a.K & 127) != 0 || a.K > 4096) { kernel_fail("bark-hip: unsupported K=%d in f32 linear op", a.K); }
-    if (a.batched || !a.x_f32) { kernel_fail("bark-hip: f32-weight products take f32 rows, one sequence at a time"); }
+    if (!a.x_f32) { kernel_fail("bark-hip: f32-weight products take f32 rows"); }
+    if (a.batched) {
+        if (a.N != 1 || a.ln_stats || a.nbatch < 1 || a.nbatch > 64) { kernel_fail("bark-hip: batched f32 products take one row per sequence, up to 64 sequences, and in-kernel LayerNorm statistics"); }
+        switch (a.K >> 7) {           // n_embd in {128, 256, 512, 768, 1024} and 4x those
+            case 1:  launch_w32_slots_n<1>(s, a); break;
+            case 2:  launch_w32_slots_n<2>(s, a); break;
+            case 4:  launch_w32_slots_n<4>(s, a); break;
+            case 6:  launch_w32_slots_n<6>(s, a); break;
+            case 8:  launch_w32_slots_n<8>(s, a); break;
+            case 16: launch_w32_slots_n<16>(s, a); break;
+            case 24: launch_w32_slots_n<24>(s, a); break;
+            case 32: launch_w32_slots_n<32>(s, a); break;
+            default: kernel_fail("bark-hip: unsupported K=%d in the f32 lock-step product", a.K);
+        }
+        return;
+    }
     if (a.N == 1) {
         dim3 grid((a.M + 15) / 16), block(256);
         if (a.ln_g) {

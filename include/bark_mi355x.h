@@ -170,7 +170,9 @@ BARK_API int bark_hip_generate_audio_batch(struct bark_context ** ctxs, const ch
  * parameters, whatever the job size, the slot count or the company an utterance travels in.  With temp > 0 every
  * utterance has its own std::mt19937 (the reference seeds one per context, bark.cpp:1179): utterance i is what a context
  * loaded with seed seeds[i] would generate; the unseeded call draws those seeds from the context's generator, in order.
- * BARK_HIP_HOST_SAMPLING degrades the call to a sequential loop.
+ * Every weight format takes this route: f16 files on the matrix cores, q4_0 .. q8_0 and f32 files on per-slot VALU products (f32: every weight
+ * chunk is read once for a group of eight slots); for those the prompts go slot by slot and the fine passes utterance by utterance.
+ * BARK_HIP_HOST_SAMPLING, and semantic / coarse models of unequal width, degrade the call to a sequential loop (bark_hip_batch_lock_steps tells).
  * Returns the number of utterances that produced audio.  Results: bark_hip_batch_audio / bark_hip_batch_tokens. */
 BARK_API int bark_hip_generate_batch(struct bark_context * bctx, const char * const * texts, int n);
 BARK_API int bark_hip_generate_batch_seeded(struct bark_context * bctx, const char * const * texts, int n, const uint32_t * seeds);
@@ -235,6 +237,9 @@ BARK_API int bark_hip_pick_rows(struct bark_context * bctx, const float * logits
                                 const int32_t * rel, int32_t * tokens_io, int32_t * near_ties);
 /* Fixes the number of lock-step slots (1..64; at least 8 are allocated) before the first job; returns 0 or -1. */
 BARK_API int bark_hip_reserve_batch(struct bark_context * bctx, int slots);
+/* The lock steps the context's last job ran: out2[0] in the semantic stage, out2[1] in the coarse stage (one lock step = one decode step of all live
+ * slots together).  {0, 0}: the sequential fallback served the job.  Returns 0, or -1 when no job has run on the context (out2 untouched). */
+BARK_API int bark_hip_batch_lock_steps(struct bark_context * bctx, int32_t out2[2]);
 /* audio of utterance i of the last batch: returns the sample count (-1 on error), *data points into the context */
 BARK_API int bark_hip_batch_audio(struct bark_context * bctx, int i, float ** data);
 /* token stream of utterance i: stage 0 semantic, 1 coarse [T][2], 2 fine [T][8]; returns the id count or -1 */
@@ -315,7 +320,9 @@ BARK_API double bark_hip_time_gemv(struct bark_context * bctx, int which, int op
  * `iters` back-to-back launches that rotate through the layers' weights.  op: 0 QKV, 1 attention out-proj, 2 FC + GELU, 3 MLP out-proj,
  * 4 LayerNorm of the slot rows, 5 attention of every slot at context `ctx`.  kind: 0 = the VALU GEMV per pair of slots with the LayerNorm fused
  * (ops 0 / 2) and, for op 5, one workgroup per (head, slot); 6 = the matrix-core product with the LayerNorm fused (ops 0 / 2); any other value =
- * the matrix-core product on normalised f16 rows and, for op 5, the scores + mix pair of launches where the engine would use it.  f16 model files only. */
+ * the matrix-core product on normalised f16 rows and, for op 5, the scores + mix pair of launches where the engine would use it.  f16 model files, and
+ * f32 model files with kind 0 for ops 0 - 3 (the slot-group product gemv_w32_slots_kernel) and op 5; an f32 file has no op 4 and no matrix-core kinds, a
+ * block-quantised file none of this (< 0). */
 BARK_API double bark_hip_time_slots(struct bark_context * bctx, int which, int op, int n_slots, int kind, int ctx, int iters);
 
 /* Time line of ONE lock step over n_slots slots of model `which` (0 semantic, 1 coarse) at context `ctx`: the step is enqueued eagerly `reps`
