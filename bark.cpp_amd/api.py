@@ -48,6 +48,21 @@ class BarkHipVoicePrompt(C.Structure):
                 ("fine_Tx8", C.c_void_p), ("n_fine_frames", C.c_int32)]
 
 
+class BarkHipAudioFormat(C.Structure):
+    """struct bark_hip_audio_format (bark_mi355x.h): output rate and sample format of an answer (rule C14r); {24000, SAMPLE_F32}: what the engine makes."""
+    _fields_ = [("sample_rate", C.c_int32), ("sample_format", C.c_int32)]
+
+
+SAMPLE_F32, SAMPLE_S16, SAMPLE_MULAW = 0, 1, 2          # enum bark_hip_sample_format
+SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "mulaw": SAMPLE_MULAW}
+SAMPLE_DTYPES = {SAMPLE_F32: np.float32, SAMPLE_S16: np.int16, SAMPLE_MULAW: np.uint8}
+
+
+def audio_format(rate: int = 24000, fmt="f32") -> BarkHipAudioFormat:
+    """fmt: "f32" | "s16" | "mulaw", or the enum's value"""
+    return BarkHipAudioFormat(int(rate), SAMPLE_FORMATS[fmt] if isinstance(fmt, str) else int(fmt))
+
+
 def _voice_struct(voice):
     """(struct, arrays that must stay alive while it is used) for a voice.VoicePrompt or any object with semantic / coarse [T][2] / fine [T][8]."""
     sem = np.ascontiguousarray(voice.semantic, dtype=np.int32).reshape(-1)
@@ -102,6 +117,8 @@ EXPORTS = [
     "bark_hip_load_semantic_encoder", "bark_hip_has_semantic_encoder", "bark_hip_semantic_encode", "bark_hip_semantic_encode_tap", "bark_hip_semantic_head", "bark_hip_semantic_encode_device_us",
     "bark_hip_resample_taps", "bark_hip_resample_24k_to_16k", "bark_hip_voice_from_audio", "bark_hip_set_voice_from_audio", "bark_hip_time_resample",
     "bark_hip_batch_lock_steps",
+    "bark_hip_resample_out_len", "bark_hip_resample_table", "bark_hip_resample", "bark_hip_resample_many", "bark_hip_get_audio_as", "bark_hip_batch_audio_as",
+    "bark_hip_batcher_submit_as", "bark_hip_batcher_wait_bytes", "bark_hip_time_resample_pair",
 ]
 
 
@@ -166,6 +183,18 @@ def load_library() -> C.CDLL:
     lib.bark_hip_set_voice_from_audio.argtypes = [vp, fp, C.c_int]
     lib.bark_hip_time_resample.restype = C.c_double
     lib.bark_hip_time_resample.argtypes = [vp, C.c_int, C.c_int]
+    lib.bark_hip_resample_out_len.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.bark_hip_resample_table.argtypes = [C.c_int, C.c_int, fp, C.c_int, ip]
+    lib.bark_hip_resample.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int]
+    lib.bark_hip_resample_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.c_int, C.POINTER(BarkHipAudioFormat), vp, C.c_int, ip]
+    lib.bark_hip_get_audio_as.argtypes = [vp, C.POINTER(BarkHipAudioFormat), vp, C.c_int]
+    lib.bark_hip_batch_audio_as.argtypes = [vp, C.c_int, C.POINTER(BarkHipAudioFormat), vp, C.c_int]
+    lib.bark_hip_time_resample_pair.restype = C.c_double
+    lib.bark_hip_time_resample_pair.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.bark_hip_batcher_submit_as.restype = C.c_int64
+    lib.bark_hip_batcher_submit_as.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter), C.POINTER(BarkHipVoicePrompt),
+                                               C.POINTER(BarkHipAudioFormat)]
+    lib.bark_hip_batcher_wait_bytes.argtypes = [vp, C.c_int64, vp, C.c_int]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
     lib.bark_hip_generate_batch_seeded.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_uint32)]
     lib.bark_hip_generate_batch_ex.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams)]
@@ -545,6 +574,63 @@ class BarkContext:
             raise RuntimeError("bark_hip_time_resample failed")
         return us
 
+    # ---- output rate and sample format (rule C14r): the rational resampler and the formats f32 / s16 / mu-law ----
+    def resample(self, pcm, rate_in: int, rate_out: int) -> np.ndarray:
+        """One recording in f32 (bark_hip_resample): n samples at rate_in -> ceil(n rate_out / rate_in) at rate_out; 24000 on at least one side."""
+        x = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        cap = self._lib.bark_hip_resample_out_len(len(x), int(rate_in), int(rate_out))
+        if cap < 0:
+            raise ValueError(f"bark_hip_resample: unsupported pair {rate_in} -> {rate_out}")
+        out = np.zeros(max(cap, 1), np.float32)
+        n = self._lib.bark_hip_resample(self._h, x.ctypes.data, len(x), int(rate_in), int(rate_out), out.ctypes.data, out.size)
+        if n < 0:
+            raise ValueError("bark_hip_resample refused the recording (empty, longer than 1 310 720 samples, or a sample that is not finite)")
+        return out[:n].copy()
+
+    def resample_many(self, pcm_list, rate_in: int, rate_out: int, fmt="f32") -> list:
+        """Up to 64 segments in one launch (bark_hip_resample_many): one array per segment in the format's dtype (float32 / int16 / uint8)."""
+        xs = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in pcm_list]
+        to = audio_format(rate_out, fmt)
+        ns = _i32([len(x) for x in xs])
+        ptrs = (C.c_void_p * len(xs))(*[x.ctypes.data for x in xs])
+        dt = np.dtype(SAMPLE_DTYPES[to.sample_format])
+        cap = sum(max(self._lib.bark_hip_resample_out_len(len(x), int(rate_in), int(rate_out)), 0) for x in xs) * dt.itemsize
+        out = np.zeros(max(cap, 1), np.uint8)
+        n_out = np.zeros(max(len(xs), 1), np.int32)
+        got = self._lib.bark_hip_resample_many(self._h, ptrs, ns.ctypes.data, len(xs), int(rate_in), C.byref(to), out.ctypes.data, cap, n_out.ctypes.data)
+        if got < 0:
+            raise ValueError("bark_hip_resample_many refused the call (segment count or length, a sample that is not finite, the pair or the format)")
+        res, off = [], 0
+        for k in n_out[:len(xs)]:
+            res.append(out[off:off + int(k) * dt.itemsize].view(dt).copy()); off += int(k) * dt.itemsize
+        return res
+
+    def _audio_as(self, call, to) -> np.ndarray:
+        n = call(None, 0)                                   # probe: -(2 + bytes)
+        if n > -2:
+            raise RuntimeError("no audio held, or an unsupported rate / format")
+        buf = np.zeros(-n - 2, np.uint8)
+        n = call(buf.ctypes.data, buf.size)
+        if n < 0:
+            raise RuntimeError("the conversion failed")
+        return buf[:n].view(SAMPLE_DTYPES[to.sample_format]).copy()
+
+    def audio_as(self, rate: int = 24000, fmt="f32") -> np.ndarray:
+        """The last generate_audio result at `rate` in `fmt` (bark_hip_get_audio_as); audio_data() stays 24 kHz f32."""
+        to = audio_format(rate, fmt)
+        return self._audio_as(lambda p, cap: self._lib.bark_hip_get_audio_as(self._h, C.byref(to), p, cap), to)
+
+    def batch_audio_as(self, i: int, rate: int = 24000, fmt="f32") -> np.ndarray:
+        """Utterance i of the last job at `rate` in `fmt` (bark_hip_batch_audio_as)."""
+        to = audio_format(rate, fmt)
+        return self._audio_as(lambda p, cap: self._lib.bark_hip_batch_audio_as(self._h, int(i), C.byref(to), p, cap), to)
+
+    def time_resample_pair(self, n: int, rate_in: int, rate_out: int, fmt="f32", iters: int = 20) -> float:
+        us = self._lib.bark_hip_time_resample_pair(self._h, int(n), int(rate_in), int(rate_out), audio_format(rate_out, fmt).sample_format, int(iters))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_resample_pair failed")
+        return us
+
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""
         p = self._params if self._params is not None else default_params()
@@ -759,6 +845,7 @@ class Batcher:
         ctxs = list(ctx) if isinstance(ctx, (list, tuple)) else [ctx]
         self._lib = ctxs[0]._lib
         self._ctx = ctxs                                # the worker threads run on these contexts: they must outlive the batcher
+        self._formats = {}                              # ticket -> sample format of the requests submitted with audio_format (wait_bytes picks the dtype)
         if len(ctxs) > 1:
             arr = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
             self._b = self._lib.bark_hip_batcher_create_multi(arr, len(ctxs), max_batch, max_wait_ms)
@@ -780,11 +867,23 @@ class Batcher:
             pass
 
     def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None,
-               voice=None) -> int:
-        """top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
+               voice=None, audio_format: "BarkHipAudioFormat | None" = None) -> int:
+        """audio_format: the rate / sample format of the answer (api.audio_format(rate, "s16"); bark_hip_batcher_submit_as) - fetch it with wait_bytes().
+        top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
         neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does.
         voice: the request's own voice.VoicePrompt (bark_hip_batcher_submit_voiced; None: the context's)."""
-        if voice is not None:
+        if audio_format is not None:
+            flt = None
+            if top_k is not None or top_p is not None:
+                flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
+            if params is None:
+                params = self._ctx[0].request_params(seed=int(seed))
+            st, keep = _voice_struct(voice) if voice is not None else (None, None)
+            t = self._lib.bark_hip_batcher_submit_as(self._b, text.encode("utf-8"), C.byref(params), None if flt is None else C.byref(flt),
+                                                     None if st is None else C.byref(st), C.byref(audio_format))
+            if t > 0:
+                self._formats[t] = int(audio_format.sample_format)
+        elif voice is not None:
             flt = None
             if top_k is not None or top_p is not None:
                 flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
@@ -814,6 +913,17 @@ class Batcher:
         if n < 0:
             raise RuntimeError("bark_hip_batcher_wait failed")
         return pcm[:n]
+
+    def wait_bytes(self, ticket: int) -> np.ndarray:
+        """The answer of any request in its own format (bark_hip_batcher_wait_bytes): float32 / int16 / uint8 samples (a request without audio_format: float32)."""
+        n = self._lib.bark_hip_batcher_wait_bytes(self._b, ticket, None, 0)    # probe: -(2 + bytes)
+        if n > -2:
+            raise RuntimeError("generation failed")
+        buf = np.zeros(-n - 2, np.uint8)
+        n = self._lib.bark_hip_batcher_wait_bytes(self._b, ticket, buf.ctypes.data, buf.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_batcher_wait_bytes failed")
+        return buf[:n].view(SAMPLE_DTYPES[self._formats.pop(ticket, SAMPLE_F32)]).copy()
 
     def stats(self) -> dict:
         a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)

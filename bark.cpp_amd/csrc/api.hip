@@ -372,6 +372,89 @@ double bark_hip_time_resample(struct bark_context * bctx, int n, int iters) {
     return guarded("bark_hip_time_resample", -1.0, [&] { return engine_time_resample(bctx, n, iters); });
 }
 
+// ---- output rate and sample format (rule C14r) ----------------------------------------------------------------------------------------------------
+int bark_hip_resample_out_len(int n, int rate_in, int rate_out) {
+    const long long r = resample_out_len(n, rate_in, rate_out);
+    return r < 0 || r > 0x7fffffffLL ? -1 : (int) r;
+}
+
+int bark_hip_resample_table(int rate_in, int rate_out, float * out, int capacity, int32_t lmh[3]) {
+    return guarded("bark_hip_resample_table", -1, [&] {
+        const ResampleTable * t = resample_pair_table(rate_in, rate_out);
+        if (!t) return -1;
+        if (lmh) { lmh[0] = t->L; lmh[1] = t->M; lmh[2] = t->half; }
+        if (!out && capacity == 0) return (int) t->h.size();
+        if (!out || (long) capacity < (long) t->h.size()) return -1;
+        memcpy(out, t->h.data(), t->h.size() * sizeof(float));
+        return (int) t->h.size();
+    }, /*uses_gpu=*/false);
+}
+
+namespace {
+// the bytes n segments give in `to`, or -1: a bad count / length / pair / format (what both resample calls refuse before any work)
+long long resampled_bytes(const int * n, int count, int rate_in, const bark_hip_audio_format & to) {
+    if (!n || count < 1 || count > kResampleMaxSegments || !sample_format_bytes(to.sample_format) || !resample_pair_supported(rate_in, to.sample_rate)) return -1;
+    long long total = 0;
+    for (int i = 0; i < count; i++) {
+        if (n[i] < 1 || n[i] > kResampleMaxSamples) return -1;
+        total += resample_out_len(n[i], rate_in, to.sample_rate) * sample_format_bytes(to.sample_format);
+    }
+    return total;
+}
+// 24 kHz f32 samples held by the context -> `fmt`: the byte count, -(2 + bytes) if it does not fit, -1
+int audio_as(struct bark_context * bctx, const char * what, const std::vector<float> & pcm, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes) {
+    if (!fmt || pcm.empty()) return -1;
+    const int n = (int) pcm.size();
+    const long long bytes = resampled_bytes(&n, 1, 24000, *fmt);
+    if (bytes < 0 || bytes > 0x7ffffff0LL) return -1;
+    if (!out || (long long) capacity_bytes < bytes) return -2 - (int) bytes;
+    return guarded(what, -1, [&] {
+        const float * p = pcm.data();
+        std::vector<int32_t> n_out;
+        const std::vector<uint8_t> r = engine_resample_many(bctx, &p, &n, 1, 24000, fmt->sample_rate, fmt->sample_format, n_out);
+        memcpy(out, r.data(), r.size());
+        return (int) r.size();
+    });
+}
+}  // namespace
+
+int bark_hip_resample_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, int rate_in, const struct bark_hip_audio_format * to,
+                           void * out_concat, int capacity_bytes, int32_t * n_out) {
+    if (!bctx || !pcm || !n || !to || !out_concat) return -1;
+    const long long bytes = resampled_bytes(n, count, rate_in, *to);
+    if (bytes < 0 || bytes > (long long) capacity_bytes) return -1;                       // refused before any work
+    for (int i = 0; i < count; i++) if (!pcm[i]) return -1;
+    return guarded("bark_hip_resample_many", -1, [&] {
+        std::vector<int32_t> no;
+        const std::vector<uint8_t> r = engine_resample_many(bctx, pcm, n, count, rate_in, to->sample_rate, to->sample_format, no);
+        memcpy(out_concat, r.data(), r.size());
+        if (n_out) memcpy(n_out, no.data(), no.size() * 4);
+        return (int) r.size();
+    });
+}
+
+int bark_hip_resample(struct bark_context * bctx, const float * pcm, int n, int rate_in, int rate_out, float * out, int capacity) {
+    const bark_hip_audio_format to{rate_out, BARK_HIP_SAMPLE_F32};
+    const long long cap_bytes = std::min<long long>(4LL * std::max(capacity, 0), 0x7ffffffcLL);
+    const int r = bark_hip_resample_many(bctx, &pcm, &n, 1, rate_in, &to, out, (int) cap_bytes, nullptr);
+    return r < 0 ? -1 : r / 4;
+}
+
+int bark_hip_get_audio_as(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes) {
+    if (!bctx) return -1;
+    return audio_as(bctx, "bark_hip_get_audio_as", bctx->audio, fmt, out, capacity_bytes);
+}
+
+int bark_hip_batch_audio_as(struct bark_context * bctx, int i, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes) {
+    if (!bctx || i < 0 || i >= (int) bctx->batch_results.size() || !bctx->batch_results[(size_t) i].ok) return -1;
+    return audio_as(bctx, "bark_hip_batch_audio_as", bctx->batch_results[(size_t) i].audio, fmt, out, capacity_bytes);
+}
+
+double bark_hip_time_resample_pair(struct bark_context * bctx, int n, int rate_in, int rate_out, int sample_format, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_resample_pair", -1.0, [&] { return engine_time_resample_pair(bctx, n, rate_in, rate_out, sample_format, iters); });
+}
+
 namespace {
 // the part of a recording that bark_hip_voice_from_audio uses, and the sizes of what it makes of it
 struct VoiceAudioCounts { int n_used, n_sem, n_frames; };

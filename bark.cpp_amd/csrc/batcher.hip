@@ -5,7 +5,9 @@
 // in that place on this engine: any number of host threads submit texts; ONE worker thread owns the context, collects what is pending
 // (up to max_batch requests, waiting at most max_wait_ms for a batch to fill once the first request is there) and runs them as one
 // lock-step batch.  Per-request results are those of a fresh context seeded with the request's seed (engine_generate_batch's contract),
-// whatever batch a request happened to travel in.  Plain C++ threads; nothing here touches the device.
+// whatever batch a request happened to travel in.  Plain C++ threads; the device is touched through the engine's entry points only, on the worker that owns the context.
+// A request may ask for its answer in another rate / sample format (bark_hip_batcher_submit_as, rule C14r): the worker converts behind the job, one
+// engine_resample_many per distinct format among the job's requests; requests in {24000, f32} take the path they always took.
 // Job streams (bark_hip_batcher_create_ex, n_streams 1 .. 4): further workers on clones of the context (own streams, caches and graphs, the
 // same weights) serve the same queue - a lock step is a chain of ~100 small dependent kernels, so two jobs share the chip (two streams of
 // 64-slot jobs out of phase: 37.8 prompts/s against 33.2 from one, profiles/r04_staggered_jobs.txt).  Workers that start together stay in
@@ -25,7 +27,12 @@
 using namespace barkhip;
 
 struct bark_hip_batcher {
-    struct Req { std::string text; bark_hip_request_params rp{}; bark_hip_sampling_filter flt{0, 1.0f}; VoicePtr voice; std::vector<float> pcm; bool done = false, ok = false; };
+    struct Req {
+        std::string text; bark_hip_request_params rp{}; bark_hip_sampling_filter flt{0, 1.0f}; VoicePtr voice; std::vector<float> pcm; bool done = false, ok = false;
+        bark_hip_audio_format fmt{24000, BARK_HIP_SAMPLE_F32};      // what the answer comes in (bark_hip_batcher_submit_as); the default keeps pcm, any other fills bytes
+        std::vector<uint8_t> bytes;
+        bool plain() const { return fmt.sample_rate == 24000 && fmt.sample_format == BARK_HIP_SAMPLE_F32; }
+    };
     bark_context * ctx = nullptr;                          // worker 0's context (the caller's); request defaults are read from it
     std::vector<bark_context *> ctxs;                      // one per worker; ctxs[1 ..] are clones owned by the batcher ...
     bool owns_workers = true;                              // ... unless the caller brought every context itself (bark_hip_batcher_create_multi: one per GPU)
@@ -80,10 +87,37 @@ struct bark_hip_batcher {
             try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit, flts.data(), voices.data()); }
             catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: batch failed: %s\n", e.what()); failed = true; }
             ctx->voice = ctx_voice;
+            // answers in another rate / format: converted here, on the thread that owns the context, one resample_many per distinct format (64 segments a call)
+            std::vector<std::vector<uint8_t>> conv(batch.size());
+            std::vector<char> conv_ok(batch.size(), 0);
+            for (size_t i = 0; i < batch.size() && !failed; i++) {
+                if (batch[i]->plain() || conv_ok[i] || !(i < ctx->batch_results.size() && ctx->batch_results[i].ok)) continue;
+                const bark_hip_audio_format f = batch[i]->fmt;
+                std::vector<size_t> who;
+                for (size_t k = i; k < batch.size(); k++)
+                    if (!batch[k]->plain() && batch[k]->fmt.sample_rate == f.sample_rate && batch[k]->fmt.sample_format == f.sample_format && k < ctx->batch_results.size() &&
+                        ctx->batch_results[k].ok && !ctx->batch_results[k].audio.empty() && !conv_ok[k]) who.push_back(k);
+                for (size_t g0 = 0; g0 < who.size(); g0 += kResampleMaxSegments) {
+                    const size_t g1 = std::min(who.size(), g0 + (size_t) kResampleMaxSegments);
+                    std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> n_out;
+                    for (size_t g = g0; g < g1; g++) { ptr.push_back(ctx->batch_results[who[g]].audio.data()); len.push_back((int) ctx->batch_results[who[g]].audio.size()); }
+                    try {
+                        const std::vector<uint8_t> r = engine_resample_many(ctx, ptr.data(), len.data(), (int) ptr.size(), 24000, f.sample_rate, f.sample_format, n_out);
+                        size_t off = 0;
+                        for (size_t g = g0; g < g1; g++) {
+                            const size_t nb = (size_t) n_out[g - g0] * (size_t) sample_format_bytes(f.sample_format);
+                            conv[who[g]].assign(r.begin() + (long) off, r.begin() + (long) (off + nb)); conv_ok[who[g]] = 1; off += nb;
+                        }
+                    } catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: conversion failed: %s\n", e.what()); }
+                }
+            }
             lk.lock();
             for (size_t i = 0; i < batch.size(); i++) {
                 Req & r = *batch[i];
-                if (!failed && i < ctx->batch_results.size() && ctx->batch_results[i].ok) { r.pcm = ctx->batch_results[i].audio; r.ok = true; }
+                if (!failed && i < ctx->batch_results.size() && ctx->batch_results[i].ok) {
+                    if (r.plain()) { r.pcm = ctx->batch_results[i].audio; r.ok = true; }
+                    else if (conv_ok[i]) { r.bytes = std::move(conv[i]); r.ok = true; }
+                }
                 r.done = true;
             }
             n_batches++; n_requests += (int) batch.size(); largest = std::max(largest, (int) batch.size());
@@ -154,9 +188,10 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create(struct bark_context *
 }
 
 static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp, const bark_hip_sampling_filter * flt = nullptr,
-                               const VoicePtr * voice = nullptr) {
+                               const VoicePtr * voice = nullptr, const bark_hip_audio_format * fmt = nullptr) {
     auto r = std::make_shared<bark_hip_batcher::Req>();
     r->text = text; r->rp = rp;
+    if (fmt) r->fmt = *fmt;
     std::lock_guard<std::mutex> lk(b->mu);
     if (b->stop) return -1;
     r->flt = flt ? *flt : b->default_filter;
@@ -197,12 +232,42 @@ BARK_API int64_t bark_hip_batcher_submit_voiced(struct bark_hip_batcher * b, con
     return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr);
 }
 
+BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                            const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
+                                            const struct bark_hip_audio_format * fmt) {
+    if (!b || !text || (filter && !filter_valid(*filter))) return -1;
+    if (fmt && (!sample_format_bytes(fmt->sample_format) || !resample_pair_supported(24000, fmt->sample_rate))) return -1;
+    VoicePtr v;
+    if (voice) {
+        try { v = engine_make_voice(b->ctx, voice); }
+        catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher_submit_as: %s\n", e.what()); return -1; }
+    }
+    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr, fmt);
+}
+
+BARK_API int bark_hip_batcher_wait_bytes(struct bark_hip_batcher * b, int64_t ticket, void * out, int capacity_bytes) {
+    if (!b) return -1;
+    std::unique_lock<std::mutex> lk(b->mu);
+    auto it = b->tickets.find(ticket);
+    if (it == b->tickets.end()) return -1;
+    std::shared_ptr<bark_hip_batcher::Req> r = it->second;
+    b->cv_done.wait(lk, [&] { return r->done; });
+    if (!r->ok) { b->tickets.erase(ticket); return -1; }
+    const void * src = r->plain() ? (const void *) r->pcm.data() : (const void *) r->bytes.data();
+    const size_t bytes = r->plain() ? r->pcm.size() * sizeof(float) : r->bytes.size();
+    if (!out || (size_t) std::max(capacity_bytes, 0) < bytes) return -2 - (int) bytes;      // too small: -(2 + bytes); the ticket stays valid
+    memcpy(out, src, bytes);
+    b->tickets.erase(ticket);
+    return (int) bytes;
+}
+
 BARK_API int bark_hip_batcher_wait(struct bark_hip_batcher * b, int64_t ticket, float * pcm, int capacity) {
     if (!b) return -1;
     std::unique_lock<std::mutex> lk(b->mu);
     auto it = b->tickets.find(ticket);
     if (it == b->tickets.end()) return -1;
     std::shared_ptr<bark_hip_batcher::Req> r = it->second;
+    if (!r->plain()) return -1;                                 // its answer is not 24 kHz f32: bark_hip_batcher_wait_bytes; the ticket stays valid
     b->cv_done.wait(lk, [&] { return r->done; });
     if (!r->ok) { b->tickets.erase(ticket); return -1; }
     if (!pcm || capacity < (int) r->pcm.size()) return -2 - (int) r->pcm.size();       // too small: -(2 + samples); the ticket stays valid

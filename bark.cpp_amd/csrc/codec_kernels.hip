@@ -659,4 +659,90 @@ void launch_resample_24k_16k(hipStream_t s, const float * x, int n, float * y, i
     hipLaunchKernelGGL(resample_24k_16k_kernel, dim3((n_out + kRsTile - 1) / kRsTile), dim3(256), 0, s, x, n, y, n_out, vec, taps);
 }
 
+// ---- rational resampler and the sample formats (rule C14r) ----------------------------------------------------------------------
+// The general form of the kernel above: any L / M, up to 160 phases of up to 40 taps - too large for a kernel argument, so the table lives in a device
+// buffer (uploaded once per pair and context) and every workgroup copies it into LDS, rows 2 half + 1 floats apart (consecutive outputs read consecutive
+// phase rows: an odd row distance spreads them over the banks).  One workgroup = one tile of 1024 consecutive outputs of ONE segment (the tile table of
+// `seg` says which): it stages the input window x[base(m0) - half + 1 .. base(m0 + cnt - 1) + half] once, as 16-byte loads from the 16-byte boundary at or
+// below the window's first sample - a segment starts anywhere in x, so the boundary is found from in_off + the window's start - and sample by sample, zero
+// outside the segment, where a quad crosses the segment's ends or x itself is not 16-byte aligned.  Work-item t forms outputs m0 + t + 256 i: neighbours
+// read LDS M / L <= 3 floats apart and store side by side.  Index arithmetic: m M is formed in 64 bits once per tile (m0 M = base0 L + ph0); inside the tile
+// (ph0 + d M) < 2^18 gives base and phase in 32 bits.
+__device__ __forceinline__ int sample_s16(float y) {
+    const float r = rintf(y * 32768.0f);                                 // ties to even; the product is exact (a power of two) or infinite
+    return (int) fminf(fmaxf(r, -32768.0f), 32767.0f);                   // saturates; a NaN (a chain that overflowed both ways) goes to -32768
+}
+__device__ __forceinline__ unsigned sample_mulaw(int s) {
+    const unsigned sign = s < 0 ? 0x80u : 0u;
+    const int mag = min(s < 0 ? -s : s, 32635) + 132;                    // 132 .. 32767
+    const int e = (mag >= 256) + (mag >= 512) + (mag >= 1024) + (mag >= 2048) + (mag >= 4096) + (mag >= 8192) + (mag >= 16384);      // floor(log2 mag) - 7
+    const unsigned man = ((unsigned) mag >> (e + 3)) & 15u;
+    return ~(sign | ((unsigned) e << 4) | man) & 0xFFu;
+}
+__device__ __forceinline__ void store_sample(void * y, size_t i, float v, int fmt) {
+    if (fmt == 0) static_cast<float *>(y)[i] = v;
+    else if (fmt == 1) static_cast<int16_t *>(y)[i] = (int16_t) sample_s16(v);
+    else static_cast<uint8_t *>(y)[i] = (uint8_t) sample_mulaw(sample_s16(v));
+}
+
+__global__ __launch_bounds__(256) void resample_pair_kernel(const ResamplePairArgs a, int vec) {
+    __shared__ float4 win4[kResampleWinFloats / 4];
+    __shared__ float tab[kResampleTabFloats];
+    constexpr int S = kResampleMaxSegments + 1;
+    const int t = (int) threadIdx.x, tile = (int) blockIdx.x;
+    const int * tile_off = a.seg + 4 * S;
+    int s = 0;
+    for (int hi = a.B; hi - s > 1;) { const int mid = (s + hi) >> 1; if (tile_off[mid] <= tile) s = mid; else hi = mid; }      // tile_off[s] <= tile < tile_off[s + 1]
+    const int n = a.seg[s], in_off = a.seg[S + s], n_out = a.seg[2 * S + s], out_off = a.seg[3 * S + s];
+    const int nt = 2 * a.half, ld = nt + 1;
+    for (int i = t; i < a.L * nt; i += 256) { const int p = i / nt; tab[p * ld + (i - p * nt)] = a.taps[i]; }
+    const int m0 = (tile - tile_off[s]) * kResampleTile;
+    const int cnt = min(kResampleTile, n_out - m0);
+    const long long t0 = (long long) m0 * a.M;
+    const int base0 = (int) (t0 / a.L), ph0 = (int) (t0 - (long long) base0 * a.L);
+    const int last = base0 + (ph0 + (cnt - 1) * a.M) / a.L;              // base of the tile's last output
+    const int w0 = base0 - a.half + 1;                                   // the first sample the tile reads, counted from the segment's start (may be < 0)
+    const int mis = (in_off + w0) & 3;                                   // samples between the 16-byte boundary and w0 (two's complement: also for a negative sum)
+    const int nq = (last + a.half - (w0 - mis)) / 4 + 1;                 // quads that cover w0 - mis .. last + half
+    const float * xs0 = a.x + in_off;
+    for (int q = t; q < nq; q += 256) {
+        const int r = w0 - mis + 4 * q;
+        float4 v;
+        if (vec && r >= 0 && r + 3 < n) v = *reinterpret_cast<const float4 *>(xs0 + r);
+        else {
+            v.x = (r >= 0 && r < n) ? xs0[r] : 0.0f;
+            v.y = (r + 1 >= 0 && r + 1 < n) ? xs0[r + 1] : 0.0f;
+            v.z = (r + 2 >= 0 && r + 2 < n) ? xs0[r + 2] : 0.0f;
+            v.w = (r + 3 >= 0 && r + 3 < n) ? xs0[r + 3] : 0.0f;
+        }
+        win4[q] = v;
+    }
+    __syncthreads();
+    const float * w = reinterpret_cast<const float *>(win4) + mis;       // w[b] = x[base0 + b - half + 1]
+    for (int d = t; d < cnt; d += 256) {
+        const int k = ph0 + d * a.M;
+        const int b = k / a.L;
+        const float * xv = w + b, * h = tab + (k - b * a.L) * ld;
+        float acc = 0.0f;
+        for (int i = 0; i < nt; i++) acc = fmaf(xv[i], h[i], acc);
+        store_sample(a.y, (size_t) out_off + (size_t) (m0 + d), acc, a.fmt);
+    }
+}
+void launch_resample_pair(hipStream_t s, const ResamplePairArgs & a, int n_tiles) {
+    if (!a.x || !a.y || !a.taps || !a.seg || a.B < 1 || a.B > kResampleMaxSegments || a.L < 1 || a.M < 1 || a.half < 1 || a.fmt < 0 || a.fmt > 2 || n_tiles < a.B ||
+        a.L * (2 * a.half + 1) > kResampleTabFloats || (long long) (kResampleTile - 1) * a.M / a.L + 2 * a.half + 8 > kResampleWinFloats)
+        kernel_fail("bark-hip: the rational resampler takes 1 .. %d segments and a table that fits its LDS copy (got B %d, L %d, M %d, half %d)", kResampleMaxSegments, a.B, a.L, a.M, a.half);
+    const int vec = ((size_t) a.x & 15) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(resample_pair_kernel, dim3(n_tiles), dim3(256), 0, s, a, vec);
+}
+
+__global__ __launch_bounds__(256) void sample_format_kernel(const float * x, void * y, size_t n, int fmt) {
+    const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (i < n) store_sample(y, i, x[i], fmt);
+}
+void launch_sample_format(hipStream_t s, const float * x, void * y, size_t n, int fmt) {
+    if (!x || !y || n < 1 || fmt < 1 || fmt > 2) kernel_fail("bark-hip: the sample format kernel takes fmt 1 (s16) or 2 (mu-law) and at least one sample");
+    hipLaunchKernelGGL(sample_format_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, y, n, fmt);
+}
+
 }  // namespace barkhip

@@ -182,6 +182,10 @@ struct bark_context {
     } hubs;
     hipEvent_t hub_ev[2] = {nullptr, nullptr}; double hub_device_us = -1.0;
     float * rs_in = nullptr, * rs_out = nullptr; size_t rs_elems = 0;      // resampler (C13r): the recording and its 16 kHz form (grown on demand)
+    // rational resampler (C14r): the taps of every pair used so far (uploaded once per pair), the segments' samples back to back, their results in the
+    // requested format (both grown on demand) and the segment table [5][kResampleMaxSegments + 1]
+    std::map<std::pair<int, int>, const float *> rp_taps;
+    float * rp_in = nullptr; size_t rp_in_elems = 0; void * rp_out = nullptr; size_t rp_out_bytes = 0; int * rp_seg = nullptr;
     struct CodecGraph { hipGraphExec_t exec = nullptr; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -289,6 +293,20 @@ constexpr int kVoiceAudioMaxSamples = 480000;
 std::vector<float> engine_resample_24k_16k(bark_context * ctx, const float * pcm24k, int n);
 VoicePtr engine_voice_from_audio(bark_context * ctx, const float * pcm24k, int n);
 double engine_time_resample(bark_context * ctx, int n, int iters);
+// Rational resampler and sample formats (C14r).  Rates: 8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000 with 24000 on at least one side;
+// rate_in == rate_out (24000) is the identity.  resample_pair_table: L, M, half and the taps [L][2 half] of a pair, computed once per process in double
+// precision and rounded to f32 (24000 -> 16000: the committed table of C13r); nullptr for the identity and for an unsupported pair.
+// resample_out_len: ceil(n L / M), n for the identity, -1 for an unsupported pair or n < 0.
+struct ResampleTable { int L = 1, M = 1, half = 1; std::vector<float> h; };
+const ResampleTable * resample_pair_table(int rate_in, int rate_out);
+bool resample_pair_supported(int rate_in, int rate_out);
+long long resample_out_len(long long n, int rate_in, int rate_out);
+inline int sample_format_bytes(int fmt) { return fmt == BARK_HIP_SAMPLE_F32 ? 4 : fmt == BARK_HIP_SAMPLE_S16 ? 2 : fmt == BARK_HIP_SAMPLE_MULAW ? 1 : 0; }
+// count <= 64 segments (1 .. 1 310 720 finite samples each) in ONE launch -> their results back to back as bytes of the format, n_out[i] samples each;
+// bit-identical to count single calls.  Throws on a bad count / length / sample / pair / format.
+std::vector<uint8_t> engine_resample_many(bark_context * ctx, const float * const * pcm, const int * n, int count, int rate_in, int rate_out, int fmt,
+                                          std::vector<int32_t> & n_out);
+double engine_time_resample_pair(bark_context * ctx, int n, int rate_in, int rate_out, int fmt, int iters);
 // kernel-level hook: latents [T][H] -> codes [n_q][T] by the RVQ kernel alone (C11q)
 std::vector<int32_t> engine_rvq_encode(bark_context * ctx, const float * latents, int T, int n_q);
 bool engine_generate(bark_context * ctx, const char * text);

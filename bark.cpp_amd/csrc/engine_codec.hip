@@ -6,6 +6,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
 #include <stdexcept>
 
 using namespace barkhip;
@@ -533,6 +536,147 @@ double engine_time_resample(bark_context * c, int n, int iters) {
     iters = std::max(1, iters);
     for (int i = 0; i < 2; i++) launch_resample_24k_16k(c->stream, c->rs_in, n, c->rs_out, n_out);
     return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_resample_24k_16k(c->stream, c->rs_in, n, c->rs_out, n_out); }) / iters;
+}
+
+// ---- output rate and sample format: the rational resampler (rule C14r) ------------------------------------------------------------------------------------
+namespace {
+constexpr int kPairRates[8] = {8000, 12000, 16000, 22050, 24000, 32000, 44100, 48000};
+bool pair_rate(int r) { for (int v : kPairRates) if (v == r) return true; return false; }
+int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+// numpy's sinc: sin(pi x) / (pi x) with x = 0 moved to 1e-20 (the quotient is then exactly 1)
+double np_sinc(double x) { const double y = M_PI * (x == 0.0 ? 1.0e-20 : x); return sin(y) / y; }
+ResampleTable make_pair_table(int rate_in, int rate_out) {
+    ResampleTable t;
+    const int g = gcd_int(rate_in, rate_out);
+    t.L = rate_out / g; t.M = rate_in / g;
+    const double c = 0.99 * std::min(1.0, (double) t.L / (double) t.M), W = 6.0 / c;
+    t.half = (int) ceil(W) + 1;
+    const int nt = 2 * t.half;
+    t.h.resize((size_t) t.L * nt);
+    if (rate_in == 24000 && rate_out == 16000) {                // C13r's committed table IS this pair's table
+        if (t.L != 2 || nt != 22) throw std::runtime_error("resampler: the committed 24000 -> 16000 table does not have the rule's shape");
+        std::copy(resample_taps(), resample_taps() + 44, t.h.begin());
+        return t;
+    }
+    // every step in double, in the expression order of voice.resample_24k_to_16k / tests/resample_ref.py (this file is compiled without contraction)
+    for (int p = 0; p < t.L; p++) for (int k = 0; k < nt; k++) {
+        const double u = (double) p / (double) t.L - (double) (k - t.half + 1);
+        const double s = c * np_sinc(c * u);
+        double win = 0.0;
+        if (fabs(u) < W) { const double co = cos(M_PI * u / (2.0 * W)); win = co * co; }
+        t.h[(size_t) p * nt + k] = (float) (s * win);
+    }
+    return t;
+}
+}  // namespace
+
+bool resample_pair_supported(int rate_in, int rate_out) { return pair_rate(rate_in) && pair_rate(rate_out) && (rate_in == 24000 || rate_out == 24000); }
+
+const ResampleTable * resample_pair_table(int rate_in, int rate_out) {
+    if (!resample_pair_supported(rate_in, rate_out) || rate_in == rate_out) return nullptr;
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, ResampleTable> cache;          // entries are never removed: the pointers stay valid
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find({rate_in, rate_out});
+    if (it == cache.end()) it = cache.emplace(std::make_pair(rate_in, rate_out), make_pair_table(rate_in, rate_out)).first;
+    return &it->second;
+}
+
+long long resample_out_len(long long n, int rate_in, int rate_out) {
+    if (n < 0 || !resample_pair_supported(rate_in, rate_out)) return -1;
+    if (rate_in == rate_out) return n;
+    const int g = gcd_int(rate_in, rate_out);
+    const long long L = rate_out / g, M = rate_in / g;
+    return (n * L + M - 1) / M;
+}
+
+namespace {
+// the device copy of a pair's taps, uploaded with the context's first use of the pair
+const float * device_taps(bark_context * c, int rate_in, int rate_out, const ResampleTable & t) {
+    auto it = c->rp_taps.find({rate_in, rate_out});
+    if (it != c->rp_taps.end()) return it->second;
+    float * d = dev_alloc<float>(c, t.h.size());
+    HIP_OK(hipMemcpyAsync(d, t.h.data(), t.h.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->rp_taps[{rate_in, rate_out}] = d;
+    return d;
+}
+void ensure_resample_buffers(bark_context * c, size_t in_elems, size_t out_bytes) {
+    if (in_elems > c->rp_in_elems) { c->rp_in = dev_alloc<float>(c, in_elems); c->rp_in_elems = in_elems; }
+    if (out_bytes > c->rp_out_bytes) { c->rp_out = dev_alloc<uint8_t>(c, out_bytes); c->rp_out_bytes = out_bytes; }
+    if (!c->rp_seg) c->rp_seg = dev_alloc<int>(c, 5 * (kResampleMaxSegments + 1));
+}
+// the segment table of launch_resample_pair for `count` segments of n[i] samples; returns the tile count
+int fill_segment_table(int (&seg)[5][kResampleMaxSegments + 1], const int * n, int count, int rate_in, int rate_out, std::vector<int32_t> & n_out) {
+    memset(seg, 0, sizeof(seg));
+    n_out.assign((size_t) count, 0);
+    for (int i = 0; i < count; i++) {
+        n_out[(size_t) i] = (int32_t) resample_out_len(n[i], rate_in, rate_out);
+        seg[0][i] = n[i]; seg[2][i] = n_out[(size_t) i];
+        seg[1][i + 1] = seg[1][i] + n[i]; seg[3][i + 1] = seg[3][i] + n_out[(size_t) i];
+        seg[4][i + 1] = seg[4][i] + (n_out[(size_t) i] + kResampleTile - 1) / kResampleTile;
+    }
+    return seg[4][count];
+}
+}  // namespace
+
+std::vector<uint8_t> engine_resample_many(bark_context * c, const float * const * pcm, const int * n, int count, int rate_in, int rate_out, int fmt,
+                                          std::vector<int32_t> & n_out) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!pcm || !n || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("resampler: 1 .. 64 segments in one call");
+    if (!resample_pair_supported(rate_in, rate_out)) throw std::runtime_error("resampler: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000, with 24000 on at least one side");
+    const int bytes_per = sample_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("resampler: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    size_t total_in = 0;
+    for (int i = 0; i < count; i++) {
+        if (!pcm[i] || n[i] < 1 || n[i] > kResampleMaxSamples) throw std::runtime_error("resampler: a segment needs 1 .. 1 310 720 samples");
+        for (int k = 0; k < n[i]; k++) if (!std::isfinite(pcm[i][k])) throw std::runtime_error("resampler: non-finite sample");
+        total_in += (size_t) n[i];
+    }
+    int seg[5][kResampleMaxSegments + 1];
+    const int n_tiles = fill_segment_table(seg, n, count, rate_in, rate_out, n_out);
+    const size_t total_out = (size_t) seg[3][count];
+    std::vector<uint8_t> out(total_out * (size_t) bytes_per);
+    const ResampleTable * t = resample_pair_table(rate_in, rate_out);
+    if (!t && fmt == BARK_HIP_SAMPLE_F32) {                      // the identity in f32: no filter, no launch, the samples themselves
+        for (int i = 0; i < count; i++) memcpy(out.data() + (size_t) seg[3][i] * 4, pcm[i], (size_t) n[i] * 4);
+        return out;
+    }
+    ensure_resample_buffers(c, total_in, out.size());
+    hipStream_t s = c->stream;
+    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->rp_in + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
+    if (!t) launch_sample_format(s, c->rp_in, c->rp_out, total_in, fmt);
+    else {
+        HIP_OK(hipMemcpyAsync(c->rp_seg, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+        ResamplePairArgs a;
+        a.x = c->rp_in; a.y = c->rp_out; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg;
+        a.B = count; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
+        launch_resample_pair(s, a, n_tiles);
+    }
+    HIP_OK(hipMemcpyAsync(out.data(), c->rp_out, out.size(), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));                             // seg is a stack object
+    return out;
+}
+
+double engine_time_resample_pair(bark_context * c, int n, int rate_in, int rate_out, int fmt, int iters) {
+    HIP_OK(hipSetDevice(c->device));
+    if (n < 1 || n > kResampleMaxSamples) throw std::runtime_error("time_resample_pair: 1 .. 1 310 720 samples");
+    const ResampleTable * t = resample_pair_table(rate_in, rate_out);
+    const int bytes_per = sample_format_bytes(fmt);
+    if (!t || !bytes_per) throw std::runtime_error("time_resample_pair: one of the 14 pairs with a filter and a sample format 0 .. 2");
+    int seg[5][kResampleMaxSegments + 1];
+    std::vector<int32_t> n_out;
+    const int n_tiles = fill_segment_table(seg, &n, 1, rate_in, rate_out, n_out);
+    ensure_resample_buffers(c, (size_t) n, (size_t) n_out[0] * (size_t) bytes_per);
+    HIP_OK(hipMemsetAsync(c->rp_in, 0, (size_t) n * 4, c->stream));      // the time does not depend on the values
+    HIP_OK(hipMemcpyAsync(c->rp_seg, seg, sizeof(seg), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    ResamplePairArgs a;
+    a.x = c->rp_in; a.y = c->rp_out; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg;
+    a.B = 1; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
+    iters = std::max(1, iters);
+    for (int i = 0; i < 2; i++) launch_resample_pair(c->stream, a, n_tiles);
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_resample_pair(c->stream, a, n_tiles); }) / iters;
 }
 
 VoicePtr engine_voice_from_audio(bark_context * c, const float * pcm, int n) {

@@ -345,4 +345,21 @@ constexpr int kResampleMaxSamples = 4096 * 320;
 const float * resample_taps();
 void launch_resample_24k_16k(hipStream_t s, const float * x, int n, float * y, int n_out);
 
+// ---- rational resampler between 24 kHz and the other output / input rates, sample formats (rule C14r; codec_kernels.hip) ------
+// L = rate_out / gcd, M = rate_in / gcd, taps [L][2 half] f32 on the device.  Output m of a segment: base = floor(m M / L), phase = (m M) mod L,
+// y[m] = one fmaf chain from +0 over x[base + j] taps[phase][j + half - 1], j = -half + 1 .. half ascending, samples outside the segment +0.
+// One launch serves up to kResampleMaxSegments segments: seg is a device table [5][kResampleMaxSegments + 1] of ints - input lengths, input offsets
+// (prefix sums: segment s reads x[in_off[s] ..]), output lengths (ceil(n L / M)), output offsets (in samples) and tile offsets (prefix sums of
+// ceil(n_out / kResampleTile), closed by the total).  fmt: 0 y is float *, 1 int16_t * (rintf(v 32768) clamped), 2 uint8_t * (G.711 mu-law of that s16 value).
+constexpr int kResampleMaxSegments = 64, kResampleTile = 1024;
+constexpr int kResampleTabFloats = 2752;                // LDS copy of the taps, rows 2 half + 1 apart: 160 x 17 (22050 -> 24000) is the largest
+constexpr int kResampleWinFloats = 3 * kResampleTile + 96;          // LDS window of a tile: M / L <= 3 input samples per output, 2 half <= 80 of reach, alignment
+struct ResamplePairArgs {
+    const float * x = nullptr; void * y = nullptr; const float * taps = nullptr; const int * seg = nullptr;
+    int B = 1, L = 1, M = 1, half = 1, fmt = 0;
+};
+void launch_resample_pair(hipStream_t s, const ResamplePairArgs & a, int n_tiles);
+// y[i] = format(x[i]) for n samples (fmt 1 or 2): the formats alone, where no filter runs
+void launch_sample_format(hipStream_t s, const float * x, void * y, size_t n, int fmt);
+
 }  // namespace barkhip

@@ -18,9 +18,13 @@
 //   GET /voices/NAME         the voice as a voice prompt file (what --voice name=file reads)
 // The recording is encoded by bark_hip_voice_from_audio on a clone kept for that purpose behind its own mutex: the contexts the collector owns are never
 // touched by a connection thread.
+// Output rate and sample format (bark_hip_audio_format, rule C14r): "sample_rate": 8000 | 12000 | 16000 | 22050 | 24000 | 32000 | 44100 | 48000 and "format": "f32" |
+// "s16" | "mulaw" in a /bark request (defaults: --sample-rate / --format, 24000 and f32) - the answer is a WAV with the matching header (IEEE float; 16-bit PCM;
+// 8-bit mu-law with a fact chunk), an unsupported value is answered 400.  POST /voices?name=NAME&resample=1 (for --voice-audio: --voice-audio-resample) takes a
+// recording at any of those rates and brings it to 24 kHz with bark_hip_resample on the encoder's clone; without the switch another rate stays a 400.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -59,6 +63,8 @@ struct Options {
     std::vector<std::string> voices;               // --voice name=file
     std::string semantic_encoder;                  // --semantic-encoder file
     std::vector<std::string> voice_audio;          // --voice-audio name=file.wav
+    bool voice_audio_resample = false;             // --voice-audio-resample: --voice-audio recordings at any supported rate
+    int sample_rate = 24000; std::string format = "f32";      // --sample-rate / --format: what a request without "sample_rate" / "format" is answered in
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -79,6 +85,8 @@ void respond(int fd, int status, const char * reason, const char * type, const s
 std::atomic<uint32_t> next_seed{0};
 bark_hip_request_params request_defaults{};            // the context's sampling parameters (a request with its own filter carries them explicitly)
 bark_hip_sampling_filter filter_defaults{0, 1.0f};
+bark_hip_audio_format format_defaults{24000, BARK_HIP_SAMPLE_F32};
+bool format_valid(const bark_hip_audio_format & f) { return f.sample_format >= 0 && f.sample_format <= 2 && bark_hip_resample_out_len(1, 24000, f.sample_rate) >= 1; }
 // the voices by name: read by every /bark request, written by POST /voices.  An entry is never changed, only replaced: a request that has looked its
 // voice up keeps it alive through its shared_ptr while a later POST puts another one under the same name
 std::shared_mutex voice_mutex;
@@ -97,6 +105,17 @@ void put_voice(const std::string & name, VoiceFile && v) {
 bark_context * encoder_ctx = nullptr;
 std::mutex encoder_mutex;
 constexpr size_t kMaxBody = 1u << 20, kMaxVoiceBody = 4u << 20;
+// a recording at another supported rate -> 24 kHz (bark_hip_resample on the encoder's clone); false: the engine refused it
+bool recording_to_24k(std::vector<float> & pcm, int rate) {
+    if (pcm.size() > 0x7fffffffu) return false;
+    const int n_out = bark_hip_resample_out_len((int) pcm.size(), rate, 24000);
+    if (n_out < 1) return false;
+    std::vector<float> out((size_t) n_out);
+    std::lock_guard<std::mutex> lock(encoder_mutex);
+    if (bark_hip_resample(encoder_ctx, pcm.data(), (int) pcm.size(), rate, 24000, out.data(), n_out) != n_out) return false;
+    pcm.swap(out);
+    return true;
+}
 // 24 kHz mono samples -> voice; false: the engine refused the recording (its message is on stderr)
 bool voice_from_recording(const std::vector<float> & pcm, VoiceFile & out) {
     const int used = (int) std::min<size_t>(pcm.size(), BARK_HIP_VOICE_AUDIO_MAX_SAMPLES);
@@ -151,10 +170,13 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
         std::vector<float> pcm;
         int rate = 0;
         VoiceFile vf;
+        std::string rs;
+        const bool may_resample = barkhttp::query_param(path, "resample", rs) && rs == "1";
         if (!encoder_ctx) respond(fd, 409, "Conflict", "text/plain", "no semantic encoder (--semantic-encoder) or no codec encoder in the model file");
         else if (!barkhttp::query_param(path, "name", name) || !barkhttp::valid_voice_name(name)) respond(fd, 400, "Bad Request", "text/plain", "expected ?name=NAME with 1 .. 64 of [A-Za-z0-9_.-]");
         else if (body.size() != content_length || !barkhttp::parse_wav(body, pcm, rate, err)) respond(fd, 400, "Bad Request", "text/plain", err.empty() ? "incomplete body" : err);
-        else if (rate != 24000) respond(fd, 400, "Bad Request", "text/plain", "the recording must be sampled at 24000 Hz");
+        else if (rate != 24000 && !may_resample) respond(fd, 400, "Bad Request", "text/plain", "the recording must be sampled at 24000 Hz (or send ?resample=1)");
+        else if (rate != 24000 && !recording_to_24k(pcm, rate)) respond(fd, 400, "Bad Request", "text/plain", "the rate is not one the resampler takes, or the engine refused the recording");
         else if (!voice_from_recording(pcm, vf)) respond(fd, 400, "Bad Request", "text/plain", "the engine refused the recording (too short, or samples that are not finite)");
         else {
             char js[256];
@@ -193,6 +215,19 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 ::close(fd);
                 return;
             }
+            // "sample_rate" / "format": what the answer comes in; checked here as well, for the same reason
+            bark_hip_audio_format af = format_defaults;
+            std::string fname;
+            const int hr = json_int(body, "sample_rate", af.sample_rate);
+            const bool hf = body.find("\"format\"") != std::string::npos;
+            if (hf) af.sample_format = json_string(body, "format", fname) ? barkhttp::sample_format_of(fname) : -1;
+            if (hr < 0 || !format_valid(af)) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"sample_rate\" must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and \"format\" \"f32\", \"s16\" or \"mulaw\"");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
+            const bool plain = af.sample_rate == 24000 && af.sample_format == BARK_HIP_SAMPLE_F32;
             // "voice": absent - no voice; otherwise a string that names a voice of the table (held until the answer is sent)
             std::shared_ptr<const VoiceFile> vf;
             int has_voice = 0;
@@ -208,6 +243,24 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
             }
             uint32_t seed = 0;
             if (!json_uint(body, "seed", seed)) seed = next_seed.fetch_add(1);
+            if (!plain) {
+                bark_hip_request_params rp = request_defaults; rp.seed = seed;
+                bark_hip_voice_prompt vp{};
+                if (vf) vp = bark_hip_voice_prompt{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
+                                                   vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
+                ticket = bark_hip_batcher_submit_as(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af);
+                int nb = ticket > 0 ? bark_hip_batcher_wait_bytes(batcher, ticket, nullptr, 0) : -1;     // probe: -(2 + bytes)
+                if (nb <= -2) {
+                    std::vector<char> bytes((size_t) (-nb - 2));
+                    nb = bark_hip_batcher_wait_bytes(batcher, ticket, bytes.data(), (int) bytes.size());
+                    const int width = af.sample_format == BARK_HIP_SAMPLE_F32 ? 4 : af.sample_format == BARK_HIP_SAMPLE_S16 ? 2 : 1;
+                    if (nb >= 0) respond(fd, 200, "OK", "audio/wav", barkhttp::wav_samples(bytes.data(), nb / width, af.sample_rate, af.sample_format));
+                }
+                if (nb < 0) respond(fd, 500, "Internal Server Error", "text/plain", "Internal Server Error");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
             if (vf) {
                 bark_hip_request_params rp = request_defaults; rp.seed = seed;
                 const bark_hip_voice_prompt vp{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
@@ -235,7 +288,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")]\n", argv0);
 }
 
 }  // namespace
@@ -260,9 +313,14 @@ int main(int argc, char ** argv) {
         else if (a == "--voice") o.voices.push_back(next("--voice"));
         else if (a == "--semantic-encoder") o.semantic_encoder = next("--semantic-encoder");
         else if (a == "--voice-audio") o.voice_audio.push_back(next("--voice-audio"));
+        else if (a == "--voice-audio-resample") o.voice_audio_resample = true;
+        else if (a == "--sample-rate") o.sample_rate = atoi(next("--sample-rate"));
+        else if (a == "--format") o.format = next("--format");
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
+    format_defaults = bark_hip_audio_format{o.sample_rate, barkhttp::sample_format_of(o.format)};
+    if (!format_valid(format_defaults)) { fprintf(stderr, "%s: --sample-rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and --format f32, s16 or mulaw\n", argv[0]); return 1; }
     {
         std::map<std::string, VoiceFile> files;
         for (const std::string & v : o.voices) {
@@ -317,7 +375,8 @@ int main(int argc, char ** argv) {
         fclose(f);
         if (body.size() > kMaxVoiceBody) return fail(arg.substr(eq + 1) + ": larger than 4 MiB");
         if (!barkhttp::parse_wav(body, pcm, rate, err)) return fail(arg.substr(eq + 1) + ": " + err);
-        if (rate != 24000) return fail(arg.substr(eq + 1) + ": the recording must be sampled at 24000 Hz");
+        if (rate != 24000 && !o.voice_audio_resample) return fail(arg.substr(eq + 1) + ": the recording must be sampled at 24000 Hz (or pass --voice-audio-resample)");
+        if (rate != 24000 && !recording_to_24k(pcm, rate)) return fail(arg.substr(eq + 1) + ": the rate is not one the resampler takes, or the engine refused the recording");
         if (!voice_from_recording(pcm, vf)) return fail(arg.substr(eq + 1) + ": the engine refused the recording");
         put_voice(arg.substr(0, eq), std::move(vf));
     }

@@ -255,4 +255,25 @@ inline std::string wav_f32(const float * pcm, int n, int rate) {
     return s;
 }
 
+// the request field / option value "f32" | "s16" | "mulaw" -> 0 | 1 | 2 (enum bark_hip_sample_format), -1: anything else
+inline int sample_format_of(const std::string & name) { return name == "f32" ? 0 : name == "s16" ? 1 : name == "mulaw" ? 2 : -1; }
+
+// A mono WAV around n samples in one of the three sample formats: 0 IEEE float (tag 3, 32 bit; the bytes of wav_f32), 1 PCM (tag 1, 16 bit), 2 G.711 mu-law
+// (tag 7, 8 bit: a non-PCM format, so the fmt chunk carries cbSize = 0 and a `fact` chunk states the sample count; an odd data chunk is followed by a pad byte)
+inline std::string wav_samples(const void * data, int n, int rate, int format) {
+    auto u32 = [](std::string & s, uint32_t v) { s.append(reinterpret_cast<const char *>(&v), 4); };
+    auto u16 = [](std::string & s, uint16_t v) { s.append(reinterpret_cast<const char *>(&v), 2); };
+    if (format == 0) return wav_f32(static_cast<const float *>(data), n, rate);
+    const uint32_t width = format == 1 ? 2 : 1, bytes = (uint32_t) n * width, pad = bytes & 1;
+    std::string s;
+    s += "RIFF"; u32(s, (format == 1 ? 36 : 50) + bytes + pad); s += "WAVE";
+    s += "fmt "; u32(s, format == 1 ? 16 : 18); u16(s, format == 1 ? 1 /* PCM */ : 7 /* mu-law */); u16(s, 1); u32(s, (uint32_t) rate); u32(s, (uint32_t) rate * width);
+    u16(s, (uint16_t) width); u16(s, (uint16_t) (8 * width));
+    if (format != 1) { u16(s, 0); s += "fact"; u32(s, 4); u32(s, (uint32_t) n); }
+    s += "data"; u32(s, bytes);
+    s.append(static_cast<const char *>(data), bytes);
+    if (pad) s.push_back('\0');
+    return s;
+}
+
 }  // namespace barkhttp

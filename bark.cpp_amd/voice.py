@@ -110,8 +110,11 @@ def from_audio(ctx, pcm, semantic=None) -> VoicePrompt:
     return VoicePrompt(semantic, codes[:2].T, codes[:8].T)
 
 
-def from_audio_native(ctx, pcm) -> VoicePrompt:
+def from_audio_native(ctx, pcm, rate: int = 24000) -> VoicePrompt:
     """The same voice prompt made by ONE native call (ctx.voice_from_audio, bark_hip_voice_from_audio): the resampler runs on the device in f32 under rule
     C13r instead of resample_24k_to_16k above, so the semantic ids may differ from from_audio's on undecided frames; a recording longer than 20 s is used
-    from its last 480 000 samples on.  ValueError where the call refuses."""
+    from its last 480 000 samples on.  rate: the recording's own rate - one of 8000, 12000, 16000, 22050, 32000, 44100, 48000 is brought to 24 kHz first by
+    ctx.resample (rule C14r, bark_hip_resample).  ValueError where a call refuses."""
+    if rate != 24000:
+        pcm = ctx.resample(pcm, rate, 24000)
     return VoicePrompt(*ctx.voice_from_audio(pcm))

@@ -152,6 +152,38 @@ BARK_API int bark_hip_set_voice_from_audio(struct bark_context * bctx, const flo
 /* Device time (us) of ONE resampler launch over n samples, averaged over `iters` launches (hipEvents on the context's stream).  Returns < 0 on error. */
 BARK_API double bark_hip_time_resample(struct bark_context * bctx, int n, int iters);
 
+/* Output rate and sample format (rule C14r): the rational resampler between 24 kHz and 8000, 12000, 16000, 22050, 32000, 44100 or
+ * 48000 Hz (24000 on at least one side; rate_in == rate_out == 24000 is the identity: no filter runs), and the formats f32, s16 and G.711 mu-law.
+ * With g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g: c = 0.99 min(1, L / M), W = 6 / c, HALF = ceil(W) + 1, 2 HALF taps per phase,
+ * h[p][j] = c sinc(c u) cos^2(pi u / (2 W)) for |u| < W else 0, u = p / L - j, j = -HALF + 1 .. HALF - double precision, rounded once to f32 (24000 -> 16000:
+ * the committed table of bark_hip_resample_taps).  Output m: base = floor(m M / L), phase = (m M) mod L, one fmaf chain from +0 over x[base + j] h[phase][j]
+ * in ascending j, samples outside the recording +0, no renormalisation; n_out = ceil(n L / M).
+ * Formats, by definition format(resample_f32(x)): s16 = rintf(y * 32768) (ties to even) clamped to [-32768, 32767] - |y| reaches 1.87 for |x| <= 1, so the
+ * clamp is a real case; mu-law from that s16 value s: sign = s < 0 ? 0x80 : 0, mag = min(|s|, 32635) + 132, e = floor(log2 mag) - 7,
+ * man = (mag >> (e + 3)) & 15, byte = ~(sign | e << 4 | man) & 0xFF (0 -> 0xFF, -1 -> 0x7F, 32767 -> 0x80, -32768 -> 0x00). */
+enum bark_hip_sample_format { BARK_HIP_SAMPLE_F32 = 0, BARK_HIP_SAMPLE_S16 = 1, BARK_HIP_SAMPLE_MULAW = 2 };
+struct bark_hip_audio_format { int32_t sample_rate; int32_t sample_format; };
+/* n_out for n samples (n itself for the identity), or -1: an unsupported pair, n < 0.  Needs no context. */
+BARK_API int bark_hip_resample_out_len(int n, int rate_in, int rate_out);
+/* The pair's table out[p * 2 HALF + (j + HALF - 1)] and lmh = {L, M, HALF}; returns L * 2 HALF, or -1: an unsupported pair, the identity (it has no
+ * table), capacity (in floats) too small.  out may be NULL with capacity 0 to read lmh alone (returns the count).  Needs no context. */
+BARK_API int bark_hip_resample_table(int rate_in, int rate_out, float * out, int capacity, int32_t lmh[3]);
+/* One recording in f32: n samples at rate_in -> n_out samples at rate_out.  Returns n_out, or -1 (the context stays usable): n < 1, n > 1 310 720, a
+ * sample that is not finite, an unsupported pair, capacity (in floats) < n_out. */
+BARK_API int bark_hip_resample(struct bark_context * bctx, const float * pcm, int n, int rate_in, int rate_out, float * out, int capacity);
+/* count <= 64 segments at rate_in in ONE launch -> their results at to->sample_rate in to->sample_format back to back in out_concat, n_out[i] samples each
+ * (n_out may be NULL); bit-identical to count single calls.  Returns the bytes written, or -1 as above (also: a format outside 0 .. 2, capacity_bytes too small). */
+BARK_API int bark_hip_resample_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, int rate_in,
+                                    const struct bark_hip_audio_format * to, void * out_concat, int capacity_bytes, int32_t * n_out);
+/* The last bark_generate_audio result (24 kHz f32, bark_get_audio_data - which stays what it was) in another rate / format: returns the byte count,
+ * -(2 + bytes) if capacity_bytes is too small (out may then be NULL), -1 (no audio held, an unsupported format).  bark_hip_batch_audio_as: the same for
+ * utterance i of the context's last job (bark_hip_batch_audio stays what it was). */
+BARK_API int bark_hip_get_audio_as(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes);
+BARK_API int bark_hip_batch_audio_as(struct bark_context * bctx, int i, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes);
+/* Device time (us) of ONE launch of the rational resampler over n samples of one of the 14 pairs with a filter, with the format's epilogue, averaged over
+ * `iters` launches (hipEvents on the context's stream).  Returns < 0 on error. */
+BARK_API double bark_hip_time_resample_pair(struct bark_context * bctx, int n, int rate_in, int rate_out, int sample_format, int iters);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);
@@ -281,6 +313,15 @@ BARK_API int64_t bark_hip_batcher_submit_filtered(struct bark_hip_batcher * b, c
 BARK_API int64_t bark_hip_batcher_submit_voiced(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
                                                 const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice);
 BARK_API int bark_hip_batcher_wait(struct bark_hip_batcher * b, int64_t ticket, float * pcm, int capacity);
+/* A request whose answer comes in another rate / format (bark_hip_audio_format; -1 for an unsupported one).  The worker thread owns the context, so the
+ * conversion happens there, behind the job: one bark_hip_resample_many per distinct format among the job's requests.  fmt == NULL or {24000, F32}: the
+ * path of bark_hip_batcher_submit_voiced - no further launch, the same bits.  bark_hip_batcher_wait_bytes: as bark_hip_batcher_wait, in bytes of the
+ * request's format (any request, f32 ones included): the byte count, -1, or -(2 + bytes) with the ticket still valid.  bark_hip_batcher_wait on a ticket
+ * whose format is not {24000, F32} returns -1 and leaves the ticket valid. */
+BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                            const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
+                                            const struct bark_hip_audio_format * fmt);
+BARK_API int bark_hip_batcher_wait_bytes(struct bark_hip_batcher * b, int64_t ticket, void * out, int capacity_bytes);
 BARK_API void bark_hip_batcher_stats(struct bark_hip_batcher * b, int * n_batches, int * n_requests, int * largest_batch);
 /* requests that joined a job that was already running (continuous admission: while the semantic stage of a job has free slots, requests
  * arriving in the meantime are taken along, up to max_batch per job) */
