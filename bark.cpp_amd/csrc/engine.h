@@ -19,8 +19,46 @@
 #include <string>
 #include <vector>
 
+struct bark_context;
+
 namespace barkhip {
 
+// ---- owners: each releases what it holds, so neither the context's destructor nor a throwing call lists handles ----
+// A captured graph.  Move-only: state that holds one cannot be copied by accident (a clone captures its own).
+struct GraphExec {
+    GraphExec() = default;
+    explicit GraphExec(hipGraphExec_t exec) : e(exec) {}
+    GraphExec(GraphExec && o) noexcept : e(o.e) { o.e = nullptr; }
+    GraphExec & operator=(GraphExec && o) noexcept { if (this != &o) { reset(); e = o.e; o.e = nullptr; } return *this; }
+    ~GraphExec() { reset(); }
+    void reset() { if (e) (void) hipGraphExecDestroy(e); e = nullptr; }
+    explicit operator bool() const { return e != nullptr; }
+    hipGraphExec_t get() const { return e; }
+private:
+    hipGraphExec_t e = nullptr;
+};
+// An event, created by its first record() (engine_internal.h).
+struct Event {
+    Event() = default;
+    Event(Event && o) noexcept : e(o.e) { o.e = nullptr; }
+    Event & operator=(Event && o) noexcept { if (this != &o) { reset(); e = o.e; o.e = nullptr; } return *this; }
+    ~Event() { reset(); }
+    void reset() { if (e) (void) hipEventDestroy(e); e = nullptr; }
+    void record(hipStream_t s);
+    hipEvent_t get() const { return e; }
+private:
+    hipEvent_t e = nullptr;
+};
+// Scratch that grows on demand: a VIEW of n elements at p.  The allocation belongs to the context (bark_context::allocs, as every dev_alloc), and one
+// that a larger one has superseded stays there until the context is freed.  Trivially copyable: bark_context::Batch and HubScratch are copied by value.
+template <typename T> struct DevBuf {
+    T * p = nullptr; size_t n = 0;
+    // a fresh allocation of exactly `count` elements, exactly when count > n (engine_internal.h).  Every buffer keeps its own n, so a group that grows
+    // together (one reserve each, from one call) stays consistent when an allocation in the middle of it throws.
+    void reserve(bark_context * ctx, size_t count);
+};
+
+// Immutable after load: clones copy it with a plain assignment and share the weights behind the pointers.
 struct GptModel {
     GptHparams hp;
     const half_t * wte[8] = {};
@@ -37,15 +75,19 @@ struct GptModel {
         const float * attn_b = nullptr, * proj_b = nullptr, * fc_b = nullptr, * mproj_b = nullptr;
     };
     std::vector<Layer> layers;
+    size_t kv_layer_stride = 0;                         // floats per layer of a KV cache of this model - the context's own (GptRun) or a batch slot's (0 for the
+                                                        // fine model's shared scratch)
+};
+// What one context runs a GptModel with: its KV cache and its captured decode steps (bark_context::gpt_run, one per model)
+struct GptRun {
     float * kcache = nullptr, * vcache = nullptr;       // [L][H][16][P][4] / [L][H][P][64] f32; fine model: L = 1 scratch
     float * vtcache = nullptr;                          // second copy of V in the K layout [L][H][16][P][4] (semantic / coarse): the decode attention
                                                         // reads 4 value dims of consecutive keys as one contiguous stream
-    size_t kv_layer_stride = 0;                         // floats per layer (0 for the fine model's shared scratch)
     // layers -> LM head -> sample + embedding of the next token; [ng]: variant whose kernels request the keys below 256 ng without
     // waiting for the context length (the host knows how many rows the cache holds when it launches a step)
-    hipGraphExec_t decode_graph[5] = {};
-    hipGraphExec_t decode_graph8[5] = {};               // eight such steps in one graph: one launch gap per eight tokens
-    hipGraphExec_t bench_graph = nullptr;               // same, without advancing n_past (timing hook)
+    GraphExec decode_graph[5];
+    GraphExec decode_graph8[5];                         // eight such steps in one graph: one launch gap per eight tokens
+    GraphExec bench_graph;                              // same, without advancing n_past (timing hook)
 };
 
 struct CodecModel {
@@ -100,16 +142,35 @@ using VoicePtr = std::shared_ptr<const VoicePrompt>;
 
 }  // namespace barkhip
 
+// What the members of a context live in.  The base of bark_context, so it is destroyed after every member, which gives the release order of a context:
+// ~bark_context selects the device, the members release their graphs and events (and, behind those, the last holder its share of the weights and the
+// semantic encoder), then this frees the device allocations, the pinned host memory and, last, the stream.
+struct bark_context_memory {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<void *> allocs;                         // every dev_alloc: scratch, caches and what a grown DevBuf has left behind
+    std::vector<void *> pinned;                         // every host_alloc
+    bark_context_memory() = default;
+    bark_context_memory(const bark_context_memory &) = delete;
+    bark_context_memory & operator=(const bark_context_memory &) = delete;
+    ~bark_context_memory();
+};
+
 // The opaque handle of bark.h.
-struct bark_context {
+struct bark_context : bark_context_memory {
+    // What a context shares with its clones, immutable after load: the weight slab with the codec codebooks (bark_hip_clone_context: replicas on one
+    // GPU stream the same bytes) and the semantic encoder.  Declared first, so the last context that holds them frees them behind its graphs and events.
+    struct SharedWeights { void * slab = nullptr; void * codebooks = nullptr; std::vector<void *> extra; int device = 0; ~SharedWeights(); };
+    std::shared_ptr<SharedWeights> weights;
+    std::shared_ptr<const barkhip::HubertModel> hub;
+
     bark_context_params params;
     std::mt19937 rng;
 
     barkhip::Vocab vocab;
     barkhip::GptModel gpt[3];
+    barkhip::GptRun gpt_run[3];
     barkhip::CodecModel codec;
-    int device = 0;
-    hipStream_t stream = nullptr;
     bool use_graph = true;
     // Order of the fine model's weight products on f16 model files.  0 (default policy): C1 - the restated reference order, on the
     // f32 matrix cores - for bark_generate_audio and the stage-level entry points, C1m - the f16 matrix cores' own accumulation - inside lock-step jobs
@@ -119,12 +180,7 @@ struct bark_context {
     int fast_gemm = 0;                   // BARK_HIP_FAST_GEMM=1: N > 1 products on the f16 matrix cores in hardware accumulation order (non-canonical, tolerance mode)
     int decode_ng = 4;                                  // key groups (of 256) the decode kernels being enqueued may assume: ctx <= 256 ng
 
-    // device memory.  The weight slab (and the codec codebooks) are immutable after load and shared by every
-    // context cloned from this one (bark_hip_clone_context): replicas on one GPU stream the same bytes.
-    struct SharedWeights { void * slab = nullptr; void * codebooks = nullptr; std::vector<void *> extra; int device = 0; ~SharedWeights(); };
-    std::shared_ptr<SharedWeights> weights;
     size_t weight_bytes = 0;
-    std::vector<void *> allocs;                         // everything else (freed in destroy)
     std::vector<std::pair<void *, size_t>> guarded;     // BARK_HIP_GUARD: {base of the allocation, bytes between its two guard bands}
     // GPT scratch
     float * x = nullptr, * q = nullptr, * logits = nullptr;
@@ -151,22 +207,21 @@ struct bark_context {
     uint16_t * d_gelu_lut = nullptr;
     int max_E = 0, max_H = 0, P = 1024;
     // codec scratch (grown on demand)
-    float * cbuf[3] = {nullptr, nullptr, nullptr}; size_t cbuf_elems = 0;
-    barkhip::half_t * cbuf_hh[3] = {nullptr, nullptr, nullptr};
-    float * c_gi = nullptr, * c_cell = nullptr, * c_cell2 = nullptr; barkhip::half_t * c_hseq_h = nullptr, * c_xt_h = nullptr, * c_hseq2_h = nullptr; size_t c_T = 0;
-    int32_t * d_codes = nullptr; size_t d_codes_elems = 0;
-    hipGraphExec_t fine_graphs[16] = {};                // one captured forward pass + pick per predicted codebook, [8 * (products in C1m) + codebook]
+    barkhip::DevBuf<float> cbuf[3];                     // all six of one size
+    barkhip::DevBuf<barkhip::half_t> cbuf_hh[3];
+    barkhip::DevBuf<float> c_gi, c_cell, c_cell2; barkhip::DevBuf<barkhip::half_t> c_hseq_h, c_xt_h, c_hseq2_h;       // LSTM rows for c_gi.n / (4 D) frames; the cells
+    barkhip::DevBuf<int32_t> d_codes;
+    barkhip::GraphExec fine_graphs[16];                 // one captured forward pass + pick per predicted codebook, [8 * (products in C1m) + codebook]
     int * d_lstm_t = nullptr;                           // step counter of the replayed LSTM block
-    int * d_codec_T = nullptr;                          // frame counts of the utterances being decoded and their prefix sums (CodecBatch)
-    struct LstmGraph { hipGraphExec_t exec = nullptr; int B = 0; const float * out = nullptr; const float * gi = nullptr; } lstm_graph;    // 64 wave-front steps
+    barkhip::DevBuf<int> d_codec_T;                     // frame counts of the utterances being decoded and their prefix sums (CodecBatch)
+    struct LstmGraph { barkhip::GraphExec exec; int B = 0; const float * out = nullptr; const float * gi = nullptr; } lstm_graph;    // 64 wave-front steps
     LstmGraph lstm_graph_enc;                           // the same block with the encoder's weights and row table: a slot of its own, so encode / decode never replay each other's capture
-    int * d_enc_T = nullptr;                            // encoder: row counts and prefix sums of the recordings at each of its five stages ([5][80], laid out as d_codec_T)
-    float * d_pcm = nullptr; size_t d_pcm_elems = 0;    // encoder: the recordings' samples back to back
-    hipEvent_t enc_ev[2] = {nullptr, nullptr}; double enc_device_us = -1.0;      // events around the kernels of an encode call, and what the last call took between them
+    barkhip::DevBuf<int> d_enc_T;                       // encoder: row counts and prefix sums of the recordings at each of its five stages ([5][80], laid out as d_codec_T)
+    barkhip::DevBuf<float> d_pcm;                       // encoder: the recordings' samples back to back
+    barkhip::Event enc_ev[2]; double enc_device_us = -1.0;      // events around the kernels of an encode call, and what the last call took between them
     const float * enc_latents = nullptr; int enc_latent_rows = 0;      // the latents [rows][hidden_dim] of the last encode call, until the next codec call of this context
     LstmGraph lstm_graph_hub;                           // ... and with the token head's (semantic encoder)
-    // semantic encoder: the model (shared with clones) and this context's scratch for kHubMaxFrames frames (allocated with the first use)
-    std::shared_ptr<const barkhip::HubertModel> hub;
+    // semantic encoder: this context's scratch for kHubMaxFrames frames (allocated with the first use)
     struct HubScratch {
         bool ready = false;
         float * pcm = nullptr; barkhip::half_t * pcm_h = nullptr;            // [n_max]
@@ -178,15 +233,15 @@ struct bark_context {
         float * gi = nullptr, * c1 = nullptr, * c2 = nullptr, * out2 = nullptr; barkhip::half_t * h1 = nullptr, * h2 = nullptr;    // token head
         float * logits = nullptr; int32_t * ids = nullptr;                  // [T][n_classes], [T]
         int * rows = nullptr;                                                // [8][80] row tables of the conv stages (CodecBatch)
-        float * tap = nullptr; size_t tap_elems = 0;                        // parity tap 0 in f32 (grown on demand)
+        barkhip::DevBuf<float> tap;                                          // parity tap 0 in f32 (grown on demand)
     } hubs;
-    hipEvent_t hub_ev[2] = {nullptr, nullptr}; double hub_device_us = -1.0;
-    float * rs_in = nullptr, * rs_out = nullptr; size_t rs_elems = 0;      // resampler (C13r): the recording and its 16 kHz form (grown on demand)
+    barkhip::Event hub_ev[2]; double hub_device_us = -1.0;
+    barkhip::DevBuf<float> rs_in, rs_out;               // resampler (C13r): the recording and its 16 kHz form (grown on demand)
     // rational resampler (C14r): the taps of every pair used so far (uploaded once per pair), the segments' samples back to back, their results in the
     // requested format (both grown on demand) and the segment table [5][kResampleMaxSegments + 1]
     std::map<std::pair<int, int>, const float *> rp_taps;
-    float * rp_in = nullptr; size_t rp_in_elems = 0; void * rp_out = nullptr; size_t rp_out_bytes = 0; int * rp_seg = nullptr;
-    struct CodecGraph { hipGraphExec_t exec = nullptr; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
+    barkhip::DevBuf<float> rp_in; barkhip::DevBuf<uint8_t> rp_out; barkhip::DevBuf<int> rp_seg;
+    struct CodecGraph { barkhip::GraphExec exec; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
     // the row scratch of the all-slots prefill; FineBatch below holds the scratch of the side-by-side fine passes
@@ -202,7 +257,7 @@ struct bark_context {
         size_t ld_logits = 0;
         float * slot_par = nullptr;                      // the slots' own temperatures [cap], min_eos_p [cap] (bark_hip_request_params) and top_p [cap]
         int32_t * slot_top_k = nullptr;                  // the slots' own top_k [cap] (bark_hip_sampling_filter)
-        // pinned host memory (hipHostMalloc, freed by the context): where the sampled ids [cap][2048] and the states [cap] of the live slots land at
+        // pinned host memory (host_alloc): where the sampled ids [cap][2048] and the states [cap] of the live slots land at
         // a poll / window end, and the staging rows of the states uploaded at a window start
         int32_t * h_ids = nullptr; barkhip::StepState * h_state = nullptr, * h_state_in = nullptr;
         // window prompts of all slots in ONE pass (batch_prefill_many): row scratch for cap * P rows, the prompts' ids, the sequence table
@@ -211,8 +266,9 @@ struct bark_context {
     } batch;
     std::vector<float> h_slot_par;                      // host mirror of batch.slot_par
     std::vector<int32_t> h_slot_top_k;                  // host mirror of batch.slot_top_k
-    std::vector<std::pair<std::string, hipEvent_t>> * step_marks = nullptr;      // engine_profile_lock_step: events behind the launch sites of a lock step
-    std::map<int, hipGraphExec_t> batch_graphs;         // captured lock steps by (model, active slots, kinds of sampling among them)
+    struct StepMark { std::string name; barkhip::Event at; };
+    std::vector<StepMark> * step_marks = nullptr;       // engine_profile_lock_step: events behind the launch sites of a lock step
+    std::map<int, barkhip::GraphExec> batch_graphs;       // captured lock steps by (model, active slots, kinds of sampling among them)
     // fine windows of several utterances in one forward pass (engine_fine_many): rows = cap * 1024
     struct FineBatch {
         int cap = 0;

@@ -30,9 +30,6 @@ double weight_bytes_per_element(const GptModel & m) {
     if (m.q4) return quant_formats()[m.layers[0].attn_q.qt].block_bytes / 32.0;
     return 2.0;
 }
-float * layer_k(const GptModel & m, int l) { return m.kcache + m.kv_layer_stride * (size_t) l; }
-float * layer_v(const GptModel & m, int l) { return m.vcache + m.kv_layer_stride * (size_t) l; }
-float * layer_vt(const GptModel & m, int l) { return m.vtcache ? m.vtcache + m.kv_layer_stride * (size_t) l : nullptr; }
 
 // The fine model's products of an f16 file: C1 chains on the f32 matrix cores (gemm_kernel; the restated reference order, the oracle's default) or C1m on
 // the f16 matrix cores (gemm_f16_tile_kernel; the oracle follows with set_fine_mfma(True)) - bark_context::fine_order.  Default policy: C1 for
@@ -77,8 +74,8 @@ void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float *
     const int Z = seq > 0 ? N / seq : 1;
     const bool flash = c->fast_gemm && fast && !causal && pos0 == 0 && N % 1024 == 0 && (seq == 0 || seq == 1024) && (rbp || (!kbase && !vbase)) && rb.q16 && E % 64 == 0;
     // kbase / vbase: another utterance slot's cache (batched decode) or the fine batch's; default: the context's own cache
-    auto layer_k = [&](const GptModel & mm, int l) { return (kbase ? kbase : mm.kcache) + mm.kv_layer_stride * (size_t) l; };
-    auto layer_v = [&](const GptModel & mm, int l) { return (vbase ? vbase : mm.vcache) + mm.kv_layer_stride * (size_t) l; };
+    auto layer_k = [&](const GptModel & mm, int l) { return (kbase ? kbase : run_of(c, mm).kcache) + mm.kv_layer_stride * (size_t) l; };
+    auto layer_v = [&](const GptModel & mm, int l) { return (vbase ? vbase : run_of(c, mm).vcache) + mm.kv_layer_stride * (size_t) l; };
     // the LayerNorm in front of a product is a launch of its own here.  f16 weights: activations are rounded to f16 rows (xn / att / hbuf); q4_0
     // weights: f32 rows quantised to q8_0 (xq8 / xd8)
     auto ln_rows = [&](LinArgs & a) {
@@ -97,7 +94,7 @@ void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float *
         ln_rows(a);
         rows_in(a, rb.xn, c->xn32);
         a.q = rb.q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.pos0 = pos0;
-        if (!kbase && !vbase) a.vt = detail::layer_vt(m, l);      // the context's own cache keeps the K-layout copy of V too
+        if (!kbase && !vbase) a.vt = layer_vt(c, m, l);      // the context's own cache keeps the K-layout copy of V too
         a.seq = seq; a.kv_slot_stride = kv_seq_stride; a.seqtab = seqtab;
         if (flash) {
             // tolerance route of the fine model: q / k / v leave the product as the f16 operands of the flash attention (no KV cache)
@@ -137,17 +134,17 @@ void run_layers_decode(bark_context * c, GptModel & m) {
     const int E = m.hp.n_embd, H = m.hp.n_head, P = c->P;
     hipStream_t s = c->stream;
     for (int l = 0; l < m.hp.n_layer; l++) {
-        const bool ps = !(crosscheck_mask() & 4) && !m.w32 && P == 1024 && m.vtcache && E <= 1024;
+        const bool ps = !(crosscheck_mask() & 4) && !m.w32 && P == 1024 && run_of(c, m).vtcache && E <= 1024;
         LinArgs a = layer_product(c, m, l, OP_QKV);
-        a.x_f32 = c->x; a.q = c->q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.vt = layer_vt(m, l); a.st = c->d_state;
+        a.x_f32 = c->x; a.q = c->q; a.kc = layer_k(c, m, l); a.vc = layer_v(c, m, l); a.vt = layer_vt(c, m, l); a.st = c->d_state;
         // f16 weights: the QKV kernel also forms the partial scores of the cached keys (C2 blocks), attn_ps_kernel finishes them
         if (ps) { a.ps = c->ps; a.knew = c->knew; a.ng = c->decode_ng; }
         BARK_TRACE_SET(c, a, (a.M + 3) / 4 + 4 * (E / 4));        // room for all four copies of the q workgroups
         launch_linear(s, a);
         AttnDecodeArgs at;
-        at.q = c->q; at.kc = layer_k(m, l); at.vc = layer_v(m, l); at.H = H; at.P = P; at.st = c->d_state; at.att = c->att;
+        at.q = c->q; at.kc = layer_k(c, m, l); at.vc = layer_v(c, m, l); at.H = H; at.P = P; at.st = c->d_state; at.att = c->att;
         at.att32 = m.q4 ? c->att32 : nullptr;
-        if (ps) { at.ps = c->ps; at.knew = c->knew; at.ng = c->decode_ng; at.vt = layer_vt(m, l); }
+        if (ps) { at.ps = c->ps; at.knew = c->knew; at.ng = c->decode_ng; at.vt = layer_vt(c, m, l); }
         BARK_TRACE_SET(c, at, 8 * 16 * ((H + 7) / 8) * 16);      // up to 16 slices per head, 16 waves per workgroup
         launch_attn_decode(s, at);
         LinArgs p = layer_product(c, m, l, OP_PROJ);
@@ -274,31 +271,31 @@ void enqueue_decode_step(bark_context * c, const StageCfg & s, bool sample, int 
     if (sample) run_sample(c, s, n_past_add, prescale);
 }
 
-hipGraphExec_t capture_graph(hipStream_t s, const std::function<void()> & body) {
+GraphExec capture_graph(hipStream_t s, const std::function<void()> & body) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     try { body(); }
     catch (...) { hipGraph_t g2 = nullptr; (void) hipStreamEndCapture(s, &g2); if (g2) (void) hipGraphDestroy(g2); throw; }
     HIP_OK(hipStreamEndCapture(s, &graph));
-    HIP_OK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    const hipError_t err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void) hipGraphDestroy(graph);
-    return exec;
+    HIP_OK(err);
+    return GraphExec(exec);
 }
 
 double time_on_stream_us(bark_context * c, const std::function<void()> & body) {
-    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void) hipEventDestroy(e); } } e0, e1;
-    HIP_OK(hipEventCreate(&e0.e)); HIP_OK(hipEventCreate(&e1.e));
-    HIP_OK(hipEventRecord(e0.e, c->stream));
+    Event e0, e1;
+    e0.record(c->stream);
     body();
-    HIP_OK(hipEventRecord(e1.e, c->stream));
-    HIP_OK(hipEventSynchronize(e1.e));
+    e1.record(c->stream);
+    HIP_OK(hipEventSynchronize(e1.get()));
     float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0.e, e1.e));
+    HIP_OK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     return (double) ms * 1000.0;
 }
 
-hipGraphExec_t capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps, int ng) {
+GraphExec capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps, int ng) {
     struct Restore { bark_context * c; int ng; ~Restore() { c->decode_ng = ng; } } restore{c, c->decode_ng};      // also when a launch throws
     c->decode_ng = std::max(1, std::min(ng, 4));
     return capture_graph(c->stream, [&] { for (int i = 0; i < n_steps; i++) enqueue_decode_step(c, s, true, n_past_add, false); });
@@ -310,7 +307,7 @@ hipGraphExec_t capture_decode(bark_context * c, const StageCfg & s, int n_past_a
 // The graph variant is picked by the number of 256-key groups the launch can touch: its kernels request those keys' partial scores
 // and value rows at wave launch instead of waiting ~0.5 us for the context length to arrive from the device-resident state.
 void decode_steps_greedy(bark_context * c, const StageCfg & s, int n, int n_past) {
-    GptModel & m = c->gpt[s.which];
+    GptRun & run = c->gpt_run[s.which];
     if (!c->use_graph) {
         struct Restore { bark_context * c; ~Restore() { c->decode_ng = 4; } } restore{c};      // also when a launch throws
         for (int k = 0; k < n; k++) { c->decode_ng = std::min(4, (n_past + k + 256) / 256); enqueue_decode_step(c, s, true, 1, false); }
@@ -320,9 +317,9 @@ void decode_steps_greedy(bark_context * c, const StageCfg & s, int n, int n_past
     while (k < n) {
         const int g = n - k >= 8 ? 8 : 1;
         const int ng = std::min(4, (n_past + k + g + 255) / 256);      // ctx of the last step of this launch = n_past + k + g
-        hipGraphExec_t & e = g == 8 ? m.decode_graph8[ng] : m.decode_graph[ng];
+        GraphExec & e = g == 8 ? run.decode_graph8[ng] : run.decode_graph[ng];
         if (!e) e = capture_decode(c, s, 1, g, ng);
-        HIP_OK(hipGraphLaunch(e, c->stream));
+        HIP_OK(hipGraphLaunch(e.get(), c->stream));
         c->stats.graph_replays++;
         k += g;
     }
@@ -848,9 +845,9 @@ std::vector<int32_t> engine_fine(bark_context * c, const std::vector<int32_t> & 
                     else launch_sample_rows_multinomial(c->stream, c->logits, cs, 1024, cs, p.fine_temp, c->d_u + (size_t) (nn - nc) * 1024, pick_dst, 1, c->d_state, c->d_fine_rel);
                 };
                 if (c->use_graph) {
-                    hipGraphExec_t & g = c->fine_graphs[nn + (fine_products_on_f16_mfma(c, m, false) ? 8 : 0)];
+                    GraphExec & g = c->fine_graphs[nn + (fine_products_on_f16_mfma(c, m, false) ? 8 : 0)];
                     if (!g) g = capture_graph(c->stream, enqueue);
-                    HIP_OK(hipGraphLaunch(g, c->stream));
+                    HIP_OK(hipGraphLaunch(g.get(), c->stream));
                     c->stats.graph_replays++;
                 } else {
                     enqueue();

@@ -85,9 +85,9 @@ void ensure_batch(bark_context * c, int B) {
     bb.slot_top_k = dev_alloc<int32_t>(c, (size_t) B);
     c->h_slot_top_k.assign((size_t) B, 0);
     // pinned landing zone of the per-window / per-poll read-back (ids of all slots + their states): read_back() below
-    HIP_OK(hipHostMalloc((void **) &bb.h_ids, (size_t) B * 2048 * sizeof(int32_t), hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void **) &bb.h_state, (size_t) B * sizeof(StepState), hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void **) &bb.h_state_in, (size_t) B * sizeof(StepState), hipHostMallocDefault));
+    bb.h_ids = host_alloc<int32_t>(c, (size_t) B * 2048);
+    bb.h_state = host_alloc<StepState>(c, (size_t) B);
+    bb.h_state_in = host_alloc<StepState>(c, (size_t) B);
     bb.cap = B;
 }
 
@@ -163,8 +163,8 @@ void enqueue_batch_step(bark_context * c, const StageCfg & s, int B, const bark_
     // time line of a lock step (engine_profile_lock_step): an event behind every launch site, named
     auto mark = [&](const char * name) {
         if (!c->step_marks) return;
-        hipEvent_t e; HIP_OK(hipEventCreate(&e)); HIP_OK(hipEventRecord(e, st));
-        c->step_marks->emplace_back(name, e);
+        c->step_marks->push_back({name, Event()});
+        c->step_marks->back().at.record(st);
     };
     float * kc0 = bb.kc[s.which], * vc0 = bb.vc[s.which];
     const size_t slot = bb.slot_stride[s.which];
@@ -248,9 +248,9 @@ void batch_step(bark_context * c, const StageCfg & s, int B) {
         // one captured lock step per (model, active slots, kinds of sampling among them); a batch that shrinks slot by slot meets each
         // size once per context (the executables are kept)
         const int key = s.which | (B << 1) | (slot_kinds(c, 0, B) << 12);
-        hipGraphExec_t & exec = c->batch_graphs[key];
+        GraphExec & exec = c->batch_graphs[key];
         if (!exec) exec = capture_graph(c->stream, [&] { enqueue_batch_step(c, s, B, bb); });
-        HIP_OK(hipGraphLaunch(exec, c->stream));
+        HIP_OK(hipGraphLaunch(exec.get(), c->stream));
         c->stats.graph_replays++;
     } else {
         enqueue_batch_step(c, s, B, bb);
@@ -417,11 +417,10 @@ double engine_time_slots(bark_context * c, int which, int op, int B, int kind, i
         if (kind == 0) launch_linear(c->stream, a); else launch_linear_slots(c->stream, a);
     };
     const int per_graph = 48;
-    hipGraphExec_t exec = capture_graph(c->stream, [&] { for (int i = 0; i < per_graph; i++) launch(i % m.hp.n_layer); });
-    HIP_OK(hipGraphLaunch(exec, c->stream));
+    const GraphExec exec = capture_graph(c->stream, [&] { for (int i = 0; i < per_graph; i++) launch(i % m.hp.n_layer); });
+    HIP_OK(hipGraphLaunch(exec.get(), c->stream));
     const int reps = std::max(1, iters / per_graph);
-    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec, c->stream)); });
-    (void) hipGraphExecDestroy(exec);
+    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec.get(), c->stream)); });
     return us / (reps * per_graph);
 }
 
@@ -452,25 +451,24 @@ void engine_profile_lock_step(bark_context * c, int which, int B, int ctxlen, in
     reset();
     enqueue_batch_step(c, s, B, bb);                               // warm-up (first-use costs)
     reset();
-    std::vector<std::pair<std::string, hipEvent_t>> marks;
+    std::vector<bark_context::StepMark> marks;
     std::vector<double> acc;
     std::vector<std::string> names;
     for (int r = 0; r < reps; r++) {
-        marks.clear();
-        hipEvent_t e0; HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventRecord(e0, c->stream));
+        marks.clear();                                               // the events of the previous repetition go with their marks
+        Event e0;
+        e0.record(c->stream);
         c->step_marks = &marks;
         try { enqueue_batch_step(c, s, B, bb); } catch (...) { c->step_marks = nullptr; throw; }
         c->step_marks = nullptr;
         HIP_OK(hipStreamSynchronize(c->stream));
-        if (acc.empty()) { acc.assign(marks.size(), 0.0); for (auto & mk : marks) names.push_back(mk.first); }
-        hipEvent_t prev = e0;
+        if (acc.empty()) { acc.assign(marks.size(), 0.0); for (auto & mk : marks) names.push_back(mk.name); }
+        hipEvent_t prev = e0.get();
         for (size_t i = 0; i < marks.size(); i++) {
-            float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, prev, marks[i].second));
+            float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, prev, marks[i].at.get()));
             acc[i] += (double) ms * 1000.0;
-            prev = marks[i].second;
+            prev = marks[i].at.get();
         }
-        (void) hipEventDestroy(e0);
-        for (auto & mk : marks) (void) hipEventDestroy(mk.second);
     }
     out.clear();
     for (size_t i = 0; i < acc.size(); i++) out.emplace_back(names[i], acc[i] / reps);
@@ -611,7 +609,7 @@ struct JobTail {
         if (th.joinable()) th.join();
         tail_scope.reset();
     }
-    static void drop_fine_graphs_of(bark_context * x) { for (auto & g : x->fine_graphs) if (g) { (void) hipGraphExecDestroy(g); g = nullptr; } }
+    static void drop_fine_graphs_of(bark_context * x) { for (auto & g : x->fine_graphs) g.reset(); }
     void drop_fine_graphs() { drop_fine_graphs_of(t); }
     void push(const std::vector<int> & utts) {
         if (utts.empty()) return;

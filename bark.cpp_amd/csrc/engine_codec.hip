@@ -18,19 +18,11 @@ using namespace barkhip::detail;
 namespace {
 // scratch shared by decode and encode: three f32 and three f16 activation buffers of `need` elements, the LSTM's rows for Ts frames, its cells, the row tables
 void ensure_codec_scratch(bark_context * c, size_t need, int Ts, int D) {
-    if (need > c->cbuf_elems) {
-        for (auto & b : c->cbuf) b = dev_alloc<float>(c, need);
-        for (auto & b : c->cbuf_hh) b = dev_alloc<half_t>(c, need);
-        c->cbuf_elems = need;
-    }
-    if ((size_t) Ts > c->c_T) {
-        c->c_gi = dev_alloc<float>(c, (size_t) Ts * 4 * D);
-        c->c_hseq_h = dev_alloc<half_t>(c, (size_t) Ts * D);
-        c->c_xt_h = dev_alloc<half_t>(c, (size_t) Ts * D);
-        c->c_hseq2_h = dev_alloc<half_t>(c, (size_t) Ts * D);
-        c->c_T = (size_t) Ts;
-    }
-    if (!c->c_cell) { c->c_cell = dev_alloc<float>(c, (size_t) 32 * D); c->c_cell2 = dev_alloc<float>(c, (size_t) 32 * D); c->d_codec_T = dev_alloc<int>(c, 80); }
+    for (auto & b : c->cbuf) b.reserve(c, need);
+    for (auto & b : c->cbuf_hh) b.reserve(c, need);
+    const size_t rows = (size_t) Ts * D;                         // D is the model's: the four grow together
+    c->c_gi.reserve(c, 4 * rows); c->c_hseq_h.reserve(c, rows); c->c_xt_h.reserve(c, rows); c->c_hseq2_h.reserve(c, rows);
+    c->c_cell.reserve(c, (size_t) 32 * D); c->c_cell2.reserve(c, (size_t) 32 * D); c->d_codec_T.reserve(c, 80);
 }
 
 // 2-layer LSTM (modeling_encodec.py:236-249) over the f16 rows c->c_xt_h [Ts][D] -> out2 [Ts][D] f32 (the skip is the caller's), both layers as a wave
@@ -40,7 +32,7 @@ void ensure_codec_scratch(bark_context * c, size_t need, int Ts, int D) {
 // table (decoder and encoder each own one).
 // `io`: the rows and state buffers (the codec's own by default); the semantic encoder's token head brings its own, and an input width K_in != D
 struct LstmIo { const half_t * x_h; int K_in, D; float * gi, * c1, * c2; half_t * h1, * h2; };
-LstmIo codec_lstm_io(bark_context * c) { return LstmIo{c->c_xt_h, c->codec.D, c->codec.D, c->c_gi, c->c_cell, c->c_cell2, c->c_hseq_h, c->c_hseq2_h}; }
+LstmIo codec_lstm_io(bark_context * c) { return LstmIo{c->c_xt_h.p, c->codec.D, c->codec.D, c->c_gi.p, c->c_cell.p, c->c_cell2.p, c->c_hseq_h.p, c->c_hseq2_h.p}; }
 void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context::LstmGraph & slot, const CodecBatch & cb, int Ts, int Tmax, float * out2, const LstmIo & io) {
     hipStream_t s = c->stream;
     const int D = io.D, B = cb.B;
@@ -58,7 +50,7 @@ void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context
         return;
     }
     constexpr int kBlock = 64;
-    if (slot.exec && (slot.out != out2 || slot.gi != io.gi || slot.B != B)) { (void) hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
+    if (slot.out != out2 || slot.gi != io.gi || slot.B != B) slot.exec.reset();
     if (!slot.exec) {
         slot.exec = capture_graph(s, [&] {
             a.t_base = c->d_lstm_t;
@@ -70,7 +62,7 @@ void run_lstm_pair(bark_context * c, const CodecModel::Lstm * lstm, bark_context
     const int hdr[2] = {0, Tmax};
     HIP_OK(hipMemcpyAsync(c->d_lstm_t, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
     HIP_OK(hipStreamSynchronize(s));                         // hdr is a stack object
-    for (int i0 = 0; i0 <= Tmax; i0 += kBlock) HIP_OK(hipGraphLaunch(slot.exec, s));
+    for (int i0 = 0; i0 <= Tmax; i0 += kBlock) HIP_OK(hipGraphLaunch(slot.exec.get(), s));
 }
 
 // C11q: rvq_encode_kernel writes -1 for a frame in which no distance compared below +inf (a non-finite latent): an error, never a code
@@ -108,21 +100,21 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
     size_t need = (size_t) std::max(cm.hp.hidden_dim, D) * Ts;
     { int ch = D; size_t tt = (size_t) Ts; for (auto & b : cm.blocks) { ch = b.up.cout; tt *= b.up.stride; need = std::max(need, (size_t) ch * tt); } }
     ensure_codec_scratch(c, need, Ts, D);
-    if ((size_t) n_q * Ts > c->d_codes_elems) { c->d_codes = dev_alloc<int32_t>(c, (size_t) n_q * Ts); c->d_codes_elems = (size_t) n_q * Ts; }
+    c->d_codes.reserve(c, (size_t) n_q * Ts);
     for (int b = 0; b < B; b++)
-        HIP_OK(hipMemcpyAsync(c->d_codes + (size_t) n_q * Tpre[(size_t) b], codes[(size_t) b], (size_t) n_q * T[(size_t) b] * 4, hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(c->d_codes.p + (size_t) n_q * Tpre[(size_t) b], codes[(size_t) b], (size_t) n_q * T[(size_t) b] * 4, hipMemcpyHostToDevice, s));
     // device copies of the frame counts and their prefix sums: [0, 32) T, [40, 73) Tpre
     {
         int hdr[80] = {};
         for (int b = 0; b < B; b++) hdr[b] = T[(size_t) b];
         for (int b = 0; b <= B; b++) hdr[40 + b] = Tpre[(size_t) b];
-        HIP_OK(hipMemcpyAsync(c->d_codec_T, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(c->d_codec_T.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
         HIP_OK(hipStreamSynchronize(s));                        // hdr is a stack object
     }
-    CodecBatch cb; cb.T = c->d_codec_T; cb.Tpre = c->d_codec_T + 40; cb.B = B;
+    CodecBatch cb; cb.T = c->d_codec_T.p; cb.Tpre = c->d_codec_T.p + 40; cb.B = B;
     // time-major buffers: three f32 (A / Bf / R) and three f16 (H0 / H1 / H2)
-    float * A = c->cbuf[0], * Bf = c->cbuf[1], * R = c->cbuf[2];
-    half_t * H0 = c->cbuf_hh[0], * H1 = c->cbuf_hh[1], * H2 = c->cbuf_hh[2];
+    float * A = c->cbuf[0].p, * Bf = c->cbuf[1].p, * R = c->cbuf[2].p;
+    half_t * H0 = c->cbuf_hh[0].p, * H1 = c->cbuf_hh[1].p, * H2 = c->cbuf_hh[2].p;
 
     // one convolution over time-major rows: xh [rows_in][cin] f16 -> any of y (f32), yh_raw, yh_elu (f16: what the next operators consume)
     auto conv_args = [&](const half_t * wm, const float * w32, const float * bias, int cin, int cout, int K, int stride, const half_t * xh, int tm_in) {
@@ -139,9 +131,9 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
         launch_conv_tm(s, a);
     };
     // RVQ de-embedding, first conv
-    launch_rvq_gather(s, cm.codebooks, cm.hp.n_bins, cm.hp.hidden_dim, c->d_codes, n_q, Tmax, Ts, A, cb);
+    launch_rvq_gather(s, cm.codebooks, cm.hp.n_bins, cm.hp.hidden_dim, c->d_codes.p, n_q, Tmax, Ts, A, cb);
     launch_act_round(s, A, (size_t) cm.hp.hidden_dim * Ts, 0, H0);
-    conv(cm.init, H0, 1, nullptr, Bf, c->c_xt_h, nullptr);      // Bf = x [row][D]; its f16 image is the LSTM's input
+    conv(cm.init, H0, 1, nullptr, Bf, c->c_xt_h.p, nullptr);      // Bf = x [row][D]; its f16 image is the LSTM's input
     run_lstm_pair(c, cm.lstm, c->lstm_graph, cb, Ts, Tmax, R, codec_lstm_io(c));
     // parity taps are handed out channel-major [C][T'] (one utterance)
     auto grab = [&](int stage, const float * buf, int C, size_t rows) {
@@ -181,12 +173,12 @@ std::vector<std::vector<float>> engine_codec_decode_many(bark_context * c, const
     };
     if (c->use_graph && tap_stage < 0) {
         auto & cg = c->codec_graph;
-        if (cg.exec && (cg.T != T || cg.buf != A)) { (void) hipGraphExecDestroy(cg.exec); cg.exec = nullptr; }
+        if (cg.T != T || cg.buf != A) cg.exec.reset();
         if (!cg.exec) {
             cg.exec = capture_graph(s, [&] { tail(false); });
             cg.T = T; cg.buf = A; cg.out = pcm_dev; cg.tmul = tmul;
         }
-        HIP_OK(hipGraphLaunch(cg.exec, s));
+        HIP_OK(hipGraphLaunch(cg.exec.get(), s));
         c->stats.graph_replays++;
         pcm_dev = cg.out; tmul = cg.tmul;
     } else {
@@ -243,17 +235,17 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
     need = std::max(need, (size_t) Ts * std::max(D, Hd));
     hipStream_t s = c->stream;
     ensure_codec_scratch(c, need, Ts, D);
-    if (!c->d_enc_T) c->d_enc_T = dev_alloc<int>(c, 5 * 80);
-    if ((size_t) rows[0] > c->d_pcm_elems) { c->d_pcm = dev_alloc<float>(c, (size_t) rows[0]); c->d_pcm_elems = (size_t) rows[0]; }
-    if ((size_t) n_q * Ts > c->d_codes_elems) { c->d_codes = dev_alloc<int32_t>(c, (size_t) n_q * Ts); c->d_codes_elems = (size_t) n_q * Ts; }
+    c->d_enc_T.reserve(c, 5 * 80);
+    c->d_pcm.reserve(c, (size_t) rows[0]);
+    c->d_codes.reserve(c, (size_t) n_q * Ts);
     for (int b = 0; b < B; b++)
-        HIP_OK(hipMemcpyAsync(c->d_pcm + hdr[0][40 + b], pcm[(size_t) b], (size_t) n_samples[(size_t) b] * 4, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_enc_T, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(c->d_pcm.p + hdr[0][40 + b], pcm[(size_t) b], (size_t) n_samples[(size_t) b] * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->d_enc_T.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
     HIP_OK(hipStreamSynchronize(s));                            // hdr is a stack object
     CodecBatch cb[5];
-    for (int st = 0; st < 5; st++) { cb[st].T = c->d_enc_T + 80 * st; cb[st].Tpre = c->d_enc_T + 80 * st + 40; cb[st].B = B; }
-    float * A = c->cbuf[0], * Bf = c->cbuf[1], * R = c->cbuf[2];
-    half_t * H0 = c->cbuf_hh[0], * H1 = c->cbuf_hh[1], * H2 = c->cbuf_hh[2];
+    for (int st = 0; st < 5; st++) { cb[st].T = c->d_enc_T.p + 80 * st; cb[st].Tpre = c->d_enc_T.p + 80 * st + 40; cb[st].B = B; }
+    float * A = c->cbuf[0].p, * Bf = c->cbuf[1].p, * R = c->cbuf[2].p;
+    half_t * H0 = c->cbuf_hh[0].p, * H1 = c->cbuf_hh[1].p, * H2 = c->cbuf_hh[2].p;
 
     auto conv = [&](const CodecModel::Conv & cv, const half_t * xh, int st, const float * add, float * y, half_t * yh_raw, half_t * yh_elu) {
         ConvTmArgs a;
@@ -272,9 +264,8 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
         for (size_t r = 0; r < nrows; r++) for (int k = 0; k < C; k++) (*tap)[(size_t) k * nrows + r] = tm[r * (size_t) C + k];
     };
     const bool taps = tap_stage >= 0;
-    for (auto & e : c->enc_ev) if (!e) HIP_OK(hipEventCreate(&e));
-    HIP_OK(hipEventRecord(c->enc_ev[0], s));
-    launch_act_round(s, c->d_pcm, (size_t) rows[0], 0, H0);                  // the PCM's f16 image [rows][1]
+    c->enc_ev[0].record(s);
+    launch_act_round(s, c->d_pcm.p, (size_t) rows[0], 0, H0);                  // the PCM's f16 image [rows][1]
     conv(en.init, H0, 0, nullptr, taps ? A : nullptr, H1, H2);              // H1 = f16(x): shortcut input, H2 = f16(ELU(x)): conv1 input
     grab(0, A, ch[0], (size_t) rows[0]);
     for (int b = 0; b < 4; b++) {
@@ -288,7 +279,7 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
         d.K = bl.down.k; d.stride = bl.stride; d.kd = d.K * d.cin; d.kd16 = (d.kd + 15) & ~15;
         d.xh = H0; d.rows_out = rows[b + 1]; d.cb_in = cb[b]; d.cb_out = cb[b + 1];
         if (b < 3) { d.y = taps ? A : nullptr; d.yh_raw = H1; d.yh_elu = H2; }
-        else { d.y = Bf; d.yh_raw = c->c_xt_h; }                            // Bf = x [row][D] for the skip; its f16 image is the LSTM's input
+        else { d.y = Bf; d.yh_raw = c->c_xt_h.p; }                            // Bf = x [row][D] for the skip; its f16 image is the LSTM's input
         launch_conv_down(s, d);
         grab(1 + b, b < 3 ? A : Bf, ch[b + 1], (size_t) rows[b + 1]);
     }
@@ -298,13 +289,13 @@ std::vector<std::vector<int32_t>> engine_codec_encode_many(bark_context * c, con
     launch_act_round(s, A, (size_t) D * Ts, 1, H0);
     conv(en.fin, H0, 4, nullptr, Bf, nullptr, nullptr);                     // Bf = latent [row][H]
     grab(6, Bf, Hd, (size_t) Ts);
-    launch_rvq_encode(s, cm.codebooks, cm.hp.n_bins, Hd, Bf, n_q, Ts, c->d_codes, cb[4]);
-    HIP_OK(hipEventRecord(c->enc_ev[1], s));
+    launch_rvq_encode(s, cm.codebooks, cm.hp.n_bins, Hd, Bf, n_q, Ts, c->d_codes.p, cb[4]);
+    c->enc_ev[1].record(s);
     c->enc_latents = Bf; c->enc_latent_rows = Ts;
     std::vector<int32_t> all((size_t) n_q * Ts);
-    HIP_OK(hipMemcpyAsync(all.data(), c->d_codes, all.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(all.data(), c->d_codes.p, all.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->enc_ev[0], c->enc_ev[1])); c->enc_device_us = 1e3 * ms; }
+    { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->enc_ev[0].get(), c->enc_ev[1].get())); c->enc_device_us = 1e3 * ms; }
     throw_on_missing_pick(all);
     std::vector<std::vector<int32_t>> out((size_t) B);
     for (int b = 0; b < B; b++) out[(size_t) b].assign(all.begin() + (size_t) n_q * hdr[4][40 + b], all.begin() + (size_t) n_q * hdr[4][40 + b + 1]);
@@ -320,16 +311,16 @@ std::vector<int32_t> engine_rvq_encode(bark_context * c, const float * latents, 
     const int Hd = cm.hp.hidden_dim;
     hipStream_t s = c->stream;
     ensure_codec_scratch(c, (size_t) T * std::max(Hd, cm.D), 0, cm.D);
-    if (!c->d_enc_T) c->d_enc_T = dev_alloc<int>(c, 5 * 80);
-    if ((size_t) n_q * T > c->d_codes_elems) { c->d_codes = dev_alloc<int32_t>(c, (size_t) n_q * T); c->d_codes_elems = (size_t) n_q * T; }
+    c->d_enc_T.reserve(c, 5 * 80);
+    c->d_codes.reserve(c, (size_t) n_q * T);
     int hdr[80] = {};
     hdr[0] = T; hdr[41] = T;
-    HIP_OK(hipMemcpyAsync(c->d_enc_T, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->cbuf[1], latents, (size_t) T * Hd * 4, hipMemcpyHostToDevice, s));
-    CodecBatch cb; cb.T = c->d_enc_T; cb.Tpre = c->d_enc_T + 40; cb.B = 1;
-    launch_rvq_encode(s, cm.codebooks, cm.hp.n_bins, Hd, c->cbuf[1], n_q, T, c->d_codes, cb);
+    HIP_OK(hipMemcpyAsync(c->d_enc_T.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->cbuf[1].p, latents, (size_t) T * Hd * 4, hipMemcpyHostToDevice, s));
+    CodecBatch cb; cb.T = c->d_enc_T.p; cb.Tpre = c->d_enc_T.p + 40; cb.B = 1;
+    launch_rvq_encode(s, cm.codebooks, cm.hp.n_bins, Hd, c->cbuf[1].p, n_q, T, c->d_codes.p, cb);
     std::vector<int32_t> codes((size_t) n_q * T);
-    HIP_OK(hipMemcpyAsync(codes.data(), c->d_codes, codes.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(codes.data(), c->d_codes.p, codes.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));                            // also: hdr is a stack object
     throw_on_missing_pick(codes);
     return codes;
@@ -422,7 +413,7 @@ std::vector<int32_t> engine_semantic_encode(bark_context * c, const float * pcm,
     bark_context::HubScratch & h = c->hubs;
     hipStream_t s = c->stream;
     const bool taps = tap_stage >= 0;
-    if (tap_stage == 0 && (size_t) T0 * C > h.tap_elems) { h.tap = dev_alloc<float>(c, (size_t) T0 * C); h.tap_elems = (size_t) T0 * C; }
+    if (tap_stage == 0) h.tap.reserve(c, (size_t) T0 * C);
     {
         int hdr[8][80] = {};
         for (int st = 0; st < 8; st++) { hdr[st][0] = rows[st]; hdr[st][41] = rows[st]; }
@@ -437,17 +428,16 @@ std::vector<int32_t> engine_semantic_encode(bark_context * c, const float * pcm,
         HIP_OK(hipMemcpyAsync(tap->data(), buf, elems * 4, hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
     };
-    for (auto & e : c->hub_ev) if (!e) HIP_OK(hipEventCreate(&e));
-    HIP_OK(hipEventRecord(c->hub_ev[0], s));
+    c->hub_ev[0].record(s);
     // feature encoder: the f16 image of the samples, convolution 0 + norm + GELU, six valid convolutions on the matrix cores (a16 <-> b16)
     launch_act_round(s, h.pcm, (size_t) n, 0, h.pcm_h);
     {
         HubConv0Args a;
         a.xh = h.pcm_h; a.n = n; a.T0 = T0; a.w = hm.conv0_w; a.C = C; a.K = hm.k0; a.stride = 5;
-        a.part = h.part; a.stats = h.stats; a.g = hm.gn_g; a.b = hm.gn_b; a.yh = h.a16; a.y = tap_stage == 0 ? h.tap : nullptr;
+        a.part = h.part; a.stats = h.stats; a.g = hm.gn_g; a.b = hm.gn_b; a.yh = h.a16; a.y = tap_stage == 0 ? h.tap.p : nullptr;
         launch_hub_conv0(s, a);
     }
-    grab(0, h.tap, (size_t) T0 * C);
+    grab(0, h.tap.p, (size_t) T0 * C);
     half_t * src = h.a16, * dst = h.b16;
     for (int i = 0; i < 6; i++) {
         const HubertModel::Conv & cv = hm.conv[i];
@@ -502,12 +492,12 @@ std::vector<int32_t> engine_semantic_encode(bark_context * c, const float * pcm,
     }
     grab(4, h.x, (size_t) T * H);
     run_token_head(c, T);
-    HIP_OK(hipEventRecord(c->hub_ev[1], s));
+    c->hub_ev[1].record(s);
     grab(5, h.logits, (size_t) T * hp.n_classes);
     std::vector<int32_t> ids((size_t) T);
     HIP_OK(hipMemcpyAsync(ids.data(), h.ids, ids.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    if (!taps) { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->hub_ev[0], c->hub_ev[1])); c->hub_device_us = 1e3 * ms; }
+    if (!taps) { float ms = 0.0f; HIP_OK(hipEventElapsedTime(&ms, c->hub_ev[0].get(), c->hub_ev[1].get())); c->hub_device_us = 1e3 * ms; }
     return ids;
 }
 
@@ -517,12 +507,12 @@ std::vector<float> engine_resample_24k_16k(bark_context * c, const float * pcm, 
     if (!pcm || n < 1 || n > kResampleMaxSamples) throw std::runtime_error("resampler: a recording needs 1 .. 1 310 720 samples (4096 codec frames)");
     for (int i = 0; i < n; i++) if (!std::isfinite(pcm[i])) throw std::runtime_error("resampler: non-finite sample");
     const int n_out = (2 * n + 2) / 3;
-    if ((size_t) n > c->rs_elems) { c->rs_in = dev_alloc<float>(c, (size_t) n); c->rs_out = dev_alloc<float>(c, ((size_t) 2 * n + 2) / 3); c->rs_elems = (size_t) n; }
+    c->rs_in.reserve(c, (size_t) n); c->rs_out.reserve(c, (size_t) n_out);
     hipStream_t s = c->stream;
-    HIP_OK(hipMemcpyAsync(c->rs_in, pcm, (size_t) n * 4, hipMemcpyHostToDevice, s));
-    launch_resample_24k_16k(s, c->rs_in, n, c->rs_out, n_out);
+    HIP_OK(hipMemcpyAsync(c->rs_in.p, pcm, (size_t) n * 4, hipMemcpyHostToDevice, s));
+    launch_resample_24k_16k(s, c->rs_in.p, n, c->rs_out.p, n_out);
     std::vector<float> out((size_t) n_out);
-    HIP_OK(hipMemcpyAsync(out.data(), c->rs_out, out.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(out.data(), c->rs_out.p, out.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     return out;
 }
@@ -531,11 +521,11 @@ double engine_time_resample(bark_context * c, int n, int iters) {
     HIP_OK(hipSetDevice(c->device));
     if (n < 1 || n > kResampleMaxSamples) throw std::runtime_error("time_resample: 1 .. 1 310 720 samples");
     const int n_out = (2 * n + 2) / 3;
-    if ((size_t) n > c->rs_elems) { c->rs_in = dev_alloc<float>(c, (size_t) n); c->rs_out = dev_alloc<float>(c, ((size_t) 2 * n + 2) / 3); c->rs_elems = (size_t) n; }
-    HIP_OK(hipMemsetAsync(c->rs_in, 0, (size_t) n * 4, c->stream));      // the time does not depend on the values
+    c->rs_in.reserve(c, (size_t) n); c->rs_out.reserve(c, (size_t) n_out);
+    HIP_OK(hipMemsetAsync(c->rs_in.p, 0, (size_t) n * 4, c->stream));      // the time does not depend on the values
     iters = std::max(1, iters);
-    for (int i = 0; i < 2; i++) launch_resample_24k_16k(c->stream, c->rs_in, n, c->rs_out, n_out);
-    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_resample_24k_16k(c->stream, c->rs_in, n, c->rs_out, n_out); }) / iters;
+    for (int i = 0; i < 2; i++) launch_resample_24k_16k(c->stream, c->rs_in.p, n, c->rs_out.p, n_out);
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_resample_24k_16k(c->stream, c->rs_in.p, n, c->rs_out.p, n_out); }) / iters;
 }
 
 // ---- output rate and sample format: the rational resampler (rule C14r) ------------------------------------------------------------------------------------
@@ -602,9 +592,9 @@ const float * device_taps(bark_context * c, int rate_in, int rate_out, const Res
     return d;
 }
 void ensure_resample_buffers(bark_context * c, size_t in_elems, size_t out_bytes) {
-    if (in_elems > c->rp_in_elems) { c->rp_in = dev_alloc<float>(c, in_elems); c->rp_in_elems = in_elems; }
-    if (out_bytes > c->rp_out_bytes) { c->rp_out = dev_alloc<uint8_t>(c, out_bytes); c->rp_out_bytes = out_bytes; }
-    if (!c->rp_seg) c->rp_seg = dev_alloc<int>(c, 5 * (kResampleMaxSegments + 1));
+    c->rp_in.reserve(c, in_elems);
+    c->rp_out.reserve(c, out_bytes);
+    c->rp_seg.reserve(c, 5 * (kResampleMaxSegments + 1));
 }
 // the segment table of launch_resample_pair for `count` segments of n[i] samples; returns the tile count
 int fill_segment_table(int (&seg)[5][kResampleMaxSegments + 1], const int * n, int count, int rate_in, int rate_out, std::vector<int32_t> & n_out) {
@@ -644,16 +634,16 @@ std::vector<uint8_t> engine_resample_many(bark_context * c, const float * const 
     }
     ensure_resample_buffers(c, total_in, out.size());
     hipStream_t s = c->stream;
-    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->rp_in + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
-    if (!t) launch_sample_format(s, c->rp_in, c->rp_out, total_in, fmt);
+    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->rp_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
+    if (!t) launch_sample_format(s, c->rp_in.p, c->rp_out.p, total_in, fmt);
     else {
-        HIP_OK(hipMemcpyAsync(c->rp_seg, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(c->rp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
         ResamplePairArgs a;
-        a.x = c->rp_in; a.y = c->rp_out; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg;
+        a.x = c->rp_in.p; a.y = c->rp_out.p; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg.p;
         a.B = count; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
         launch_resample_pair(s, a, n_tiles);
     }
-    HIP_OK(hipMemcpyAsync(out.data(), c->rp_out, out.size(), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(out.data(), c->rp_out.p, out.size(), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));                             // seg is a stack object
     return out;
 }
@@ -668,11 +658,11 @@ double engine_time_resample_pair(bark_context * c, int n, int rate_in, int rate_
     std::vector<int32_t> n_out;
     const int n_tiles = fill_segment_table(seg, &n, 1, rate_in, rate_out, n_out);
     ensure_resample_buffers(c, (size_t) n, (size_t) n_out[0] * (size_t) bytes_per);
-    HIP_OK(hipMemsetAsync(c->rp_in, 0, (size_t) n * 4, c->stream));      // the time does not depend on the values
-    HIP_OK(hipMemcpyAsync(c->rp_seg, seg, sizeof(seg), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->rp_in.p, 0, (size_t) n * 4, c->stream));      // the time does not depend on the values
+    HIP_OK(hipMemcpyAsync(c->rp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     ResamplePairArgs a;
-    a.x = c->rp_in; a.y = c->rp_out; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg;
+    a.x = c->rp_in.p; a.y = c->rp_out.p; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg.p;
     a.B = 1; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
     iters = std::max(1, iters);
     for (int i = 0; i < 2; i++) launch_resample_pair(c->stream, a, n_tiles);

@@ -1,8 +1,9 @@
-// engine_internal.h - declarations shared by the engine's translation units (engine_load.hip: model upload; engine.hip:
-// building blocks and the stage loops; engine_batch.hip: lock-step batching; engine_codec.hip: EnCodec decode; engine_timing.hip: bench
-// hooks).  Every launch descriptor that follows from the model alone is stated once here / in engine.hip (layer_product, lm_head_args,
-// set_token_embedding), and so are graph capture (capture_graph), event timing (time_on_stream_us) and the fine stage's window plan
-// (fine_plan / fine_window / fine_write_back).  Not an API.
+// engine_internal.h - declarations shared by the engine's translation units (engine_load.hip: model upload, a context's runtime state and its
+// release; engine.hip: building blocks and the stage loops; engine_batch.hip: lock-step batching; engine_codec.hip: EnCodec decode and encode,
+// semantic encoder, resamplers; engine_timing.hip: bench hooks).  Every launch descriptor that follows from the model alone is stated once here /
+// in engine.hip (layer_product, lm_head_args, set_token_embedding), and so are graph capture (capture_graph), event timing (time_on_stream_us)
+// and the fine stage's window plan (fine_plan / fine_window / fine_write_back).  Who owns what: the owner types of
+// engine.h (GraphExec, Event, DevBuf) and the two allocators of a context here (dev_alloc, host_alloc).  Not an API.
 #pragma once
 #include "engine.h"
 
@@ -71,6 +72,24 @@ template <typename T> T * dev_alloc(bark_context * ctx, size_t count) {
     return (T *) p;
 }
 int guard_check(bark_context * ctx, const char * where);      // number of damaged guard bands (0 without BARK_HIP_GUARD)
+// pinned host memory of the context (freed with it, behind the device allocations)
+template <typename T> T * host_alloc(bark_context * ctx, size_t count) {
+    void * p = nullptr;
+    HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    ctx->pinned.push_back(p);
+    return (T *) p;
+}
+} }  // namespace barkhip::detail
+
+template <typename T> void barkhip::DevBuf<T>::reserve(bark_context * ctx, size_t count) {
+    if (count > n) { p = detail::dev_alloc<T>(ctx, count); n = count; }
+}
+inline void barkhip::Event::record(hipStream_t s) {
+    if (!e) HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventRecord(e, s));
+}
+
+namespace barkhip { namespace detail {
 
 // device -> host on the context's own (non-blocking) stream, complete on return: never the legacy stream, which refuses work while ANY blocking
 // stream of the process captures a graph (other contexts on other host threads do)
@@ -92,9 +111,11 @@ inline QMat q4_rows(const QMat & w, size_t row0, int K) {
 
 // ---- building blocks (engine.hip) ------------------------------------------------------------------
 double weight_bytes_per_element(const GptModel & m);
-float * layer_k(const GptModel & m, int l);
-float * layer_v(const GptModel & m, int l);
-float * layer_vt(const GptModel & m, int l);
+// layer l of the context's own KV cache of model m (one of c->gpt)
+inline GptRun & run_of(bark_context * c, const GptModel & m) { return c->gpt_run[&m - c->gpt]; }
+inline float * layer_k(bark_context * c, const GptModel & m, int l) { return run_of(c, m).kcache + m.kv_layer_stride * (size_t) l; }
+inline float * layer_v(bark_context * c, const GptModel & m, int l) { return run_of(c, m).vcache + m.kv_layer_stride * (size_t) l; }
+inline float * layer_vt(bark_context * c, const GptModel & m, int l) { float * vt = run_of(c, m).vtcache; return vt ? vt + m.kv_layer_stride * (size_t) l : nullptr; }
 // the many-row scratch a forward pass works in: the context's own (P rows), or the fine batch's (several windows back to back)
 struct RowBufs { float * x, * q; half_t * xn, * att, * hbuf, * q16, * k16, * vt16; float * logits; const int32_t * tokens; int plane; };
 RowBufs own_rows(bark_context * c);
@@ -122,8 +143,8 @@ template <typename Args> void set_token_embedding(Args & a, const bark_context *
 void embed_state_row(bark_context * c, const GptModel & m, const StepState * st, float * x);      // x = embedding of st->cur_token at position st->n_past
 // Stream capture -> executable graph: `body` enqueues its launches on s (capture mode: thread local).  A body that throws ends the capture - the
 // stream would stay in capture mode for good otherwise - and what it recorded is dropped.  Runs once per graph, off the hot path.
-hipGraphExec_t capture_graph(hipStream_t s, const std::function<void()> & body);
-// device time of what `body` enqueues on the context's stream, in microseconds: a pair of events around it, destroyed on every path
+GraphExec capture_graph(hipStream_t s, const std::function<void()> & body);
+// device time of what `body` enqueues on the context's stream, in microseconds: a pair of events around it
 double time_on_stream_us(bark_context * c, const std::function<void()> & body);
 void run_layers_rows(bark_context * c, GptModel & m, int N, bool causal, float * kbase = nullptr, float * vbase = nullptr, int pos0 = 0,
                      const RowBufs * rb = nullptr, int seq = 0, size_t kv_seq_stride = 0, const SeqTab * seqtab = nullptr);
@@ -141,7 +162,7 @@ struct StageCfg {            // what differs between the semantic and the coarse
 StageCfg stage_cfg(bark_context * c, int which);
 void run_sample(bark_context * c, const StageCfg & s, int n_past_add, bool prescaled = false);
 void enqueue_decode_step(bark_context * c, const StageCfg & s, bool sample, int n_past_add, bool embed = true);
-hipGraphExec_t capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps = 1, int ng = 4);
+GraphExec capture_decode(bark_context * c, const StageCfg & s, int n_past_add, int n_steps = 1, int ng = 4);
 void decode_steps_greedy(bark_context * c, const StageCfg & s, int n, int n_past);
 int sample_host(std::vector<float> & l, std::mt19937 & rng, float temp, float * eos_p, const bark_hip_sampling_filter * flt = nullptr);
 void filter_host(std::vector<float> & l, int32_t top_k, float top_p);      // C8n's cut, restated with a sort (removed ids -> -inf)

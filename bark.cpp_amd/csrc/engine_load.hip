@@ -75,27 +75,16 @@ float gelu_tanh_host(float x) {
 }  // namespace
 
 
+// Release order of a context (bark_context_memory, engine.h): the device is selected here; the members then release their graphs and events, and the
+// last context that holds them the shared weights and semantic encoder (the first members); the base frees the device allocations, the pinned host memory and, last, the stream.
 bark_context::~bark_context() {
     delete tail;
     (void) hipSetDevice(device);
     try { (void) barkhip::detail::guard_check(this, "bark_free"); } catch (...) { }
-    for (auto & g : gpt) {
-        for (auto & e : g.decode_graph) if (e) (void) hipGraphExecDestroy(e);
-        for (auto & e : g.decode_graph8) if (e) (void) hipGraphExecDestroy(e);
-        if (g.bench_graph) (void) hipGraphExecDestroy(g.bench_graph);
-    }
-    for (auto & g : batch_graphs) if (g.second) (void) hipGraphExecDestroy(g.second);
-    if (lstm_graph.exec) (void) hipGraphExecDestroy(lstm_graph.exec);
-    if (lstm_graph_enc.exec) (void) hipGraphExecDestroy(lstm_graph_enc.exec);
-    if (lstm_graph_hub.exec) (void) hipGraphExecDestroy(lstm_graph_hub.exec);
-    for (auto & e : enc_ev) if (e) (void) hipEventDestroy(e);
-    for (auto & e : hub_ev) if (e) (void) hipEventDestroy(e);
-    if (codec_graph.exec) (void) hipGraphExecDestroy(codec_graph.exec);
-    for (auto & g : fine_graphs) if (g) (void) hipGraphExecDestroy(g);
+}
+bark_context_memory::~bark_context_memory() {
     for (void * p : allocs) (void) hipFree(p);
-    if (batch.h_ids) (void) hipHostFree(batch.h_ids);
-    if (batch.h_state) (void) hipHostFree(batch.h_state);
-    if (batch.h_state_in) (void) hipHostFree(batch.h_state_in);
+    for (void * p : pinned) (void) hipHostFree(p);
     if (stream) (void) hipStreamDestroy(stream);
 }
 bark_context::SharedWeights::~SharedWeights() {
@@ -135,13 +124,12 @@ int guard_check(bark_context * ctx, const char * where) {
 
 void engine_invalidate_graphs(bark_context * ctx) {
     if (ctx->tail) engine_invalidate_graphs(ctx->tail);       // the clone that runs the tail of lock-step jobs replays graphs with the same constants
-    for (auto & g : ctx->batch_graphs) if (g.second) (void) hipGraphExecDestroy(g.second);
     ctx->batch_graphs.clear();
-    for (auto & g : ctx->fine_graphs) if (g) { (void) hipGraphExecDestroy(g); g = nullptr; }
-    for (auto & g : ctx->gpt) {
-        for (auto & e : g.decode_graph) if (e) { (void) hipGraphExecDestroy(e); e = nullptr; }
-        for (auto & e : g.decode_graph8) if (e) { (void) hipGraphExecDestroy(e); e = nullptr; }
-        if (g.bench_graph) { (void) hipGraphExecDestroy(g.bench_graph); g.bench_graph = nullptr; }
+    for (auto & g : ctx->fine_graphs) g.reset();
+    for (auto & r : ctx->gpt_run) {
+        for (auto & e : r.decode_graph) e.reset();
+        for (auto & e : r.decode_graph8) e.reset();
+        r.bench_graph.reset();
     }
 }
 
@@ -151,17 +139,17 @@ static void init_runtime(bark_context * ctxp, bool weights_uploaded_now) {
     // ---- KV caches, scratch ------------------------------------------------------------------------
     const int P = ctx->P;
     for (int g = 0; g < 2; g++) {
-        GptModel & m = ctx->gpt[g];
-        m.kv_layer_stride = (size_t) m.hp.n_embd * P;
-        m.kcache = dev_alloc<float>(ctx.get(), m.kv_layer_stride * m.hp.n_layer);     // bark.cpp:976-991
-        m.vcache = dev_alloc<float>(ctx.get(), m.kv_layer_stride * m.hp.n_layer);
-        m.vtcache = dev_alloc<float>(ctx.get(), m.kv_layer_stride * m.hp.n_layer);
+        const GptModel & m = ctx->gpt[g];
+        GptRun & r = ctx->gpt_run[g];
+        r.kcache = dev_alloc<float>(ctx.get(), m.kv_layer_stride * m.hp.n_layer);     // bark.cpp:976-991
+        r.vcache = dev_alloc<float>(ctx.get(), m.kv_layer_stride * m.hp.n_layer);
+        r.vtcache = dev_alloc<float>(ctx.get(), m.kv_layer_stride * m.hp.n_layer);
     }
     {
-        GptModel & m = ctx->gpt[2];
-        m.kv_layer_stride = 0;
-        m.kcache = dev_alloc<float>(ctx.get(), (size_t) m.hp.n_embd * P);
-        m.vcache = dev_alloc<float>(ctx.get(), (size_t) m.hp.n_embd * P);
+        const GptModel & m = ctx->gpt[2];
+        GptRun & r = ctx->gpt_run[2];
+        r.kcache = dev_alloc<float>(ctx.get(), (size_t) m.hp.n_embd * P);
+        r.vcache = dev_alloc<float>(ctx.get(), (size_t) m.hp.n_embd * P);
     }
     const size_t NE = (size_t) P * ctx->max_E;
     ctx->x = dev_alloc<float>(ctx.get(), NE);
@@ -287,6 +275,7 @@ bark_context * engine_load(const char * path, const bark_context_params & params
         if (m.hp.block_size != 1024) throw std::runtime_error("block_size must be 1024");
         if (m.hp.n_wtes > 8 || m.hp.n_lm_heads > 8 || m.hp.n_layer > 64) throw std::runtime_error("unsupported GPT shape");
         m.layers.resize((size_t) m.hp.n_layer);
+        m.kv_layer_stride = g < 2 ? (size_t) E * ctx->P : 0;
         n_w16 = n_wq4 = n_w32 = 0;
         for (int i = 0; i < m.hp.n_wtes; i++) place_w(need_w(T, "model/wte/" + std::to_string(i), E, m.hp.n_in_vocab), &m.wte[i], &m.wte_q[i]);
         for (int i = 0; i < m.hp.n_lm_heads; i++) place_w(need_w(T, "model/lm_head/" + std::to_string(i), E, m.hp.n_out_vocab), &m.lm_head[i], &m.lm_head_q[i]);
@@ -704,7 +693,7 @@ void engine_load_semantic_encoder(bark_context * ctx, const char * path) {
         hm->gelu_erf_lut = (const uint16_t *) up(lut.data(), lut.size() * 2);
     }
     HIP_OK(hipDeviceSynchronize());
-    if (ctx->lstm_graph_hub.exec) { (void) hipGraphExecDestroy(ctx->lstm_graph_hub.exec); ctx->lstm_graph_hub.exec = nullptr; }
+    ctx->lstm_graph_hub.exec.reset();
     ctx->hubs = bark_context::HubScratch();                       // a second load: scratch of the new dimensions (the old buffers stay with the context until it is freed)
     ctx->hub = hm;
     if (ctx->description.find(", semantic encoder") == std::string::npos) ctx->description += ", semantic encoder";
@@ -719,13 +708,7 @@ bark_context * engine_clone(bark_context * src, uint32_t seed) {
     ctx->hub = src->hub;
     ctx->rng = std::mt19937(seed);
     ctx->vocab = src->vocab;
-    for (int g = 0; g < 3; g++) {
-        ctx->gpt[g] = src->gpt[g];
-        ctx->gpt[g].kcache = ctx->gpt[g].vcache = ctx->gpt[g].vtcache = nullptr;
-        for (auto & e : ctx->gpt[g].decode_graph) e = nullptr;
-        for (auto & e : ctx->gpt[g].decode_graph8) e = nullptr;
-        ctx->gpt[g].bench_graph = nullptr;
-    }
+    for (int g = 0; g < 3; g++) ctx->gpt[g] = src->gpt[g];
     ctx->codec = src->codec;
     ctx->device = src->device; ctx->use_graph = src->use_graph; ctx->fast_gemm = src->fast_gemm; ctx->fine_order = src->fine_order;
     ctx->weights = src->weights; ctx->weight_bytes = src->weight_bytes;

@@ -52,26 +52,27 @@ double engine_time_decode_step(bark_context * c, int which, int ctxlen, int iter
     if (which < 0 || which > 1) throw std::runtime_error("time_decode_step: which must be 0 or 1");
     HIP_OK(hipSetDevice(c->device));
     GptModel & m = c->gpt[which];
+    GptRun & run = c->gpt_run[which];
     ctxlen = std::max(1, std::min(ctxlen, m.hp.block_size));
     const StageCfg s = stage_cfg(c, which);
     StepState st = fresh_state(); st.n_past = ctxlen - 1; st.cur_token = 1;
     set_state(c, st);
     // the cache rows below ctxlen hold whatever the last run left; timing does not depend on the values,
     // but keep them finite: zero them once
-    HIP_OK(hipMemsetAsync(m.kcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
-    HIP_OK(hipMemsetAsync(m.vcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
-    if (m.vtcache) HIP_OK(hipMemsetAsync(m.vtcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
+    HIP_OK(hipMemsetAsync(run.kcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
+    HIP_OK(hipMemsetAsync(run.vcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
+    if (run.vtcache) HIP_OK(hipMemsetAsync(run.vtcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
     // the graph the stage loops replay: eight steps per launch; n_past does not advance here
     const int per_graph = 8;
     upload_filter(c);                                                     // the step samples with the context's top-k / nucleus filter, if any
-    if (m.bench_graph) { (void) hipGraphExecDestroy(m.bench_graph); m.bench_graph = nullptr; }     // the variant depends on the context length
-    m.bench_graph = capture_decode(c, s, 0, per_graph, (ctxlen + 255) / 256);
-    for (int i = 0; i < 3; i++) HIP_OK(hipGraphLaunch(m.bench_graph, c->stream));
+    run.bench_graph.reset();                                              // the variant depends on the context length
+    run.bench_graph = capture_decode(c, s, 0, per_graph, (ctxlen + 255) / 256);
+    for (int i = 0; i < 3; i++) HIP_OK(hipGraphLaunch(run.bench_graph.get(), c->stream));
     set_state(c, st);
     iters = std::max(1, iters / per_graph) * per_graph;
     const double us = time_on_stream_us(c, [&] {
         for (int i = 0; i < iters; i += per_graph) {
-            HIP_OK(hipGraphLaunch(m.bench_graph, c->stream));
+            HIP_OK(hipGraphLaunch(run.bench_graph.get(), c->stream));
             if (((i / per_graph) & 127) == 127) set_state(c, st);         // out_tokens holds 2048 entries
         }
     });
@@ -104,7 +105,7 @@ double engine_time_gemv(bark_context * c, int which, int op, int iters, double *
         LinArgs a = layer_product(c, m, l, op);
         a.N = 1;
         switch (op) {
-            case OP_QKV:  a.x_f32 = c->x; a.q = c->q; a.kc = layer_k(m, l); a.vc = layer_v(m, l); a.st = c->d_state; break;
+            case OP_QKV:  a.x_f32 = c->x; a.q = c->q; a.kc = layer_k(c, m, l); a.vc = layer_v(c, m, l); a.st = c->d_state; break;
             case OP_PROJ: if (m.q4) a.x_f32 = c->att32; else a.x_f16 = c->att; a.res = c->x; break;
             case OP_FC:   a.x_f32 = c->x; a.out_h = c->hbuf; a.out_h32 = m.q4 ? c->h32 : nullptr; break;
             default:      if (m.q4) a.x_f32 = c->h32; else a.x_f16 = c->hbuf; a.res = c->x; break;
@@ -114,11 +115,10 @@ double engine_time_gemv(bark_context * c, int which, int op, int iters, double *
     // op >= 4 ("hot"): always layer 0, so the weights stay in L2; otherwise rotate through the layers.
     // The launches are captured into one hipGraph (48 nodes) so that the host launch rate does not bound the result.
     const int per_graph = 48;
-    hipGraphExec_t exec = capture_graph(c->stream, [&] { for (int i = 0; i < per_graph; i++) launch(hot ? 0 : i % m.hp.n_layer); });
-    HIP_OK(hipGraphLaunch(exec, c->stream));
+    const GraphExec exec = capture_graph(c->stream, [&] { for (int i = 0; i < per_graph; i++) launch(hot ? 0 : i % m.hp.n_layer); });
+    HIP_OK(hipGraphLaunch(exec.get(), c->stream));
     const int reps = std::max(1, iters / per_graph);
-    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec, c->stream)); });
-    (void) hipGraphExecDestroy(exec);
+    const double us = time_on_stream_us(c, [&] { for (int i = 0; i < reps; i++) HIP_OK(hipGraphLaunch(exec.get(), c->stream)); });
     iters = reps * per_graph;
     if (bytes_per_launch) {
         const double Ed = E;
@@ -133,6 +133,7 @@ double engine_time_gemv(bark_context * c, int which, int op, int iters, double *
 int engine_trace_decode_step(bark_context * c, int which, int ctxlen, int replays, unsigned long long * out6, int cap_records) {
     HIP_OK(hipSetDevice(c->device));
     GptModel & m = c->gpt[which];
+    GptRun & run = c->gpt_run[which];
     const StageCfg s = stage_cfg(c, which);
     StepState st = fresh_state(); st.n_past = ctxlen - 1; st.cur_token = 1;
     set_state(c, st);
@@ -141,26 +142,25 @@ int engine_trace_decode_step(bark_context * c, int which, int ctxlen, int replay
         c->trace_rec = dev_alloc<unsigned long long>(c, (size_t) c->trace_cap * 8);
         c->trace_pos = dev_alloc<unsigned>(c, 1);
     }
-    HIP_OK(hipMemsetAsync(m.kcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
-    HIP_OK(hipMemsetAsync(m.vcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
-    if (m.vtcache) HIP_OK(hipMemsetAsync(m.vtcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
+    HIP_OK(hipMemsetAsync(run.kcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
+    HIP_OK(hipMemsetAsync(run.vcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
+    if (run.vtcache) HIP_OK(hipMemsetAsync(run.vtcache, 0, m.kv_layer_stride * m.hp.n_layer * 4, c->stream));
     // first capture counts the waves of a step, the second bakes the per-replay stride into the kernels' arguments
     c->trace_kid = 0; c->trace_base = 0; c->trace_per_replay = 0;
-    hipGraphExec_t g = capture_decode(c, s, 0, 1, (ctxlen + 255) / 256);
-    (void) hipGraphExecDestroy(g);
+    GraphExec g = capture_decode(c, s, 0, 1, (ctxlen + 255) / 256);
+    g.reset();
     c->trace_per_replay = c->trace_base; c->trace_kid = 0; c->trace_base = 0;
     g = capture_decode(c, s, 0, 1, (ctxlen + 255) / 256);
     HIP_OK(hipMemsetAsync(c->trace_rec, 0, (size_t) c->trace_cap * 8 * sizeof(unsigned long long), c->stream));
-    for (int i = 0; i < 5; i++) { HIP_OK(hipMemsetAsync(c->trace_pos, 0, sizeof(unsigned), c->stream)); HIP_OK(hipGraphLaunch(g, c->stream)); }
+    for (int i = 0; i < 5; i++) { HIP_OK(hipMemsetAsync(c->trace_pos, 0, sizeof(unsigned), c->stream)); HIP_OK(hipGraphLaunch(g.get(), c->stream)); }
     HIP_OK(hipStreamSynchronize(c->stream));
     set_state(c, st);
     HIP_OK(hipMemsetAsync(c->trace_pos, 0, sizeof(unsigned), c->stream));
-    for (int i = 0; i < replays; i++) HIP_OK(hipGraphLaunch(g, c->stream));
+    for (int i = 0; i < replays; i++) HIP_OK(hipGraphLaunch(g.get(), c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     unsigned n = c->trace_per_replay * (unsigned) replays;
     n = std::min(n, std::min(c->trace_cap, (unsigned) std::max(0, cap_records)));
     copy_to_host(c, out6, c->trace_rec, (size_t) n * 8 * sizeof(unsigned long long));
-    (void) hipGraphExecDestroy(g);
     return (int) n;
 }
 #endif
