@@ -53,6 +53,21 @@ class BarkHipAudioFormat(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("sample_format", C.c_int32)]
 
 
+class BarkHipJoinParams(C.Structure):
+    """struct bark_hip_join_params (bark_mi355x.h): gaps, fade and trim of the long-form join (rule C15j); {6000, 0, 0.0, 0}: the defaults."""
+    _fields_ = [("gap_samples", C.c_int32), ("fade_samples", C.c_int32), ("trim_threshold", C.c_float), ("trim_pad_frames", C.c_int32)]
+
+
+class BarkHipLongParams(C.Structure):
+    """struct bark_hip_long_params (bark_mi355x.h): the splitter's budget (rule C15s), chaining and the join of bark_hip_generate_long."""
+    _fields_ = [("max_tokens", C.c_int32), ("chain", C.c_int32), ("join", BarkHipJoinParams)]
+
+
+def join_params(gap_samples: int = 6000, fade_samples: int = 0, trim_threshold: float = 0.0, trim_pad_frames: int = 0) -> BarkHipJoinParams:
+    return BarkHipJoinParams(int(gap_samples), int(fade_samples), float(trim_threshold), int(trim_pad_frames))
+
+
+SPLIT_MAX_CHUNKS = 64
 SAMPLE_F32, SAMPLE_S16, SAMPLE_MULAW = 0, 1, 2          # enum bark_hip_sample_format
 SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "mulaw": SAMPLE_MULAW}
 SAMPLE_DTYPES = {SAMPLE_F32: np.float32, SAMPLE_S16: np.int16, SAMPLE_MULAW: np.uint8}
@@ -119,6 +134,8 @@ EXPORTS = [
     "bark_hip_batch_lock_steps",
     "bark_hip_resample_out_len", "bark_hip_resample_table", "bark_hip_resample", "bark_hip_resample_many", "bark_hip_get_audio_as", "bark_hip_batch_audio_as",
     "bark_hip_batcher_submit_as", "bark_hip_batcher_wait_bytes", "bark_hip_time_resample_pair",
+    "bark_hip_split_text", "bark_hip_generate_long", "bark_hip_long_audio_as", "bark_hip_long_chunks", "bark_hip_long_chunk_audio", "bark_hip_long_chunk_tokens",
+    "bark_hip_join_many", "bark_hip_time_join", "bark_hip_batcher_submit_long", "bark_hip_batcher_ticket_chunks", "bark_hip_time_join_activity",
 ]
 
 
@@ -195,6 +212,22 @@ def load_library() -> C.CDLL:
     lib.bark_hip_batcher_submit_as.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter), C.POINTER(BarkHipVoicePrompt),
                                                C.POINTER(BarkHipAudioFormat)]
     lib.bark_hip_batcher_wait_bytes.argtypes = [vp, C.c_int64, vp, C.c_int]
+    lib.bark_hip_batcher_submit_long.restype = C.c_int64
+    lib.bark_hip_batcher_submit_long.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipLongParams), C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter),
+                                                 C.POINTER(BarkHipVoicePrompt), C.POINTER(BarkHipAudioFormat)]
+    lib.bark_hip_batcher_ticket_chunks.argtypes = [vp, C.c_int64]
+    lib.bark_hip_time_join_activity.restype = C.c_double
+    lib.bark_hip_time_join_activity.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.bark_hip_split_text.argtypes = [vp, C.c_char_p, C.c_int, ip, C.c_int]
+    lib.bark_hip_generate_long.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipLongParams), C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter),
+                                           C.POINTER(BarkHipVoicePrompt)]
+    lib.bark_hip_long_audio_as.argtypes = [vp, C.POINTER(BarkHipAudioFormat), vp, C.c_int]
+    lib.bark_hip_long_chunks.argtypes = [vp, ip, C.c_int]
+    lib.bark_hip_long_chunk_audio.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_float))]
+    lib.bark_hip_long_chunk_tokens.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int]
+    lib.bark_hip_join_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.POINTER(BarkHipJoinParams), C.POINTER(BarkHipAudioFormat), vp, C.c_int, ip]
+    lib.bark_hip_time_join.restype = C.c_double
+    lib.bark_hip_time_join.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
     lib.bark_hip_generate_batch_seeded.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_uint32)]
     lib.bark_hip_generate_batch_ex.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams)]
@@ -631,6 +664,92 @@ class BarkContext:
             raise RuntimeError("bark_hip_time_resample_pair failed")
         return us
 
+    # ---- long-form text (rules C15s, C15j): the splitter, the chunks as one lock-step job, the join on the device ----
+    def split_text(self, text, max_tokens: int = 0) -> list:
+        """The chunks of a text as byte spans [(begin, end)] into its UTF-8 bytes (bark_hip_split_text); max_tokens 0: one sentence per chunk."""
+        raw = text if isinstance(text, bytes) else text.encode("utf-8")
+        spans = np.zeros(2 * SPLIT_MAX_CHUNKS, np.int32)
+        n = self._lib.bark_hip_split_text(self._h, raw, int(max_tokens), spans.ctypes.data, SPLIT_MAX_CHUNKS)
+        if n < 0:
+            raise ValueError("bark_hip_split_text refused the text (max_tokens outside 0 .. 255, or more than 64 chunks)")
+        return [(int(spans[2 * i]), int(spans[2 * i + 1])) for i in range(n)]
+
+    def generate_long(self, text, max_tokens: int = 0, chain: bool = False, join: "BarkHipJoinParams | None" = None, params: "BarkHipRequestParams | None" = None,
+                      top_k: "int | None" = None, top_p: "float | None" = None, voice=None) -> list:
+        """A text of any length (bark_hip_generate_long): split, one lock-step job over the chunks (chain: a job per chunk, each continuing the one before
+        it), results held by the context for long_audio_as / long_chunks.  Returns one dict per chunk: pcm (untrimmed, 24 kHz) and the three token streams."""
+        raw = text if isinstance(text, bytes) else text.encode("utf-8")
+        lp = BarkHipLongParams(int(max_tokens), int(bool(chain)), join if join is not None else join_params())
+        flt = None if top_k is None and top_p is None else BarkHipSamplingFilter(int(top_k or 0), float(1.0 if top_p is None else top_p))
+        keep = None if voice is None else _voice_struct(voice)
+        n = self._lib.bark_hip_generate_long(self._h, raw, C.byref(lp), None if params is None else C.byref(params), None if flt is None else C.byref(flt),
+                                             None if keep is None else C.byref(keep[0]))
+        if n < 0:
+            raise RuntimeError("bark_hip_generate_long failed")
+        out = []
+        for i in range(n):
+            p = C.POINTER(C.c_float)()
+            ns = self._lib.bark_hip_long_chunk_audio(self._h, i, C.byref(p))
+            d = {"pcm": np.ctypeslib.as_array(p, shape=(ns,)).copy() if ns > 0 else np.zeros(0, np.float32)}
+            for stage, (name, w) in enumerate((("semantic", 1), ("coarse", 2), ("fine", 8))):
+                buf = np.zeros(65536, np.int32)
+                k = self._lib.bark_hip_long_chunk_tokens(self._h, i, stage, buf.ctypes.data, buf.size)
+                d[name] = buf[:max(k, 0)].copy().reshape(-1, w) if w > 1 else buf[:max(k, 0)].copy()
+            out.append(d)
+        return out
+
+    def long_audio_as(self, rate: int = 24000, fmt="f32") -> np.ndarray:
+        """The joined audio of the last generate_long at `rate` in `fmt` (bark_hip_long_audio_as)."""
+        to = audio_format(rate, fmt)
+        n = self._lib.bark_hip_long_audio_as(self._h, C.byref(to), None, 0)
+        if n == -1:
+            raise RuntimeError("no long result held, or an unsupported rate / format")
+        buf = np.zeros(max(-n - 2, 1), np.uint8)
+        if n < -1:
+            n = self._lib.bark_hip_long_audio_as(self._h, C.byref(to), buf.ctypes.data, buf.size)
+            if n < 0:
+                raise RuntimeError("bark_hip_long_audio_as failed")
+        return buf[:n].view(SAMPLE_DTYPES[to.sample_format]).copy()
+
+    def long_chunks(self) -> list:
+        """[(text begin, text end, first sample in the joined 24 kHz signal, kept samples)] per chunk of the last generate_long (bark_hip_long_chunks)."""
+        out = np.zeros(4 * SPLIT_MAX_CHUNKS, np.int32)
+        n = self._lib.bark_hip_long_chunks(self._h, out.ctypes.data, SPLIT_MAX_CHUNKS)
+        if n < 0:
+            raise RuntimeError("no long result held")
+        return [tuple(int(v) for v in out[4 * i:4 * i + 4]) for i in range(n)]
+
+    def join_many(self, pcm_list, join: "BarkHipJoinParams | None" = None, rate: int = 24000, fmt="f32", want_layout: bool = False):
+        """The join alone on caller audio (bark_hip_join_many): up to 64 segments at 24 kHz -> one array at `rate` in `fmt`; want_layout: also
+        [(first sample in the joined signal, kept samples)] per segment."""
+        xs = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in pcm_list]
+        to = audio_format(rate, fmt)
+        jp = join if join is not None else join_params()
+        ns = _i32([len(x) for x in xs])
+        ptrs = (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
+        layout = np.zeros(2 * max(len(xs), 1), np.int32)
+        call = lambda p, cap: self._lib.bark_hip_join_many(self._h, ptrs, ns.ctypes.data, len(xs), C.byref(jp), C.byref(to), p, cap, layout.ctypes.data)
+        n_max = min(sum(len(x) for x in xs) + max(len(xs) - 1, 0) * max(int(jp.gap_samples), 0), 1 << 25)      # nothing trimmed: one call serves
+        buf = np.zeros(max(-(-n_max * max(int(rate), 0) // 24000) * np.dtype(SAMPLE_DTYPES[to.sample_format]).itemsize, 1), np.uint8)
+        n = call(buf.ctypes.data, buf.size)
+        if n < 0:
+            raise ValueError("bark_hip_join_many refused the call (segment count or length, a sample that is not finite, the parameters, the rate or the format)")
+        res = buf[:n].view(SAMPLE_DTYPES[to.sample_format]).copy()
+        return (res, [(int(layout[2 * i]), int(layout[2 * i + 1])) for i in range(len(xs))]) if want_layout else res
+
+    def time_join(self, count: int, n_each: int, rate: int = 24000, fmt="f32", iters: int = 20) -> float:
+        us = self._lib.bark_hip_time_join(self._h, int(count), int(n_each), int(rate), audio_format(rate, fmt).sample_format, int(iters))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_join failed")
+        return us
+
+    def time_join_activity(self, count: int, n_each: int, iters: int = 20) -> float:
+        """What a trim threshold adds in front of the join launch, timed apart (bark_hip_time_join_activity): the table's fill and the activity launch."""
+        us = self._lib.bark_hip_time_join_activity(self._h, int(count), int(n_each), int(iters))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_join_activity failed")
+        return us
+
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""
         p = self._params if self._params is not None else default_params()
@@ -867,12 +986,26 @@ class Batcher:
             pass
 
     def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None,
-               voice=None, audio_format: "BarkHipAudioFormat | None" = None) -> int:
+               voice=None, audio_format: "BarkHipAudioFormat | None" = None, long=None) -> int:
         """audio_format: the rate / sample format of the answer (api.audio_format(rate, "s16"); bark_hip_batcher_submit_as) - fetch it with wait_bytes().
         top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
         neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does.
-        voice: the request's own voice.VoicePrompt (bark_hip_batcher_submit_voiced; None: the context's)."""
-        if audio_format is not None:
+        voice: the request's own voice.VoicePrompt (bark_hip_batcher_submit_voiced; None: the context's).
+        long: True or a BarkHipLongParams - a text of any length as one ticket (bark_hip_batcher_submit_long): its parts travel as ordinary requests, the
+        answer is their joined audio."""
+        if long is not None and long is not False:
+            lp = long if isinstance(long, BarkHipLongParams) else BarkHipLongParams(0, 0, join_params())
+            flt = None
+            if top_k is not None or top_p is not None:
+                flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
+            if params is None:
+                params = self._ctx[0].request_params(seed=int(seed))
+            st, keep = _voice_struct(voice) if voice is not None else (None, None)
+            t = self._lib.bark_hip_batcher_submit_long(self._b, text.encode("utf-8"), C.byref(lp), C.byref(params), None if flt is None else C.byref(flt),
+                                                       None if st is None else C.byref(st), None if audio_format is None else C.byref(audio_format))
+            if t > 0 and audio_format is not None:
+                self._formats[t] = int(audio_format.sample_format)
+        elif audio_format is not None:
             flt = None
             if top_k is not None or top_p is not None:
                 flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
@@ -908,7 +1041,7 @@ class Batcher:
         n = self._lib.bark_hip_batcher_wait(self._b, ticket, None, 0)          # probe: -(2 + samples)
         if n > -2:
             raise RuntimeError("generation failed")
-        pcm = np.zeros(-n - 2, np.float32)
+        pcm = np.zeros(max(-n - 2, 1), np.float32)                             # (a long text trimmed away entirely is 0 samples: the buffer still exists)
         n = self._lib.bark_hip_batcher_wait(self._b, ticket, pcm.ctypes.data, pcm.size)
         if n < 0:
             raise RuntimeError("bark_hip_batcher_wait failed")
@@ -919,7 +1052,7 @@ class Batcher:
         n = self._lib.bark_hip_batcher_wait_bytes(self._b, ticket, None, 0)    # probe: -(2 + bytes)
         if n > -2:
             raise RuntimeError("generation failed")
-        buf = np.zeros(-n - 2, np.uint8)
+        buf = np.zeros(max(-n - 2, 1), np.uint8)                               # (0 bytes is a legal answer of a long text: the buffer still exists)
         n = self._lib.bark_hip_batcher_wait_bytes(self._b, ticket, buf.ctypes.data, buf.size)
         if n < 0:
             raise RuntimeError("bark_hip_batcher_wait_bytes failed")

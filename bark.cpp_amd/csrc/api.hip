@@ -455,6 +455,124 @@ double bark_hip_time_resample_pair(struct bark_context * bctx, int n, int rate_i
     return guarded("bark_hip_time_resample_pair", -1.0, [&] { return engine_time_resample_pair(bctx, n, rate_in, rate_out, sample_format, iters); });
 }
 
+// ---- long-form text (rules C15s, C15j) ------------------------------------------------------------------------------------------------------------------
+namespace {
+bool join_call_valid(const int * n, int count, const bark_hip_join_params & p, const bark_hip_audio_format & to) {
+    if (!n || count < 1 || count > kResampleMaxSegments || !join_params_valid(p) || !sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return false;
+    for (int i = 0; i < count; i++) if (n[i] < 1 || n[i] > kResampleMaxSamples) return false;
+    return true;
+}
+// the joined audio of the context's long result in `to`, made once per format (the probe for the size and the call that fetches join once)
+void ensure_long_join(struct bark_context * bctx, const bark_hip_audio_format & to) {
+    bark_context::LongResult & lr = bctx->long_result;
+    if (lr.joined_fmt.sample_rate == to.sample_rate && lr.joined_fmt.sample_format == to.sample_format) return;
+    std::vector<const float *> pcm;
+    std::vector<int> n;
+    for (const bark_context::BatchResult & r : lr.chunks) { pcm.push_back(r.audio.data()); n.push_back((int) r.audio.size()); }
+    lr.joined_fmt = bark_hip_audio_format{0, 0};
+    lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, lr.layout);
+    lr.joined_fmt = to;
+}
+}  // namespace
+
+int bark_hip_split_text(struct bark_context * bctx, const char * text, int max_tokens, int32_t * spans_Nx2, int capacity_chunks) {
+    if (!bctx || !text) return -1;
+    return guarded("bark_hip_split_text", -1, [&] {
+        const std::vector<TextSpan> spans = split_text(bctx->vocab, text, max_tokens);
+        if ((int) spans.size() > capacity_chunks || (!spans.empty() && !spans_Nx2)) throw std::runtime_error("output buffer too small");
+        for (size_t i = 0; i < spans.size(); i++) { spans_Nx2[2 * i] = spans[i].begin; spans_Nx2[2 * i + 1] = spans[i].end; }
+        return (int) spans.size();
+    }, /*uses_gpu=*/false);
+}
+
+int bark_hip_generate_long(struct bark_context * bctx, const char * text, const struct bark_hip_long_params * lp, const struct bark_hip_request_params * params,
+                           const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice) {
+    if (!bctx || !text) return -1;
+    bctx->long_result = bark_context::LongResult();                   // whatever refuses or fails below, no earlier result stays behind
+    if (filter && !filter_valid(*filter)) return -1;
+    return guarded("bark_hip_generate_long", -1, [&] {
+        const bark_hip_long_params def{0, 0, join_default_params()};
+        const VoicePtr v = engine_make_voice(bctx, voice);
+        return engine_generate_long(bctx, text, lp ? *lp : def, params, filter, voice ? &v : nullptr);
+    });
+}
+
+int bark_hip_long_audio_as(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes) {
+    if (!bctx || bctx->long_result.chunks.empty()) return -1;
+    const bark_hip_audio_format to = fmt ? *fmt : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
+    if (!sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    return guarded("bark_hip_long_audio_as", -1, [&] {
+        ensure_long_join(bctx, to);
+        const std::vector<uint8_t> & r = bctx->long_result.joined;
+        if (r.empty()) return 0;                                                          // every chunk trimmed away
+        if (!out || (size_t) std::max(capacity_bytes, 0) < r.size()) return -2 - (int) r.size();
+        memcpy(out, r.data(), r.size());
+        return (int) r.size();
+    });
+}
+
+int bark_hip_long_chunks(struct bark_context * bctx, int32_t * out_Nx4, int capacity_chunks) {
+    if (!bctx || bctx->long_result.chunks.empty()) return -1;
+    const int n = (int) bctx->long_result.chunks.size();
+    if (!out_Nx4 || capacity_chunks < n) return -1;
+    return guarded("bark_hip_long_chunks", -1, [&] {
+        bark_context::LongResult & lr = bctx->long_result;
+        if (lr.layout.empty()) {                                     // no join has run yet: the layout alone (one launch with a threshold, none without)
+            std::vector<const float *> pcm;
+            std::vector<int> len;
+            for (const bark_context::BatchResult & r : lr.chunks) { pcm.push_back(r.audio.data()); len.push_back((int) r.audio.size()); }
+            lr.layout = engine_join_layout(bctx, pcm.data(), len.data(), n, lr.join);
+        }
+        for (int i = 0; i < n; i++) {
+            out_Nx4[4 * i] = lr.spans[(size_t) i].begin; out_Nx4[4 * i + 1] = lr.spans[(size_t) i].end;
+            out_Nx4[4 * i + 2] = lr.layout[(size_t) i * 2]; out_Nx4[4 * i + 3] = lr.layout[(size_t) i * 2 + 1];
+        }
+        return n;
+    });
+}
+
+int bark_hip_long_chunk_audio(struct bark_context * bctx, int i, float ** data) {
+    if (!bctx || i < 0 || i >= (int) bctx->long_result.chunks.size()) return -1;
+    if (data) *data = bctx->long_result.chunks[(size_t) i].audio.data();
+    return (int) bctx->long_result.chunks[(size_t) i].audio.size();
+}
+
+int bark_hip_long_chunk_tokens(struct bark_context * bctx, int i, int stage, int32_t * out, int capacity) {
+    if (!bctx || i < 0 || i >= (int) bctx->long_result.chunks.size() || stage < 0 || stage > 2) return -1;
+    const auto & r = bctx->long_result.chunks[(size_t) i];
+    const std::vector<int32_t> & v = stage == 0 ? r.semantic : stage == 1 ? r.coarse : r.fine;
+    if (!out || capacity < (int) v.size()) return -1;
+    if (!v.empty()) memcpy(out, v.data(), v.size() * 4);
+    return (int) v.size();
+}
+
+int bark_hip_join_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const struct bark_hip_join_params * params,
+                       const struct bark_hip_audio_format * to, void * out, int capacity_bytes, int32_t * layout_Nx2) {
+    if (!bctx || !pcm || !n) return -1;
+    const bark_hip_join_params p = params ? *params : join_default_params();
+    const bark_hip_audio_format f = to ? *to : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
+    if (!join_call_valid(n, count, p, f)) return -1;                                      // refused before any work
+    for (int i = 0; i < count; i++) if (!pcm[i]) return -1;
+    return guarded("bark_hip_join_many", -1, [&] {
+        std::vector<int32_t> layout;
+        const std::vector<uint8_t> r = engine_join_many(bctx, pcm, n, count, p, f.sample_rate, f.sample_format, layout);
+        if (layout_Nx2) memcpy(layout_Nx2, layout.data(), layout.size() * 4);
+        if (r.empty()) return 0;                                                          // every segment trimmed away
+        if (!out || (size_t) std::max(capacity_bytes, 0) < r.size()) return -2 - (int) r.size();
+        memcpy(out, r.data(), r.size());
+        return (int) r.size();
+    });
+}
+
+double bark_hip_time_join(struct bark_context * bctx, int count, int n_each, int rate_out, int sample_format, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_join", -1.0, [&] { return engine_time_join(bctx, count, n_each, rate_out, sample_format, iters); });
+}
+double bark_hip_time_join_activity(struct bark_context * bctx, int count, int n_each, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_join_activity", -1.0, [&] { return engine_time_join(bctx, count, n_each, 24000, BARK_HIP_SAMPLE_F32, iters, true); });
+}
+
 namespace {
 // the part of a recording that bark_hip_voice_from_audio uses, and the sizes of what it makes of it
 struct VoiceAudioCounts { int n_used, n_sem, n_frames; };

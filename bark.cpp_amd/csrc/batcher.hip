@@ -8,6 +8,8 @@
 // whatever batch a request happened to travel in.  Plain C++ threads; the device is touched through the engine's entry points only, on the worker that owns the context.
 // A request may ask for its answer in another rate / sample format (bark_hip_batcher_submit_as, rule C14r): the worker converts behind the job, one
 // engine_resample_many per distinct format among the job's requests; requests in {24000, f32} take the path they always took.
+// A long text (bark_hip_batcher_submit_long, rules C15s / C15j) is one ticket over several ordinary requests: the worker that finishes the last of them
+// joins their audio with engine_join_many on its own context.
 // Job streams (bark_hip_batcher_create_ex, n_streams 1 .. 4): further workers on clones of the context (own streams, caches and graphs, the
 // same weights) serve the same queue - a lock step is a chain of ~100 small dependent kernels, so two jobs share the chip (two streams of
 // 64-slot jobs out of phase: 37.8 prompts/s against 33.2 from one, profiles/r04_staggered_jobs.txt).  Workers that start together stay in
@@ -27,10 +29,17 @@
 using namespace barkhip;
 
 struct bark_hip_batcher {
+    struct Req;
+    // A long text (bark_hip_batcher_submit_long, rules C15s / C15j): its parts are ordinary requests in the queue - they share jobs with other traffic and
+    // may be served by different workers - and `whole` is what the ticket waits for.  `left` counts the parts still out and is only touched under `mu`:
+    // the worker that brings it to zero joins the parts' audio on its own context.
+    struct Long { std::vector<std::shared_ptr<Req>> parts; std::shared_ptr<Req> whole; int left = 0; bool failed = false; bark_hip_join_params join{6000, 0, 0.0f, 0}; };
     struct Req {
+        std::shared_ptr<Long> of;                                   // a part of a long text: not in `tickets`, its audio goes to the join
         std::string text; bark_hip_request_params rp{}; bark_hip_sampling_filter flt{0, 1.0f}; VoicePtr voice; std::vector<float> pcm; bool done = false, ok = false;
         bark_hip_audio_format fmt{24000, BARK_HIP_SAMPLE_F32};      // what the answer comes in (bark_hip_batcher_submit_as); the default keeps pcm, any other fills bytes
         std::vector<uint8_t> bytes;
+        int n_parts = 1;                                            // the parts a long text's ticket stands for (bark_hip_batcher_ticket_chunks)
         bool plain() const { return fmt.sample_rate == 24000 && fmt.sample_format == BARK_HIP_SAMPLE_F32; }
     };
     bark_context * ctx = nullptr;                          // worker 0's context (the caller's); request defaults are read from it
@@ -112,6 +121,7 @@ struct bark_hip_batcher {
                 }
             }
             lk.lock();
+            std::vector<std::shared_ptr<Long>> to_join;             // long texts whose LAST part this job finished ("last" is decided here, under mu)
             for (size_t i = 0; i < batch.size(); i++) {
                 Req & r = *batch[i];
                 if (!failed && i < ctx->batch_results.size() && ctx->batch_results[i].ok) {
@@ -119,9 +129,32 @@ struct bark_hip_batcher {
                     else if (conv_ok[i]) { r.bytes = std::move(conv[i]); r.ok = true; }
                 }
                 r.done = true;
+                if (r.of) {
+                    if (!r.ok || r.pcm.empty()) r.of->failed = true;
+                    if (--r.of->left == 0) to_join.push_back(r.of);
+                }
             }
             n_batches++; n_requests += (int) batch.size(); largest = std::max(largest, (int) batch.size());
             cv_done.notify_all();
+            // the join of a finished long text, on this worker's context: nobody else touches its parts any more (left == 0), so the lock is not held meanwhile
+            for (auto & lg : to_join) {
+                lk.unlock();
+                Req & w = *lg->whole;
+                bool ok = !lg->failed;
+                if (ok) {
+                    std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> layout;
+                    for (auto & p : lg->parts) { ptr.push_back(p->pcm.data()); len.push_back((int) p->pcm.size()); }
+                    try {
+                        std::vector<uint8_t> joined = engine_join_many(ctx, ptr.data(), len.data(), (int) ptr.size(), lg->join, w.fmt.sample_rate, w.fmt.sample_format, layout);
+                        if (w.plain()) { w.pcm.resize(joined.size() / sizeof(float)); if (!joined.empty()) memcpy(w.pcm.data(), joined.data(), joined.size()); }
+                        else w.bytes = std::move(joined);
+                    } catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: join failed: %s\n", e.what()); ok = false; }
+                }
+                lk.lock();
+                lg->parts.clear();
+                w.ok = ok; w.done = true;
+                cv_done.notify_all();
+            }
         }
     }
 };
@@ -243,6 +276,55 @@ BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const c
         catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher_submit_as: %s\n", e.what()); return -1; }
     }
     return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr, fmt);
+}
+
+// A long text as ONE ticket (rules C15s / C15j): split here, on the caller's thread (the vocabulary is immutable); the parts enter the queue as ordinary
+// requests - part i with seed params->seed + i - so they share jobs with other traffic and continuous admission applies; the worker that finishes the
+// last part joins.  Only chain == 0: a chained chunk needs the one before it, which is a sequence of jobs, not a job.
+BARK_API int64_t bark_hip_batcher_submit_long(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
+                                              const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                              const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt) {
+    if (!b || !text || (filter && !filter_valid(*filter))) return -1;
+    if (fmt && (!sample_format_bytes(fmt->sample_format) || !resample_pair_supported(24000, fmt->sample_rate))) return -1;
+    const bark_hip_long_params lp = long_params ? *long_params : bark_hip_long_params{0, 0, join_default_params()};
+    if (lp.chain != 0 || !join_params_valid(lp.join)) return -1;
+    VoicePtr v;
+    std::vector<TextSpan> spans;
+    const std::string full(text);
+    try {
+        if (voice) v = engine_make_voice(b->ctx, voice);
+        spans = split_text(b->ctx->vocab, full, lp.max_tokens);
+    } catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher_submit_long: %s\n", e.what()); return -1; }
+    if (spans.empty()) spans.push_back({0, (int32_t) full.size()});      // a text without a word runs as one part
+    const bark_hip_request_params rp = params ? *params : context_request_params(b->ctx, 0);
+    auto lg = std::make_shared<bark_hip_batcher::Long>();
+    lg->join = lp.join; lg->left = (int) spans.size();
+    lg->whole = std::make_shared<bark_hip_batcher::Req>();
+    lg->whole->n_parts = (int) spans.size();
+    if (fmt) lg->whole->fmt = *fmt;
+    for (size_t i = 0; i < spans.size(); i++) {
+        auto r = std::make_shared<bark_hip_batcher::Req>();
+        r->of = lg; r->text = full.substr((size_t) spans[i].begin, (size_t) (spans[i].end - spans[i].begin)); r->rp = rp; r->rp.seed = rp.seed + (uint32_t) i;
+        lg->parts.push_back(r);
+    }
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (b->stop) { lg->parts.clear(); return -1; }
+    const int64_t t = b->next_ticket++;
+    b->tickets[t] = lg->whole;
+    for (auto & r : lg->parts) {
+        r->flt = filter ? *filter : b->default_filter;
+        r->voice = voice ? v : b->default_voice;
+        b->queue.emplace_back(t, r);
+    }
+    b->cv_work.notify_all();
+    return t;
+}
+
+BARK_API int bark_hip_batcher_ticket_chunks(struct bark_hip_batcher * b, int64_t ticket) {
+    if (!b) return -1;
+    std::lock_guard<std::mutex> lk(b->mu);
+    auto it = b->tickets.find(ticket);
+    return it == b->tickets.end() ? -1 : it->second->n_parts;
 }
 
 BARK_API int bark_hip_batcher_wait_bytes(struct bark_hip_batcher * b, int64_t ticket, void * out, int capacity_bytes) {

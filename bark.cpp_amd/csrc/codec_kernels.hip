@@ -745,4 +745,97 @@ void launch_sample_format(hipStream_t s, const float * x, void * y, size_t n, in
     hipLaunchKernelGGL(sample_format_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, y, n, fmt);
 }
 
+// ---- long-form join (rule C15j) ---------------------------------------------------------------------------------------------------
+// Activity: one wave per frame of 240 samples (four frames a workgroup), all segments in one launch.  The peak is a maximum of |x| - exact in any order -
+// folded over the wave by xor shuffles; lane 0 of an active frame moves the segment's two table entries by atomicMax, and only when the entry it reads does
+// not already cover the frame (the entries move one way, so a stale read costs an atomic, never a result).
+__global__ __launch_bounds__(256) void segment_activity_kernel(const JoinActivityArgs a, int n_frames) {
+    constexpr int S = kResampleMaxSegments + 1;
+    const int lane = (int) threadIdx.x & 63;
+    const int f = (int) blockIdx.x * 4 + ((int) threadIdx.x >> 6);       // wave-uniform
+    const bool valid = f < n_frames;
+    const int * frame_off = a.seg + 2 * S;
+    int s = 0, j = 0;
+    float peak = 0.0f;
+    if (valid) {
+        for (int hi = a.B; hi - s > 1;) { const int mid = (s + hi) >> 1; if (frame_off[mid] <= f) s = mid; else hi = mid; }      // frame_off[s] <= f < frame_off[s + 1]
+        j = f - frame_off[s];
+        const int n = a.seg[s];
+        const float * x = a.x + a.seg[S + s];
+        const int end = min(kJoinFrame * (j + 1), n);
+        for (int i = kJoinFrame * j + lane; i < end; i += 64) peak = fmaxf(peak, fabsf(x[i]));
+    }
+    for (int off = 32; off > 0; off >>= 1) peak = fmaxf(peak, __shfl_xor(peak, off, 64));
+    if (valid && lane == 0 && peak >= a.thr) {
+        int * first = a.act + 2 * s, * last = first + 1;
+        if (-j > *(volatile int *) first) atomicMax(first, -j);
+        if (j > *(volatile int *) last) atomicMax(last, j);
+    }
+}
+void launch_segment_activity(hipStream_t s, const JoinActivityArgs & a, int n_frames) {
+    if (!a.x || !a.seg || !a.act || a.B < 1 || a.B > kResampleMaxSegments || n_frames < a.B || !(a.thr >= 0.0f))
+        kernel_fail("bark-hip: the activity kernel takes 1 .. %d segments, at least a frame each, and a threshold >= 0 (got B %d, frames %d)", kResampleMaxSegments, a.B, n_frames);
+    hipLaunchKernelGGL(segment_activity_kernel, dim3((unsigned) ((n_frames + 3) / 4)), dim3(256), 0, s, a, n_frames);
+}
+
+// Join: resample_pair_kernel with another staging loop.  One workgroup = one tile of 1024 consecutive outputs of the joined signal J, which exists only
+// as the position table (copied into LDS): while it stages the tile's window, work-item i resolves J's index w0 + i to (range, offset) by binary search
+// over the ranges' first samples, reads the sample from its segment, applies the fade weight and writes +0 between the ranges and outside J - once per
+// staged sample, not once per tap.  Consecutive work-items write consecutive LDS words; the compute loop is resample_pair_kernel's (tap rows an odd
+// distance apart).  m M is formed in 64 bits once per tile (m < 2^26, M <= 160).  The identity has no table: the staged sample itself is stored.
+__global__ __launch_bounds__(256) void join_resample_kernel(const JoinResampleArgs a) {
+    __shared__ float win[kResampleWinFloats];
+    __shared__ float tab[kResampleTabFloats];
+    __shared__ int pos[3 * kResampleMaxSegments];
+    const int t = (int) threadIdx.x, tile = (int) blockIdx.x;
+    const int nt = 2 * a.half, ld = nt + 1;
+    if (a.taps) for (int i = t; i < a.L * nt; i += 256) { const int p = i / nt; tab[p * ld + (i - p * nt)] = a.taps[i]; }
+    if (t < 3 * kResampleMaxSegments) pos[t] = a.pos[t];
+    const int * start = pos, * len = pos + kResampleMaxSegments, * src = pos + 2 * kResampleMaxSegments;
+    const int m0 = tile * kResampleTile;
+    const int cnt = min(kResampleTile, a.n_out - m0);
+    const long long t0 = (long long) m0 * a.M;
+    const int base0 = (int) (t0 / a.L), ph0 = (int) (t0 - (long long) base0 * a.L);
+    const int last = base0 + (ph0 + (cnt - 1) * a.M) / a.L;              // base of the tile's last output
+    const int w0 = base0 - a.half + 1;                                   // the first sample of J the tile reads (may be < 0)
+    const int nwin = last + a.half - w0 + 1;
+    __syncthreads();
+    for (int i = t; i < nwin; i += 256) {
+        const int v = w0 + i;
+        float x = 0.0f;
+        if (v >= 0 && v < a.N) {
+            int r = 0;
+            for (int hi = a.R; hi - r > 1;) { const int mid = (r + hi) >> 1; if (start[mid] <= v) r = mid; else hi = mid; }      // start[r] <= v (start[0] == 0)
+            const int off = v - start[r], K = len[r];
+            if (off < K) {
+                x = a.x[(size_t) src[r] + (size_t) off];
+                const int d = min(off, K - 1 - off);
+                if (d < a.F) x = x * a.fade[d];
+            }
+        }
+        win[i] = x;                                                      // win[b] = J[base0 + b - half + 1]
+    }
+    __syncthreads();
+    for (int d = t; d < cnt; d += 256) {
+        const int k = ph0 + d * a.M;
+        const int b = k / a.L;
+        float acc = 0.0f;
+        if (a.taps) {
+            const float * xv = win + b, * h = tab + (k - b * a.L) * ld;
+            for (int i = 0; i < nt; i++) acc = fmaf(xv[i], h[i], acc);
+        } else acc = win[b];
+        store_sample(a.y, (size_t) (m0 + d), acc, a.fmt);
+    }
+}
+void launch_join_resample(hipStream_t s, const JoinResampleArgs & a) {
+    const bool identity = !a.taps;
+    if (!a.x || !a.y || !a.pos || a.R < 1 || a.R > kResampleMaxSegments || a.F < 0 || a.F > kJoinMaxFade || (a.F && !a.fade) || a.N < 1 || a.N > kJoinMaxSamples ||
+        a.L < 1 || a.M < 1 || a.half < 1 || a.fmt < 0 || a.fmt > 2 || (identity && (a.L != 1 || a.M != 1 || a.half != 1)) ||
+        (long long) a.n_out != ((long long) a.N * a.L + a.M - 1) / a.M || a.L * (2 * a.half + 1) > kResampleTabFloats ||
+        (long long) (kResampleTile - 1) * a.M / a.L + 2 * a.half + 1 > kResampleWinFloats)
+        kernel_fail("bark-hip: the join takes 1 .. %d ranges, 1 .. 2^25 samples and a table that fits its LDS copy (got R %d, N %d, n_out %d, L %d, M %d, half %d, F %d)",
+                    kResampleMaxSegments, a.R, a.N, a.n_out, a.L, a.M, a.half, a.F);
+    hipLaunchKernelGGL(join_resample_kernel, dim3((unsigned) ((a.n_out + kResampleTile - 1) / kResampleTile)), dim3(256), 0, s, a);
+}
+
 }  // namespace barkhip

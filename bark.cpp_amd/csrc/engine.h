@@ -241,6 +241,8 @@ struct bark_context : bark_context_memory {
     // requested format (both grown on demand) and the segment table [5][kResampleMaxSegments + 1]
     std::map<std::pair<int, int>, const float *> rp_taps;
     barkhip::DevBuf<float> rp_in; barkhip::DevBuf<uint8_t> rp_out; barkhip::DevBuf<int> rp_seg;
+    // long-form join (C15j): the segment, activity and position tables of a call, the fade table of the last fade length used (jn_fade_F; -1: none yet)
+    barkhip::DevBuf<int> jn_tab; barkhip::DevBuf<float> jn_fade; int jn_fade_F = -1;
     struct CodecGraph { barkhip::GraphExec exec; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -279,6 +281,13 @@ struct bark_context : bark_context_memory {
     } fine_batch;
     struct BatchResult { std::vector<int32_t> semantic, coarse, fine; std::vector<float> audio; bool ok = false; };
     std::vector<BatchResult> batch_results;
+    // the last bark_hip_generate_long call (C15s / C15j): the chunks' spans in the text, their results (untrimmed) and the join parameters; no chunk: none held
+    // joined / layout: what the last bark_hip_long_audio_as made, in joined_fmt (sample_rate 0: nothing yet), so that a probe for the size and the call that
+    // fetches the bytes join once
+    struct LongResult {
+        std::vector<barkhip::TextSpan> spans; std::vector<BatchResult> chunks; bark_hip_join_params join{6000, 0, 0.0f, 0};
+        std::vector<uint8_t> joined; std::vector<int32_t> layout; bark_hip_audio_format joined_fmt{0, 0};
+    } long_result;
     // lock steps (batch_step calls) of the last bark_hip_generate_batch job: [0] semantic stage, [1] coarse stage; {0, 0}: the sequential fallback took
     // the job; -1: no job has run (bark_hip_batch_lock_steps)
     int32_t job_lock_steps[2] = {-1, -1};
@@ -363,6 +372,23 @@ inline int sample_format_bytes(int fmt) { return fmt == BARK_HIP_SAMPLE_F32 ? 4 
 std::vector<uint8_t> engine_resample_many(bark_context * ctx, const float * const * pcm, const int * n, int count, int rate_in, int rate_out, int fmt,
                                           std::vector<int32_t> & n_out);
 double engine_time_resample_pair(bark_context * ctx, int n, int rate_in, int rate_out, int fmt, int iters);
+// Long-form join (C15j): count <= 64 segments of 24 kHz f32 (1 .. 1 310 720 finite samples each) -> trim by frame activity, fade, gaps of +0 between
+// the non-empty kept ranges, then format(C14r(J, 24000 -> rate_out)) of the joined signal J (N <= 2^25 samples; N == 0: no bytes) - at most two launches
+// whatever the count (threshold 0: the host writes the activity table, one launch).  layout [count][2]: first sample in J and kept samples of every segment.  Throws on a bad count / length / sample / parameter /
+// rate / format and on N > 2^25.  join_params_valid: gap >= 0, fade 0 .. 24000, threshold >= 0 and finite, pad >= 0.
+inline bark_hip_join_params join_default_params() { return bark_hip_join_params{6000, 0, 0.0f, 0}; }
+bool join_params_valid(const bark_hip_join_params & p);
+std::vector<uint8_t> engine_join_many(bark_context * ctx, const float * const * pcm, const int * n, int count, const bark_hip_join_params & p, int rate_out, int fmt,
+                                      std::vector<int32_t> & layout);
+// the layout alone: the checks and the active frames (one launch with a threshold, none without), no sample staged or filtered
+std::vector<int32_t> engine_join_layout(bark_context * ctx, const float * const * pcm, const int * n, int count, const bark_hip_join_params & p);
+// device time of the join launch (all a default call runs: threshold 0 needs no activity launch) or, activity: of the table's fill + the activity launch alone
+double engine_time_join(bark_context * ctx, int count, int n_each, int rate_out, int fmt, int iters, bool activity = false);
+// Long-form text (C15s + C15j): split, run the chunks (chain 0: ONE lock-step job, chunk i with seed rp.seed + i; chain 1: one job per chunk, chunk
+// i + 1 with the voice made of chunk i's three streams, the previous voice where that one is refused), keep the results in ctx->long_result.  Returns
+// the chunk count; throws if a chunk fails.  A text without a word runs as one chunk.
+int engine_generate_long(bark_context * ctx, const char * text, const bark_hip_long_params & lp, const bark_hip_request_params * rp, const bark_hip_sampling_filter * flt,
+                         const VoicePtr * voice);
 // kernel-level hook: latents [T][H] -> codes [n_q][T] by the RVQ kernel alone (C11q)
 std::vector<int32_t> engine_rvq_encode(bark_context * ctx, const float * latents, int T, int n_q);
 bool engine_generate(bark_context * ctx, const char * text);

@@ -669,6 +669,215 @@ double engine_time_resample_pair(bark_context * c, int n, int rate_in, int rate_
     return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_resample_pair(c->stream, a, n_tiles); }) / iters;
 }
 
+// ---- long-form join (rule C15j) -----------------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kJoinSegInts = 3 * (kResampleMaxSegments + 1), kJoinActAt = 196, kJoinPosAt = kJoinActAt + 2 * kResampleMaxSegments,
+              kJoinTabInts = kJoinPosAt + 3 * kResampleMaxSegments;
+static_assert(kJoinActAt >= kJoinSegInts, "the activity table starts behind the segment table");
+// the segment table of launch_segment_activity; returns the frame count
+int fill_activity_table(int (&seg)[3][kResampleMaxSegments + 1], const int * n, int count) {
+    memset(seg, 0, sizeof(seg));
+    for (int i = 0; i < count; i++) {
+        seg[0][i] = n[i];
+        seg[1][i + 1] = seg[1][i] + n[i];
+        seg[2][i + 1] = seg[2][i] + (n[i] + kJoinFrame - 1) / kJoinFrame;
+    }
+    return seg[2][count];
+}
+// what the join kernel reads and the caller is told: from the segments' active frames (act: -first, last; last < 0: none) to the ranges of J
+struct JoinPlan { int pos[3][kResampleMaxSegments]; int R = 0; long long N = 0; std::vector<int32_t> layout; };
+JoinPlan plan_join(const int * n, const int * in_off, const int * act, int count, const bark_hip_join_params & p) {
+    JoinPlan pl;
+    memset(pl.pos, 0, sizeof(pl.pos));
+    pl.layout.assign((size_t) count * 2, 0);
+    for (int i = 0; i < count; i++) {
+        long long a = 0, b = 0;
+        if (act[2 * i + 1] >= 0) {
+            const long long fa = -(long long) act[2 * i], fb = act[2 * i + 1];
+            a = kJoinFrame * std::max(fa - p.trim_pad_frames, 0LL);
+            b = std::min(kJoinFrame * (fb + 1 + p.trim_pad_frames), (long long) n[i]);
+        }
+        if (b > a) {
+            if (pl.R) pl.N += p.gap_samples;
+            if (pl.N + (b - a) > kJoinMaxSamples) throw std::runtime_error("join: the joined signal would pass 2^25 samples");
+            pl.pos[0][pl.R] = (int) pl.N; pl.pos[1][pl.R] = (int) (b - a); pl.pos[2][pl.R] = in_off[i] + (int) a;
+            pl.R++;
+        }
+        pl.layout[(size_t) i * 2] = (int32_t) pl.N; pl.layout[(size_t) i * 2 + 1] = (int32_t) (b - a);
+        pl.N += b - a;
+    }
+    return pl;
+}
+// the device copy of the fade table W[k] = (float) (0.5 - 0.5 cos(pi (k + 0.5) / F)): formed in double, rounded once, kept until another F is asked for
+const float * device_fade(bark_context * c, int F) {
+    if (F < 1) return nullptr;
+    if (c->jn_fade_F != F) {
+        std::vector<float> w((size_t) F);
+        for (int k = 0; k < F; k++) w[(size_t) k] = (float) (0.5 - 0.5 * cos(M_PI * ((double) k + 0.5) / (double) F));
+        c->jn_fade_F = -1;
+        c->jn_fade.reserve(c, (size_t) kJoinMaxFade);
+        HIP_OK(hipMemcpyAsync(c->jn_fade.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));                 // w is a local
+        c->jn_fade_F = F;
+    }
+    return c->jn_fade.p;
+}
+// the join kernel's arguments for a plan; L = M = half = 1 without a table (the identity)
+JoinResampleArgs join_args(bark_context * c, const JoinPlan & pl, const bark_hip_join_params & p, int rate_out, int fmt) {
+    JoinResampleArgs a;
+    const ResampleTable * t = resample_pair_table(24000, rate_out);
+    a.x = c->rp_in.p; a.y = c->rp_out.p; a.pos = c->jn_tab.p + kJoinPosAt; a.fade = device_fade(c, p.fade_samples);
+    a.taps = t ? device_taps(c, 24000, rate_out, *t) : nullptr;
+    a.R = pl.R; a.F = p.fade_samples; a.N = (int) pl.N; a.n_out = (int) resample_out_len(pl.N, 24000, rate_out); a.fmt = fmt;
+    if (t) { a.L = t->L; a.M = t->M; a.half = t->half; }
+    return a;
+}
+}  // namespace
+
+bool join_params_valid(const bark_hip_join_params & p) {
+    return p.gap_samples >= 0 && p.fade_samples >= 0 && p.fade_samples <= kJoinMaxFade && std::isfinite(p.trim_threshold) && p.trim_threshold >= 0.0f && p.trim_pad_frames >= 0;
+}
+
+namespace {
+// the join, or (layout_only) its first half: the checks, the active frames and the layout of J, without staging or filtering a sample
+std::vector<uint8_t> join_impl(bark_context * c, const float * const * pcm, const int * n, int count, const bark_hip_join_params & p, int rate_out, int fmt,
+                               std::vector<int32_t> & layout, bool layout_only) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!pcm || !n || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("join: 1 .. 64 segments in one call");
+    if (!join_params_valid(p)) throw std::runtime_error("join: gap_samples >= 0, fade_samples 0 .. 24000, trim_threshold >= 0 and finite, trim_pad_frames >= 0");
+    if (!resample_pair_supported(24000, rate_out)) throw std::runtime_error("join: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
+    const int bytes_per = sample_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("join: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    long long total_in = 0;
+    for (int i = 0; i < count; i++) {
+        if (!pcm[i] || n[i] < 1 || n[i] > kResampleMaxSamples) throw std::runtime_error("join: a segment needs 1 .. 1 310 720 samples");
+        total_in += n[i];
+    }
+    if (p.trim_threshold == 0.0f && total_in + (long long) (count - 1) * p.gap_samples > kJoinMaxSamples)      // nothing is trimmed: known before any work
+        throw std::runtime_error("join: the joined signal would pass 2^25 samples");
+    for (int i = 0; i < count; i++) for (int k = 0; k < n[i]; k++) if (!std::isfinite(pcm[i][k])) throw std::runtime_error("join: non-finite sample");
+    int seg[3][kResampleMaxSegments + 1], act[2 * kResampleMaxSegments];
+    const int n_frames = fill_activity_table(seg, n, count);
+    const bool trim = p.trim_threshold > 0.0f;                  // threshold 0: every frame is active, the host knows the table - no activity launch, no read-back
+    hipStream_t s = c->stream;
+    if (trim || !layout_only) {
+        c->rp_in.reserve(c, (size_t) total_in);
+        c->jn_tab.reserve(c, (size_t) kJoinTabInts);
+        for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->rp_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
+    }
+    if (trim) {
+        HIP_OK(hipMemcpyAsync(c->jn_tab.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemsetAsync(c->jn_tab.p + kJoinActAt, kJoinActFill, sizeof(act), s));
+        JoinActivityArgs aa;
+        aa.x = c->rp_in.p; aa.seg = c->jn_tab.p; aa.act = c->jn_tab.p + kJoinActAt; aa.B = count; aa.thr = p.trim_threshold;
+        launch_segment_activity(s, aa, n_frames);
+        HIP_OK(hipMemcpyAsync(act, c->jn_tab.p + kJoinActAt, (size_t) count * 8, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+    } else {
+        for (int i = 0; i < count; i++) { act[2 * i] = 0; act[2 * i + 1] = seg[2][i + 1] - seg[2][i] - 1; }
+    }
+    const JoinPlan pl = plan_join(n, seg[1], act, count, p);
+    layout = pl.layout;
+    if (pl.N == 0 || layout_only) return {};                     // (N == 0 needs a threshold: the uploads are behind the read-back's synchronisation)
+    const long long n_out = resample_out_len(pl.N, 24000, rate_out);
+    std::vector<uint8_t> out((size_t) n_out * (size_t) bytes_per);
+    c->rp_out.reserve(c, out.size());
+    HIP_OK(hipMemcpyAsync(c->jn_tab.p + kJoinPosAt, pl.pos, sizeof(pl.pos), hipMemcpyHostToDevice, s));
+    launch_join_resample(s, join_args(c, pl, p, rate_out, fmt));
+    HIP_OK(hipMemcpyAsync(out.data(), c->rp_out.p, out.size(), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return out;
+}
+}  // namespace
+
+std::vector<uint8_t> engine_join_many(bark_context * c, const float * const * pcm, const int * n, int count, const bark_hip_join_params & p, int rate_out, int fmt,
+                                      std::vector<int32_t> & layout) {
+    return join_impl(c, pcm, n, count, p, rate_out, fmt, layout, false);
+}
+
+std::vector<int32_t> engine_join_layout(bark_context * c, const float * const * pcm, const int * n, int count, const bark_hip_join_params & p) {
+    std::vector<int32_t> layout;
+    join_impl(c, pcm, n, count, p, 24000, BARK_HIP_SAMPLE_F32, layout, true);
+    return layout;
+}
+
+double engine_time_join(bark_context * c, int count, int n_each, int rate_out, int fmt, int iters, bool activity) {
+    HIP_OK(hipSetDevice(c->device));
+    const bark_hip_join_params p = join_default_params();
+    const int bytes_per = sample_format_bytes(fmt);
+    if (count < 1 || count > kResampleMaxSegments || n_each < 1 || n_each > kResampleMaxSamples || !resample_pair_supported(24000, rate_out) || !bytes_per ||
+        (long long) count * n_each + (long long) (count - 1) * p.gap_samples > kJoinMaxSamples)
+        throw std::runtime_error("time_join: 1 .. 64 segments of 1 .. 1 310 720 samples, 2^25 joined samples at most, a supported rate and format");
+    std::vector<int> n((size_t) count, n_each), act((size_t) count * 2);
+    int seg[3][kResampleMaxSegments + 1];
+    const int n_frames = fill_activity_table(seg, n.data(), count);
+    for (int i = 0; i < count; i++) { act[(size_t) i * 2] = 0; act[(size_t) i * 2 + 1] = seg[2][i + 1] - seg[2][i] - 1; }      // every frame is active at threshold 0
+    const JoinPlan pl = plan_join(n.data(), seg[1], act.data(), count, p);
+    c->rp_in.reserve(c, (size_t) count * (size_t) n_each);
+    c->rp_out.reserve(c, (size_t) resample_out_len(pl.N, 24000, rate_out) * (size_t) bytes_per);
+    c->jn_tab.reserve(c, (size_t) kJoinTabInts);
+    hipStream_t s = c->stream;
+    HIP_OK(hipMemsetAsync(c->rp_in.p, 0, (size_t) count * (size_t) n_each * 4, s));      // the time does not depend on the values
+    HIP_OK(hipMemcpyAsync(c->jn_tab.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->jn_tab.p + kJoinPosAt, pl.pos, sizeof(pl.pos), hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));
+    JoinActivityArgs aa;
+    aa.x = c->rp_in.p; aa.seg = c->jn_tab.p; aa.act = c->jn_tab.p + kJoinActAt; aa.B = count; aa.thr = 0.0f;
+    const JoinResampleArgs ja = join_args(c, pl, p, rate_out, fmt);
+    // the join launch - all the device work of a call with the default parameters (threshold 0 runs no activity launch) - or, apart from it, what a
+    // threshold adds in front: the activity table's fill and the activity launch, with every frame active (each one reaches for its segment's entries)
+    auto one = [&] {
+        if (!activity) { launch_join_resample(s, ja); return; }
+        HIP_OK(hipMemsetAsync(c->jn_tab.p + kJoinActAt, kJoinActFill, (size_t) count * 8, s));
+        launch_segment_activity(s, aa, n_frames);
+    };
+    iters = std::max(1, iters);
+    for (int i = 0; i < 2; i++) one();
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) one(); }) / iters;
+}
+
+// ---- long-form text: split (C15s), run the chunks as lock-step jobs, keep the results for the join (C15j) -------------------------------------------------
+int engine_generate_long(bark_context * c, const char * text, const bark_hip_long_params & lp, const bark_hip_request_params * rp, const bark_hip_sampling_filter * flt,
+                         const VoicePtr * voice) {
+    c->long_result = bark_context::LongResult();                        // a refused or failed call leaves no result behind
+    if (lp.chain != 0 && lp.chain != 1) throw std::runtime_error("generate_long: chain is 0 (one job) or 1 (every chunk continues the one before it)");
+    if (!join_params_valid(lp.join)) throw std::runtime_error("generate_long: gap_samples >= 0, fade_samples 0 .. 24000, trim_threshold >= 0 and finite, trim_pad_frames >= 0");
+    const std::string full(text);
+    std::vector<TextSpan> spans = split_text(c->vocab, full, lp.max_tokens);
+    if (spans.empty()) spans.push_back({0, (int32_t) full.size()});      // a text without a word runs as one chunk, as it does today
+    const int n = (int) spans.size();
+    const bark_context_params & p = c->params;
+    bark_hip_request_params base = rp ? *rp : bark_hip_request_params{p.temp, p.fine_temp, p.min_eos_p, p.n_steps_text_encoder, (uint32_t) c->rng()};
+    std::vector<std::string> texts;
+    std::vector<const char *> ptrs;
+    std::vector<bark_hip_request_params> rps((size_t) n, base);
+    for (int i = 0; i < n; i++) {
+        texts.push_back(full.substr((size_t) spans[(size_t) i].begin, (size_t) (spans[(size_t) i].end - spans[(size_t) i].begin)));
+        rps[(size_t) i].seed = base.seed + (uint32_t) i;                 // wraps in uint32
+    }
+    for (const std::string & t : texts) ptrs.push_back(t.c_str());
+    const std::vector<bark_hip_sampling_filter> flts((size_t) n, flt ? *flt : c->filter);
+    bark_context::LongResult res;
+    res.spans = spans; res.join = lp.join;
+    if (lp.chain == 0) {
+        const std::vector<VoicePtr> voices((size_t) n, voice ? *voice : VoicePtr());
+        if (engine_generate_batch(c, ptrs.data(), n, nullptr, rps.data(), nullptr, flts.data(), voices.data()) != n) throw std::runtime_error("generate_long: a chunk failed");
+        res.chunks = c->batch_results;
+    } else {
+        VoicePtr v = voice ? *voice : VoicePtr();
+        for (int i = 0; i < n; i++) {
+            if (engine_generate_batch(c, &ptrs[(size_t) i], 1, nullptr, &rps[(size_t) i], nullptr, &flts[(size_t) i], &v) != 1) throw std::runtime_error("generate_long: a chunk failed");
+            res.chunks.push_back(c->batch_results[0]);
+            const bark_context::BatchResult & r = res.chunks.back();
+            const bark_hip_voice_prompt vp{r.semantic.data(), (int32_t) r.semantic.size(), r.coarse.data(), (int32_t) (r.coarse.size() / 2), r.fine.data(), (int32_t) (r.fine.size() / 8)};
+            try { v = engine_make_voice(c, &vp); } catch (const std::exception &) {}          // a history too short to continue from: the next chunk keeps this one's voice
+        }
+    }
+    for (const bark_context::BatchResult & r : res.chunks) if (!r.ok || r.audio.empty() || r.audio.size() > (size_t) kResampleMaxSamples) throw std::runtime_error("generate_long: a chunk gave no audio");
+    c->long_result = std::move(res);
+    return n;
+}
+
 VoicePtr engine_voice_from_audio(bark_context * c, const float * pcm, int n) {
     if (!c->hub) throw std::runtime_error("voice from audio: no semantic encoder loaded (bark_hip_load_semantic_encoder)");
     if (!c->codec.enc.present) throw std::runtime_error("voice from audio: the model file holds no codec encoder");

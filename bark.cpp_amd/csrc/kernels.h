@@ -362,4 +362,23 @@ void launch_resample_pair(hipStream_t s, const ResamplePairArgs & a, int n_tiles
 // y[i] = format(x[i]) for n samples (fmt 1 or 2): the formats alone, where no filter runs
 void launch_sample_format(hipStream_t s, const float * x, void * y, size_t n, int fmt);
 
+// ---- long-form join: trim, fade, gaps and the output format of up to 64 segments in two launches (rule C15j; codec_kernels.hip) ----
+// segment_activity_kernel: frame j of segment s covers x[in_off[s] + 240 j ..] up to the segment's end and is active iff max |x| >= thr.  seg is a device
+// table [3][kResampleMaxSegments + 1] of ints: lengths, input offsets, frame offsets (prefix sums of ceil(n / 240), closed by the total).  act [2 B]:
+// act[2 s] = -(first active frame), act[2 s + 1] = last active frame, both by atomicMax (the first frame is held negated, so one integer maximum serves
+// both ends); the caller fills it with the byte kJoinActFill before the launch (hipMemsetAsync): an int below every frame index and every negated
+// one, which is what a segment without an active frame keeps (act[2 s + 1] < 0).
+constexpr int kJoinFrame = 240, kJoinActFill = 0x80, kJoinMaxFade = 24000, kJoinMaxSamples = 1 << 25;
+struct JoinActivityArgs { const float * x = nullptr; const int * seg = nullptr; int * act = nullptr; int B = 1; float thr = 0.0f; };
+void launch_segment_activity(hipStream_t s, const JoinActivityArgs & a, int n_frames);
+// join_resample_kernel: launch_resample_pair's tile, table and fmaf chain over the VIRTUAL signal J of N samples: pos is a device table
+// [3][kResampleMaxSegments] of ints for the R non-empty kept ranges in order - first sample in J (pos[0][0] == 0), length, offset of the range's first
+// sample in x; sample k of a range of length K is x * fade[d] (one f32 product) where d = min(k, K - 1 - k) < F, else x itself; J is +0 between the ranges
+// and outside [0, N).  taps == nullptr (with L = M = half = 1): the identity - the staged sample itself goes through the format's epilogue.
+struct JoinResampleArgs {
+    const float * x = nullptr; void * y = nullptr; const float * taps = nullptr; const int * pos = nullptr; const float * fade = nullptr;
+    int R = 1, F = 0, N = 0, n_out = 0, L = 1, M = 1, half = 1, fmt = 0;
+};
+void launch_join_resample(hipStream_t s, const JoinResampleArgs & a);
+
 }  // namespace barkhip

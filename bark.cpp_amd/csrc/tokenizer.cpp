@@ -3,7 +3,9 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <regex>
+#include <stdexcept>
 
 namespace barkhip {
 
@@ -87,6 +89,73 @@ std::vector<int32_t> build_semantic_prompt(const Vocab & vocab, const PromptPara
     ids.insert(ids.end(), 256, p.semantic_pad_token);
     ids.push_back(p.semantic_infer_token);
     return ids;
+}
+
+// ---- long-form text: the splitter (rule C15s) ----------------------------------------------------------------------------------------------------------
+namespace {
+inline bool split_space(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v'; }
+inline bool ends_with(const char * w, size_t n, const char * tail, size_t k) { return n >= k && memcmp(w + n - k, tail, k) == 0; }
+struct SplitWord { int32_t begin, end; bool sentence, clause; };
+// the word's length without its trailing closers
+size_t strip_closers(const char * w, size_t n) {
+    for (;;) {
+        if (n && (w[n - 1] == '"' || w[n - 1] == '\'' || w[n - 1] == ')' || w[n - 1] == ']' || w[n - 1] == '}')) n -= 1;
+        else if (ends_with(w, n, "\xE2\x80\x9D", 3) || ends_with(w, n, "\xE2\x80\x99", 3)) n -= 3;
+        else if (ends_with(w, n, "\xC2\xBB", 2)) n -= 2;
+        else return n;
+    }
+}
+}  // namespace
+
+std::vector<TextSpan> split_text(const Vocab & vocab, const std::string & text, int max_tokens) {
+    if (max_tokens < 0 || max_tokens > 255) throw std::runtime_error("split_text: max_tokens is 0 (one sentence per chunk) or 1 .. 255");
+    const bool merge = max_tokens > 0;
+    const int B = merge ? max_tokens : 255;
+    std::vector<SplitWord> words;
+    const size_t len = text.size();
+    for (size_t i = 0; i < len;) {
+        while (i < len && split_space((unsigned char) text[i])) i++;
+        if (i >= len) break;
+        size_t e = i;
+        while (e < len && !split_space((unsigned char) text[e])) e++;
+        size_t g = e;
+        bool line_break = false;
+        while (g < len && split_space((unsigned char) text[g])) { line_break |= text[g] == '\n'; g++; }
+        const char * w = text.data() + i;
+        const size_t n = e - i, k = strip_closers(w, n);
+        SplitWord sw;
+        sw.begin = (int32_t) i; sw.end = (int32_t) e;
+        sw.sentence = line_break || (k && (w[k - 1] == '.' || w[k - 1] == '!' || w[k - 1] == '?')) || ends_with(w, k, "\xE2\x80\xA6", 3);
+        sw.clause = (k && (w[k - 1] == ',' || w[k - 1] == ';' || w[k - 1] == ':')) || (n == 1 && w[0] == '-') ||
+                    (n == 3 && (memcmp(w, "\xE2\x80\x93", 3) == 0 || memcmp(w, "\xE2\x80\x94", 3) == 0));
+        words.push_back(sw);
+        i = g;
+    }
+    std::vector<int32_t> ids(257);
+    auto count = [&](int s, int e) {
+        const std::string span = text.substr((size_t) words[(size_t) s].begin, (size_t) (words[(size_t) e].end - words[(size_t) s].begin));
+        return wordpiece_encode(vocab, span.c_str(), ids.data(), 257, false);
+    };
+    std::vector<TextSpan> chunks;
+    const int nw = (int) words.size();
+    for (int s = 0; s < nw;) {
+        int E = s;                                               // a single word over B is a chunk of its own
+        if (count(s, s) <= B) while (E + 1 < nw && count(s, E + 1) <= B) E++;
+        int cut = -1;
+        if (merge) {
+            if (E == nw - 1) cut = E;
+            else for (int e = E; e >= s && cut < 0; e--) if (words[(size_t) e].sentence) cut = e;
+        } else {
+            for (int e = s; e <= E && cut < 0; e++) if (words[(size_t) e].sentence) cut = e;
+            if (cut < 0 && E == nw - 1) cut = E;
+        }
+        for (int e = E; e >= s && cut < 0; e--) if (words[(size_t) e].clause) cut = e;
+        if (cut < 0) cut = E;
+        if ((int) chunks.size() == kSplitMaxChunks) throw std::runtime_error("split_text: the text gives more than 64 chunks");
+        chunks.push_back({words[(size_t) s].begin, words[(size_t) cut].end});
+        s = cut + 1;
+    }
+    return chunks;
 }
 
 }  // namespace barkhip

@@ -28,4 +28,17 @@ struct PromptParams {
 // 256 text slots (+offset, padded) | 256 semantic-history pads | infer token  -> 513 ids
 std::vector<int32_t> build_semantic_prompt(const Vocab & vocab, const PromptParams & p, const char * text, bool log_unknown);
 
+// Long-form text (rule C15s): the chunks of a text of any length as byte spans [begin, end) into it, each within the 256 text
+// slots of a prompt.  Whitespace is space, \t, \n, \r, \f, \v; a word is a maximal run of other bytes; count(span) is wordpiece_encode of the span's
+// bytes with n_max = 257 (256: over).  A word ends a SENTENCE if, with trailing closers (" ' ) ] } U+201D U+2019 U+00BB) stripped, its last byte is
+// . ! ? or it ends in U+2026, or if the whitespace behind it holds a \n; it ends a CLAUSE if the stripped last byte is , ; : or the whole word is
+// - U+2013 U+2014.  Budget B: max_tokens 0 -> 255 without merging (one sentence per chunk), 1 .. 255 -> max_tokens with greedy merging.
+// From word s: E = the last word with count(s .. e) <= B for every e up to it (a single word over B is a chunk of its own).  E the last word: the
+// chunk is s .. end (without merging the first sentence end in [s, E] still ends it).  Else the cut is the sentence end in [s, E] (the LAST with
+// merging, the FIRST without), else the last clause end in [s, E], else E.  No word: no chunk.  Throws std::runtime_error for max_tokens outside
+// 0 .. 255 and for more than kSplitMaxChunks chunks.
+constexpr int kSplitMaxChunks = 64;
+struct TextSpan { int32_t begin, end; };
+std::vector<TextSpan> split_text(const Vocab & vocab, const std::string & text, int max_tokens);
+
 }  // namespace barkhip

@@ -22,9 +22,14 @@
 // "s16" | "mulaw" in a /bark request (defaults: --sample-rate / --format, 24000 and f32) - the answer is a WAV with the matching header (IEEE float; 16-bit PCM;
 // 8-bit mu-law with a fact chunk), an unsupported value is answered 400.  POST /voices?name=NAME&resample=1 (for --voice-audio: --voice-audio-resample) takes a
 // recording at any of those rates and brings it to 24 kHz with bark_hip_resample on the encoder's clone; without the switch another rate stays a 400.
+// Long texts (rules C15s / C15j of bark_mi355x.h): "long": true in a /bark request (default: --long) takes a text of any length - it is split into chunks
+// ("max_tokens": 0 one sentence per chunk, 1 .. 255 greedy merging; default --max-tokens), the chunks travel through the collector as ordinary requests
+// (chunk i with seed + i) and their audio is joined on the device with "gap_ms" of silence between them (default --gap-ms, 250) at the request's
+// "sample_rate" / "format"; the answer carries X-Bark-Chunks: n.  More than 64 chunks or a malformed field is a 400.  Without "long" and --long a request
+// is served as before.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw] [--long] [--max-tokens n] [--gap-ms n]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -65,6 +70,7 @@ struct Options {
     std::vector<std::string> voice_audio;          // --voice-audio name=file.wav
     bool voice_audio_resample = false;             // --voice-audio-resample: --voice-audio recordings at any supported rate
     int sample_rate = 24000; std::string format = "f32";      // --sample-rate / --format: what a request without "sample_rate" / "format" is answered in
+    bool long_form = false; int max_tokens = 0, gap_ms = 250;  // --long / --max-tokens / --gap-ms: what a request without "long" / "max_tokens" / "gap_ms" gets
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -76,9 +82,10 @@ bool send_all(int fd, const char * p, size_t n) {
     return true;
 }
 
-void respond(int fd, int status, const char * reason, const char * type, const std::string & body) {
-    char head[256];
-    const int n = snprintf(head, sizeof(head), "HTTP/1.1 %d %s\r\nContent-Type: %s\r\nContent-Length: %zu\r\nConnection: close\r\n\r\n", status, reason, type, body.size());
+// extra: further header lines, each closed by \r\n (X-Bark-Chunks of a long answer)
+void respond(int fd, int status, const char * reason, const char * type, const std::string & body, const char * extra = "") {
+    char head[320];
+    const int n = snprintf(head, sizeof(head), "HTTP/1.1 %d %s\r\nContent-Type: %s\r\nContent-Length: %zu\r\n%sConnection: close\r\n\r\n", status, reason, type, body.size(), extra);
     if (send_all(fd, head, (size_t) n)) send_all(fd, body.data(), body.size());
 }
 
@@ -86,6 +93,10 @@ std::atomic<uint32_t> next_seed{0};
 bark_hip_request_params request_defaults{};            // the context's sampling parameters (a request with its own filter carries them explicitly)
 bark_hip_sampling_filter filter_defaults{0, 1.0f};
 bark_hip_audio_format format_defaults{24000, BARK_HIP_SAMPLE_F32};
+// long texts (rules C15s / C15j): the route is taken by requests with "long": true (or by all of them under --long); the splitter's budget and the gap
+struct LongDefaults { bool on = false; int32_t max_tokens = 0, gap_ms = 250; } long_defaults;
+constexpr int kMaxGapMs = 60000;
+bool long_valid(int32_t max_tokens, int32_t gap_ms) { return max_tokens >= 0 && max_tokens <= 255 && gap_ms >= 0 && gap_ms <= kMaxGapMs; }
 bool format_valid(const bark_hip_audio_format & f) { return f.sample_format >= 0 && f.sample_format <= 2 && bark_hip_resample_out_len(1, 24000, f.sample_rate) >= 1; }
 // the voices by name: read by every /bark request, written by POST /voices.  An entry is never changed, only replaced: a request that has looked its
 // voice up keeps it alive through its shared_ptr while a later POST puts another one under the same name
@@ -227,6 +238,16 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 ::close(fd);
                 return;
             }
+            // "long": true / false, "max_tokens": 0 .. 255, "gap_ms": 0 .. 60000 - the long-form route; checked here as well, for the same reason
+            bool is_long = long_defaults.on;
+            int32_t max_tokens = long_defaults.max_tokens, gap_ms = long_defaults.gap_ms;
+            const int hl = barkhttp::json_bool(body, "long", is_long), hm = json_int(body, "max_tokens", max_tokens), hg = json_int(body, "gap_ms", gap_ms);
+            if (hl < 0 || hm < 0 || hg < 0 || !long_valid(max_tokens, gap_ms)) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"long\" must be true or false, \"max_tokens\" an integer in 0 .. 255 and \"gap_ms\" an integer in 0 .. 60000");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
             const bool plain = af.sample_rate == 24000 && af.sample_format == BARK_HIP_SAMPLE_F32;
             // "voice": absent - no voice; otherwise a string that names a voice of the table (held until the answer is sent)
             std::shared_ptr<const VoiceFile> vf;
@@ -243,6 +264,33 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
             }
             uint32_t seed = 0;
             if (!json_uint(body, "seed", seed)) seed = next_seed.fetch_add(1);
+            if (is_long) {
+                // one ticket for the whole text (bark_hip_batcher_submit_long splits on this connection's thread; chunk i runs with seed + i); the answer
+                // is the joined audio in the request's rate and format, the chunk count travels in X-Bark-Chunks.  A text of more than 64 chunks is a 400
+                bark_hip_request_params rp = request_defaults; rp.seed = seed;
+                bark_hip_voice_prompt vp{};
+                if (vf) vp = bark_hip_voice_prompt{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
+                                                   vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
+                const bark_hip_long_params lp{max_tokens, 0, {gap_ms * 24, 0, 0.0f, 0}};
+                ticket = bark_hip_batcher_submit_long(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af);
+                if (ticket <= 0) {
+                    respond(fd, 400, "Bad Request", "text/plain", "the text gives more than 64 chunks");
+                } else {
+                    char extra[64];
+                    snprintf(extra, sizeof(extra), "X-Bark-Chunks: %d\r\n", bark_hip_batcher_ticket_chunks(batcher, ticket));
+                    int nb = bark_hip_batcher_wait_bytes(batcher, ticket, nullptr, 0);                 // probe: -(2 + bytes)
+                    if (nb <= -2) {
+                        std::vector<char> bytes((size_t) std::max(-nb - 2, 1));
+                        nb = bark_hip_batcher_wait_bytes(batcher, ticket, bytes.data(), -nb - 2);
+                        const int width = af.sample_format == BARK_HIP_SAMPLE_F32 ? 4 : af.sample_format == BARK_HIP_SAMPLE_S16 ? 2 : 1;
+                        if (nb >= 0) respond(fd, 200, "OK", "audio/wav", barkhttp::wav_samples(bytes.data(), nb / width, af.sample_rate, af.sample_format), extra);
+                    }
+                    if (nb < 0) respond(fd, 500, "Internal Server Error", "text/plain", "Internal Server Error");
+                }
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
             if (!plain) {
                 bark_hip_request_params rp = request_defaults; rp.seed = seed;
                 bark_hip_voice_prompt vp{};
@@ -288,7 +336,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")]\n", argv0);
 }
 
 }  // namespace
@@ -316,11 +364,16 @@ int main(int argc, char ** argv) {
         else if (a == "--voice-audio-resample") o.voice_audio_resample = true;
         else if (a == "--sample-rate") o.sample_rate = atoi(next("--sample-rate"));
         else if (a == "--format") o.format = next("--format");
+        else if (a == "--long") o.long_form = true;
+        else if (a == "--max-tokens") o.max_tokens = atoi(next("--max-tokens"));
+        else if (a == "--gap-ms") o.gap_ms = atoi(next("--gap-ms"));
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
     format_defaults = bark_hip_audio_format{o.sample_rate, barkhttp::sample_format_of(o.format)};
     if (!format_valid(format_defaults)) { fprintf(stderr, "%s: --sample-rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and --format f32, s16 or mulaw\n", argv[0]); return 1; }
+    long_defaults.on = o.long_form; long_defaults.max_tokens = o.max_tokens; long_defaults.gap_ms = o.gap_ms;
+    if (!long_valid(o.max_tokens, o.gap_ms)) { fprintf(stderr, "%s: --max-tokens must be 0 .. 255 and --gap-ms 0 .. 60000\n", argv[0]); return 1; }
     {
         std::map<std::string, VoiceFile> files;
         for (const std::string & v : o.voices) {

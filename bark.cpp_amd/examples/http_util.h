@@ -1,6 +1,7 @@
 // http_util.h - the request-side helpers of batch_server.cpp (flat-JSON field access, 32-bit float WAV framing, WAV parsing, voice prompt files), header-only
 // so that a CPU test can drive them without a device (tests/test_host_frontend.py, tests/test_voice_audio_frontend.py).
 #pragma once
+#include <cctype>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +68,23 @@ inline bool json_uint(const std::string & js, const char * key, uint32_t & out) 
     if (p >= js.size() || js[p] < '0' || js[p] > '9') return false;
     out = (uint32_t) strtoul(js.c_str() + p, nullptr, 10);
     return true;
+}
+
+// the value of `key` as a boolean (the literals true / false): 0 the key is absent, 1 *out holds it, -1 the key is there with another value
+inline int json_bool(const std::string & js, const char * key, bool & out) {
+    const std::string pat = std::string("\"") + key + "\"";
+    size_t p = js.find(pat);
+    if (p == std::string::npos) return 0;
+    p = js.find(':', p + pat.size());
+    if (p == std::string::npos) return -1;
+    p++;
+    while (p < js.size() && (js[p] == ' ' || js[p] == '\t')) p++;
+    const bool t = js.compare(p, 4, "true") == 0, f = js.compare(p, 5, "false") == 0;
+    if (!t && !f) return -1;
+    const size_t e = p + (t ? 4 : 5);
+    if (e < js.size() && (isalnum((unsigned char) js[e]) || js[e] == '_')) return -1;
+    out = t;
+    return 1;
 }
 
 // the value of `key` as a number: 0 the key is absent, 1 *out holds it, -1 the key is there but its value is not a number (a server answers 400)

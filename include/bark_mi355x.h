@@ -184,6 +184,70 @@ BARK_API int bark_hip_batch_audio_as(struct bark_context * bctx, int i, const st
  * `iters` launches (hipEvents on the context's stream).  Returns < 0 on error. */
 BARK_API double bark_hip_time_resample_pair(struct bark_context * bctx, int n, int rate_in, int rate_out, int sample_format, int iters);
 
+/* Long-form text (rules C15s and C15j): a text of any length in, one recording out.  A call of this API speaks at most 256 text
+ * slots and n_steps_text_encoder semantic steps (about 15 s); a longer text is split into chunks, the chunks run as ONE lock-step job (one weight read
+ * per step for all of them) and their audio is joined on the device - trim, fade, gaps, rate and format in two launches.
+ *
+ * C15s, the splitter.  Whitespace is the six ASCII bytes space \t \n \r \f \v; a word is a maximal run of other bytes; count(span) is what
+ * bark_hip_bert_tokenize returns for the span's bytes with n_max = 257 (256 means "over").  A word ends a SENTENCE if, with its trailing closers
+ * (" ' ) ] } and U+201D U+2019 U+00BB) stripped, its last byte is . ! or ? or it ends in U+2026, or if the whitespace behind it holds a \n.  It ends a
+ * CLAUSE if the stripped last byte is , ; or : or the whole word is - U+2013 or U+2014.  Budget: max_tokens == 0 gives B = 255 and no merging (one
+ * sentence per chunk, as Suno's long-form notebook does); 1 <= max_tokens <= 255 gives B = max_tokens with greedy merging; anything else is refused.
+ * From word s: extend e word by word while count(s .. e) <= B, E = the last e that fits (a single word over B is a chunk of its own; the tokenizer cuts
+ * it as it always did).  E the last word: the chunk is s .. end - without merging the first sentence end in [s, E] still ends it.  Otherwise the cut is
+ * a sentence end in [s, E] (the LAST with merging, the FIRST without), else the last clause end in [s, E], else E.  A text without a word gives no chunk;
+ * more than 64 chunks is an error.
+ * bark_hip_split_text: the chunks of `text` as byte spans spans_Nx2[2 i] = begin, [2 i + 1] = end; returns their count, or -1 (max_tokens outside
+ * 0 .. 255, more than 64 chunks, capacity_chunks too small).  Needs no device.
+ *
+ * C15j, the join.  count <= 64 segments of 24 kHz f32, 1 .. 1 310 720 finite samples each.  Frame j of a segment covers its samples [240 j, min(240 (j + 1), n))
+ * and is active iff max |x| >= trim_threshold (0: every frame).  With a, b the first and last active frame the kept range is
+ * [240 max(a - trim_pad_frames, 0), min(240 (b + 1 + trim_pad_frames), n)); no active frame: nothing is kept.  Fade: W[k] = (float) (0.5 - 0.5 cos(pi (k + 0.5) / F)),
+ * k < F = fade_samples, formed in double and rounded once; sample k of a kept range of length K becomes x * W[d] (one f32 product) where
+ * d = min(k, K - 1 - k) < F, and stays x otherwise.  Layout: the kept ranges in order with gap_samples of +0 between consecutive NON-EMPTY ranges, none
+ * in front of the first or behind the last: the joined signal J of N <= 2^25 samples.  Result: format(C14r(J, 24000 -> rate)) as defined above for one
+ * recording holding J - for the seven other rates and for the identity (24000: no filter); n_out = ceil(N L / M); N == 0 gives 0 bytes.  At most two
+ * launches per call whatever the count: one finds the active frames of all segments (not run at threshold 0, where every frame is active), one stages J's samples tile by tile (segment lookup and fade once per staged
+ * sample) and runs C14r's chain over them; J itself is never written out for the filtered rates. */
+struct bark_hip_join_params {
+    int32_t gap_samples;      /* >= 0; default 6000, the notebook's 0.25 s */
+    int32_t fade_samples;     /* F, 0 .. 24000; default 0                   */
+    float   trim_threshold;   /* >= 0 and finite; 0 = off                   */
+    int32_t trim_pad_frames;  /* >= 0                                       */
+};
+struct bark_hip_long_params { int32_t max_tokens; int32_t chain; struct bark_hip_join_params join; };
+BARK_API int bark_hip_split_text(struct bark_context * bctx, const char * text, int max_tokens, int32_t * spans_Nx2, int capacity_chunks);
+/* Splits `text` (C15s) and generates every chunk.  NULL pointers take the defaults: long_params {0, 0, {6000, 0, 0, 0}}, the context's parameters
+ * with a seed drawn from the context's generator, the context's filter, the context's voice.  chain == 0: all chunks run in ONE
+ * bark_hip_generate_batch_voiced job with the given voice; chunk i has seed params->seed + i (wrapping in uint32).  chain == 1: one job per chunk, with
+ * the same seeds; chunk i + 1 takes the three token streams of chunk i as its voice (where bark_hip_set_voice_prompt would refuse those - a history too
+ * short - it keeps the voice chunk i had).  In both modes chunk i is bit-identical to bark_hip_generate_batch_voiced of that chunk's text alone with
+ * that seed, filter and voice.  A text without a word runs as one chunk.  Returns the chunk count, or -1 (a refusal of the splitter, bad join
+ * parameters, chain outside 0 .. 1, a chunk that failed: no result is held then).  The results stay with the context until its next long call:
+ * bark_hip_long_audio_as: the joined audio (C15j over the chunks' PCM with long_params->join) at fmt's rate and format (NULL: 24000 f32); returns the
+ *   byte count, -(2 + bytes) if capacity_bytes is too small (out may then be NULL), -1 (no long result held, an unsupported format).
+ * bark_hip_long_chunks: out_Nx4[4 i ..] = text begin, text end, first sample in J, kept samples in J of chunk i; returns the chunk count or -1.
+ * bark_hip_long_chunk_audio / _tokens: the untrimmed 24 kHz PCM and the token streams of chunk i, as bark_hip_batch_audio / bark_hip_batch_tokens. */
+BARK_API int bark_hip_generate_long(struct bark_context * bctx, const char * text, const struct bark_hip_long_params * long_params,
+                                    const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                    const struct bark_hip_voice_prompt * voice);
+BARK_API int bark_hip_long_audio_as(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes);
+BARK_API int bark_hip_long_chunks(struct bark_context * bctx, int32_t * out_Nx4, int capacity_chunks);
+BARK_API int bark_hip_long_chunk_audio(struct bark_context * bctx, int i, float ** data);
+BARK_API int bark_hip_long_chunk_tokens(struct bark_context * bctx, int i, int stage, int32_t * out, int capacity);
+/* The join alone (C15j) on caller audio: pcm[i] holds n[i] samples at 24 kHz.  params == NULL: {6000, 0, 0, 0}; to == NULL: 24000 f32.
+ * layout_Nx2 (optional): first sample in J and kept samples of every segment (an empty range sits where the next one starts).  Returns the bytes
+ * written (0: every segment was trimmed away), -(2 + bytes) if capacity_bytes is too small (out may then be NULL; layout_Nx2 is filled), or -1 with the
+ * context still usable: count outside 1 .. 64, n[i] outside 1 .. 1 310 720, a sample that is not finite, an unsupported rate or format, a negative gap,
+ * fade or pad, a fade above 24000, a threshold that is negative or not finite, N above 2^25. */
+BARK_API int bark_hip_join_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const struct bark_hip_join_params * params,
+                                const struct bark_hip_audio_format * to, void * out, int capacity_bytes, int32_t * layout_Nx2);
+/* Device time (us) of ONE join over `count` segments of n_each samples with the default parameters - the join launch, which is all such a call runs (see
+ * above: no activity launch at threshold 0) - averaged over `iters` launches (hipEvents on the context's stream).  bark_hip_time_join_activity: what a
+ * threshold adds in front, timed apart: the activity table's fill and the activity launch over the same segments with every frame active.  < 0 on error. */
+BARK_API double bark_hip_time_join(struct bark_context * bctx, int count, int n_each, int rate_out, int sample_format, int iters);
+BARK_API double bark_hip_time_join_activity(struct bark_context * bctx, int count, int n_each, int iters);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);
@@ -322,6 +386,20 @@ BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const c
                                             const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
                                             const struct bark_hip_audio_format * fmt);
 BARK_API int bark_hip_batcher_wait_bytes(struct bark_hip_batcher * b, int64_t ticket, void * out, int capacity_bytes);
+/* A long text as ONE ticket (bark_hip_generate_long's rules C15s / C15j; NULL pointers take its defaults, params == NULL: the context's with seed 0).
+ * Only long_params->chain == 0 is accepted.  The text is split at submit time and its parts enter the queue as ordinary requests - part i with seed
+ * params->seed + i - so they share jobs with other traffic and continuous admission applies; the worker that finishes the ticket's last part joins the
+ * parts' audio on its own context, at fmt's rate and format.  bark_hip_batcher_wait_bytes (or bark_hip_batcher_wait for {24000, F32}) returns the joined
+ * audio: what bark_hip_generate_long + bark_hip_long_audio_as give on a fresh context with the same arguments.  If a part fails, the ticket fails.
+ * Returns the ticket, or -1: chain != 0, bad join parameters, a refusal of the splitter, an unsupported format, a bad filter or voice.
+ * Cost on the CALLER's thread: the splitter runs here, before the call returns.  It counts every candidate span with the tokenizer itself (std::regex) and
+ * is quadratic in the words of a chunk: well under a millisecond for a sentence, milliseconds for a paragraph, up to seconds for 64 chunks of 250 word
+ * pieces each.  Call it from the thread that serves the request (as bark_batch_server does), never from an accept loop.
+ * bark_hip_batcher_ticket_chunks: the number of parts a ticket stands for (1 for an ordinary request) while the ticket is valid, else -1. */
+BARK_API int64_t bark_hip_batcher_submit_long(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
+                                              const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                              const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt);
+BARK_API int bark_hip_batcher_ticket_chunks(struct bark_hip_batcher * b, int64_t ticket);
 BARK_API void bark_hip_batcher_stats(struct bark_hip_batcher * b, int * n_batches, int * n_requests, int * largest_batch);
 /* requests that joined a job that was already running (continuous admission: while the semantic stage of a job has free slots, requests
  * arriving in the meantime are taken along, up to max_batch per job) */
