@@ -6,5 +6,5 @@ The directory name contains a dot, so import it through `load_package()` of the 
 """
 from . import voice  # noqa: F401
 from .api import (BarkContext, Batcher, BarkContextParams, BarkHipAudioFormat, BarkHipJoinParams, BarkHipLongParams, BarkHipStats, BarkHipVoicePrompt, audio_format,  # noqa: F401
-                  build_library, default_params, join_params, library_path, load_library)
+                  build_library, default_params, join_params, library_path, load_library, speed_permille)
 from .voice import VoicePrompt  # noqa: F401

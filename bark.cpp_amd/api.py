@@ -8,6 +8,7 @@ There is NO fallback: if the HIP library is missing or no GPU is present, loadin
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -78,6 +79,11 @@ def audio_format(rate: int = 24000, fmt="f32") -> BarkHipAudioFormat:
     return BarkHipAudioFormat(int(rate), SAMPLE_FORMATS[fmt] if isinstance(fmt, str) else int(fmt))
 
 
+def speed_permille(speed) -> int:
+    """A speaking rate as the C interface takes it: lround(1000 speed), as bark_batch_server converts its "speed" field."""
+    return int(math.floor(1000.0 * float(speed) + 0.5))
+
+
 def _voice_struct(voice):
     """(struct, arrays that must stay alive while it is used) for a voice.VoicePrompt or any object with semantic / coarse [T][2] / fine [T][8]."""
     sem = np.ascontiguousarray(voice.semantic, dtype=np.int32).reshape(-1)
@@ -136,6 +142,8 @@ EXPORTS = [
     "bark_hip_batcher_submit_as", "bark_hip_batcher_wait_bytes", "bark_hip_time_resample_pair",
     "bark_hip_split_text", "bark_hip_generate_long", "bark_hip_long_audio_as", "bark_hip_long_chunks", "bark_hip_long_chunk_audio", "bark_hip_long_chunk_tokens",
     "bark_hip_join_many", "bark_hip_time_join", "bark_hip_batcher_submit_long", "bark_hip_batcher_ticket_chunks", "bark_hip_time_join_activity",
+    "bark_hip_tempo_out_len", "bark_hip_tempo_window", "bark_hip_tempo", "bark_hip_tempo_many", "bark_hip_tempo_positions", "bark_hip_get_audio_at",
+    "bark_hip_batch_audio_at", "bark_hip_long_audio_at", "bark_hip_batcher_submit_at", "bark_hip_batcher_submit_long_at", "bark_hip_time_tempo",
 ]
 
 
@@ -226,6 +234,22 @@ def load_library() -> C.CDLL:
     lib.bark_hip_long_chunk_audio.argtypes = [vp, C.c_int, C.POINTER(C.POINTER(C.c_float))]
     lib.bark_hip_long_chunk_tokens.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int]
     lib.bark_hip_join_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.POINTER(BarkHipJoinParams), C.POINTER(BarkHipAudioFormat), vp, C.c_int, ip]
+    lib.bark_hip_tempo_out_len.argtypes = [C.c_int, C.c_int]
+    lib.bark_hip_tempo_window.argtypes = [fp]
+    lib.bark_hip_tempo.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.c_int]
+    lib.bark_hip_tempo_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, ip, C.POINTER(BarkHipAudioFormat), vp, C.c_int, ip]
+    lib.bark_hip_tempo_positions.argtypes = [vp, fp, C.c_int, C.c_int, ip, C.c_int]
+    lib.bark_hip_get_audio_at.argtypes = [vp, C.POINTER(BarkHipAudioFormat), C.c_int, vp, C.c_int]
+    lib.bark_hip_batch_audio_at.argtypes = [vp, C.c_int, C.POINTER(BarkHipAudioFormat), C.c_int, vp, C.c_int]
+    lib.bark_hip_long_audio_at.argtypes = [vp, C.POINTER(BarkHipAudioFormat), C.c_int, vp, C.c_int]
+    lib.bark_hip_batcher_submit_at.restype = C.c_int64
+    lib.bark_hip_batcher_submit_at.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter), C.POINTER(BarkHipVoicePrompt),
+                                               C.POINTER(BarkHipAudioFormat), C.c_int]
+    lib.bark_hip_batcher_submit_long_at.restype = C.c_int64
+    lib.bark_hip_batcher_submit_long_at.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipLongParams), C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter),
+                                                    C.POINTER(BarkHipVoicePrompt), C.POINTER(BarkHipAudioFormat), C.c_int]
+    lib.bark_hip_time_tempo.restype = C.c_double
+    lib.bark_hip_time_tempo.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_time_join.restype = C.c_double
     lib.bark_hip_time_join.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
@@ -750,6 +774,84 @@ class BarkContext:
             raise RuntimeError("bark_hip_time_join_activity failed")
         return us
 
+    # ---- speaking rate (rule C16t): time-scale modification on the device; speed is a factor (1.25: a quarter faster), sent as lround(1000 speed) ----
+    def tempo(self, pcm, speed: float) -> np.ndarray:
+        """One 24 kHz recording at another speaking rate, same pitch (bark_hip_tempo): n samples -> ceil(1000 n / p), p = speed_permille(speed)."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        p = speed_permille(speed)
+        cap = self._lib.bark_hip_tempo_out_len(len(x), p)
+        if cap < 0:
+            raise ValueError("bark_hip_tempo: 1 .. 1 310 720 samples and a speed of 0.5 .. 2.0")
+        out = np.zeros(cap, np.float32)
+        n = self._lib.bark_hip_tempo(self._h, x.ctypes.data, len(x), p, out.ctypes.data, out.size)
+        if n < 0:
+            raise ValueError("bark_hip_tempo refused the recording (a sample that is not finite or not below 65520 in magnitude)")
+        return out[:n]
+
+    def tempo_many(self, pcm_list, speeds, rate: int = 24000, fmt="f32") -> list:
+        """Up to 64 recordings, a speed each, in one tempo launch, then `rate` / `fmt` (bark_hip_tempo_many): one array per recording in the format's dtype."""
+        xs = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in pcm_list]
+        sp = np.asarray([speed_permille(v) for v in speeds], np.int32)
+        if len(sp) != len(xs):
+            raise ValueError("one speed per recording")
+        to = audio_format(rate, fmt)
+        dt = np.dtype(SAMPLE_DTYPES[to.sample_format])
+        lens = [self._lib.bark_hip_resample_out_len(max(self._lib.bark_hip_tempo_out_len(len(x), int(p)), 0), 24000, int(rate)) for x, p in zip(xs, sp)]
+        cap = sum(max(v, 0) for v in lens) * dt.itemsize
+        out = np.zeros(max(cap, 1), np.uint8)
+        ptrs = (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
+        ns = np.asarray([len(x) for x in xs], np.int32)
+        n_out = np.zeros(max(len(xs), 1), np.int32)
+        got = self._lib.bark_hip_tempo_many(self._h, ptrs, ns.ctypes.data, len(xs), sp.ctypes.data, C.byref(to), out.ctypes.data, cap, n_out.ctypes.data)
+        if got < 0:
+            raise ValueError("bark_hip_tempo_many refused the call (segment count or length, a speed, a sample out of range, the rate or the format)")
+        res, off = [], 0
+        for k in n_out[:len(xs)]:
+            res.append(out[off:off + int(k) * dt.itemsize].view(dt).copy()); off += int(k) * dt.itemsize
+        return res
+
+    def tempo_positions(self, pcm, speed: float) -> np.ndarray:
+        """The positions the search chose, one per frame of 360 outputs (bark_hip_tempo_positions)."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        p = speed_permille(speed)
+        cap = self._lib.bark_hip_tempo_out_len(len(x), p)
+        if cap < 0:
+            raise ValueError("bark_hip_tempo_positions: 1 .. 1 310 720 samples and a speed of 0.5 .. 2.0")
+        pos = np.zeros((cap + 359) // 360, np.int32)
+        k = self._lib.bark_hip_tempo_positions(self._h, x.ctypes.data, len(x), p, pos.ctypes.data, pos.size)
+        if k < 0:
+            raise ValueError("bark_hip_tempo_positions refused the recording")
+        return pos[:k]
+
+    def audio_at(self, speed: float, rate: int = 24000, fmt="f32") -> np.ndarray:
+        """The last generate_audio result at `speed`, then at `rate` in `fmt` (bark_hip_get_audio_at)."""
+        to, p = audio_format(rate, fmt), speed_permille(speed)
+        return self._audio_as(lambda o, cap: self._lib.bark_hip_get_audio_at(self._h, C.byref(to), p, o, cap), to)
+
+    def batch_audio_at(self, i: int, speed: float, rate: int = 24000, fmt="f32") -> np.ndarray:
+        """Utterance i of the last job at `speed`, then at `rate` in `fmt` (bark_hip_batch_audio_at)."""
+        to, p = audio_format(rate, fmt), speed_permille(speed)
+        return self._audio_as(lambda o, cap: self._lib.bark_hip_batch_audio_at(self._h, int(i), C.byref(to), p, o, cap), to)
+
+    def long_audio_at(self, speed: float, rate: int = 24000, fmt="f32") -> np.ndarray:
+        """The join of the last generate_long's chunks, each at `speed`, at `rate` in `fmt` (bark_hip_long_audio_at)."""
+        to, p = audio_format(rate, fmt), speed_permille(speed)
+        n = self._lib.bark_hip_long_audio_at(self._h, C.byref(to), p, None, 0)
+        if n == -1:
+            raise RuntimeError("no long result held, or an unsupported speed / rate / format")
+        buf = np.zeros(max(-n - 2, 1), np.uint8)
+        if n < -1:
+            n = self._lib.bark_hip_long_audio_at(self._h, C.byref(to), p, buf.ctypes.data, buf.size)
+            if n < 0:
+                raise RuntimeError("bark_hip_long_audio_at failed")
+        return buf[:n].view(SAMPLE_DTYPES[to.sample_format]).copy()
+
+    def time_tempo(self, count: int, n_each: int, speed: float, iters: int = 20) -> float:
+        us = self._lib.bark_hip_time_tempo(self._h, int(count), int(n_each), speed_permille(speed), int(iters))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_tempo failed")
+        return us
+
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""
         p = self._params if self._params is not None else default_params()
@@ -986,14 +1088,31 @@ class Batcher:
             pass
 
     def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None,
-               voice=None, audio_format: "BarkHipAudioFormat | None" = None, long=None) -> int:
+               voice=None, audio_format: "BarkHipAudioFormat | None" = None, long=None, speed: "float | None" = None) -> int:
         """audio_format: the rate / sample format of the answer (api.audio_format(rate, "s16"); bark_hip_batcher_submit_as) - fetch it with wait_bytes().
         top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
         neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does.
         voice: the request's own voice.VoicePrompt (bark_hip_batcher_submit_voiced; None: the context's).
         long: True or a BarkHipLongParams - a text of any length as one ticket (bark_hip_batcher_submit_long): its parts travel as ordinary requests, the
-        answer is their joined audio."""
-        if long is not None and long is not False:
+        answer is their joined audio.
+        speed: the speaking rate of the answer, 0.5 .. 2.0 (bark_hip_batcher_submit_at / _submit_long_at, rule C16t) - fetch it with wait_bytes()."""
+        if speed is not None:
+            fmt = audio_format if audio_format is not None else BarkHipAudioFormat(24000, 0)
+            flt = None
+            if top_k is not None or top_p is not None:
+                flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
+            if params is None:
+                params = self._ctx[0].request_params(seed=int(seed))
+            st, keep = _voice_struct(voice) if voice is not None else (None, None)
+            common = (C.byref(params), None if flt is None else C.byref(flt), None if st is None else C.byref(st), C.byref(fmt), speed_permille(speed))
+            if long is not None and long is not False:
+                lp = long if isinstance(long, BarkHipLongParams) else BarkHipLongParams(0, 0, join_params())
+                t = self._lib.bark_hip_batcher_submit_long_at(self._b, text.encode("utf-8"), C.byref(lp), *common)
+            else:
+                t = self._lib.bark_hip_batcher_submit_at(self._b, text.encode("utf-8"), *common)
+            if t > 0:
+                self._formats[t] = int(fmt.sample_format)
+        elif long is not None and long is not False:
             lp = long if isinstance(long, BarkHipLongParams) else BarkHipLongParams(0, 0, join_params())
             flt = None
             if top_k is not None or top_p is not None:

@@ -463,15 +463,25 @@ bool join_call_valid(const int * n, int count, const bark_hip_join_params & p, c
     return true;
 }
 // the joined audio of the context's long result in `to`, made once per format (the probe for the size and the call that fetches join once)
-void ensure_long_join(struct bark_context * bctx, const bark_hip_audio_format & to) {
+// speed != 1000 (rule C16t): the join runs over the time-scaled chunks - one tempo launch in front of it; lr.layout stays that of the chunks as generated
+void ensure_long_join(struct bark_context * bctx, const bark_hip_audio_format & to, int speed = 1000) {
     bark_context::LongResult & lr = bctx->long_result;
-    if (lr.joined_fmt.sample_rate == to.sample_rate && lr.joined_fmt.sample_format == to.sample_format) return;
+    if (lr.joined_fmt.sample_rate == to.sample_rate && lr.joined_fmt.sample_format == to.sample_format && lr.joined_speed == speed) return;
     std::vector<const float *> pcm;
     std::vector<int> n;
     for (const bark_context::BatchResult & r : lr.chunks) { pcm.push_back(r.audio.data()); n.push_back((int) r.audio.size()); }
     lr.joined_fmt = bark_hip_audio_format{0, 0};
-    lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, lr.layout);
+    if (speed == 1000) lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, lr.layout);
+    else {
+        const std::vector<int32_t> sp(n.size(), speed);
+        std::vector<int32_t> n24, layout;
+        const std::vector<uint8_t> scaled = engine_tempo_many(bctx, pcm.data(), n.data(), (int) n.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24);
+        size_t off = 0;
+        for (size_t i = 0; i < n.size(); i++) { pcm[i] = reinterpret_cast<const float *>(scaled.data()) + off; n[i] = n24[i]; off += (size_t) n24[i]; }
+        lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, layout);
+    }
     lr.joined_fmt = to;
+    lr.joined_speed = speed;
 }
 }  // namespace
 
@@ -571,6 +581,115 @@ double bark_hip_time_join(struct bark_context * bctx, int count, int n_each, int
 double bark_hip_time_join_activity(struct bark_context * bctx, int count, int n_each, int iters) {
     if (!bctx) return -1.0;
     return guarded("bark_hip_time_join_activity", -1.0, [&] { return engine_time_join(bctx, count, n_each, 24000, BARK_HIP_SAMPLE_F32, iters, true); });
+}
+
+// ---- speaking rate (rule C16t) ----------------------------------------------------------------------------------------------------------------------------
+namespace {
+bool speed_valid(int p) { return p >= kTempoMinSpeed && p <= kTempoMaxSpeed; }
+// the bytes the segments give at their speeds in `to`, or -1: what the tempo calls refuse before any work (the samples' values apart)
+long long tempo_bytes(const int * n, const int32_t * speed, int count, const bark_hip_audio_format & to) {
+    if (!n || !speed || count < 1 || count > kResampleMaxSegments || !sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    long long total = 0;
+    for (int i = 0; i < count; i++) {
+        const long long n24 = tempo_out_len(n[i], speed[i]);
+        if (n24 < 0) return -1;
+        total += resample_out_len(n24, 24000, to.sample_rate) * sample_format_bytes(to.sample_format);
+    }
+    return total;
+}
+// audio_as at a speaking rate: 24 kHz f32 samples held by the context -> C16t -> `fmt`
+int audio_at(struct bark_context * bctx, const char * what, const std::vector<float> & pcm, const struct bark_hip_audio_format * fmt, int speed, void * out, int capacity_bytes) {
+    if (!speed_valid(speed)) return -1;
+    if (speed == 1000) return audio_as(bctx, what, pcm, fmt, out, capacity_bytes);
+    if (!fmt || pcm.empty()) return -1;
+    const int n = (int) pcm.size();
+    const int32_t sp = speed;
+    const long long bytes = tempo_bytes(&n, &sp, 1, *fmt);
+    if (bytes < 0 || bytes > 0x7ffffff0LL) return -1;
+    if (!out || (long long) capacity_bytes < bytes) return -2 - (int) bytes;
+    return guarded(what, -1, [&] {
+        const float * p = pcm.data();
+        std::vector<int32_t> n_out;
+        const std::vector<uint8_t> r = engine_tempo_many(bctx, &p, &n, 1, &sp, fmt->sample_rate, fmt->sample_format, n_out);
+        memcpy(out, r.data(), r.size());
+        return (int) r.size();
+    });
+}
+}  // namespace
+
+int bark_hip_tempo_out_len(int n, int speed_permille) { return (int) tempo_out_len(n, speed_permille); }
+
+int bark_hip_tempo_window(float * out720) {
+    if (!out720) return -1;
+    memcpy(out720, tempo_window(), kTempoFrame * sizeof(float));
+    return kTempoFrame;
+}
+
+int bark_hip_tempo_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const int32_t * speed_permille, const struct bark_hip_audio_format * to,
+                        void * out_concat, int capacity_bytes, int32_t * n_out) {
+    if (!bctx || !pcm || !n || !speed_permille || !out_concat) return -1;
+    const bark_hip_audio_format f = to ? *to : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
+    const long long bytes = tempo_bytes(n, speed_permille, count, f);
+    if (bytes < 0 || bytes > (long long) capacity_bytes) return -1;                       // refused before any work
+    for (int i = 0; i < count; i++) if (!pcm[i]) return -1;
+    return guarded("bark_hip_tempo_many", -1, [&] {
+        std::vector<int32_t> no;
+        const std::vector<uint8_t> r = engine_tempo_many(bctx, pcm, n, count, speed_permille, f.sample_rate, f.sample_format, no);
+        memcpy(out_concat, r.data(), r.size());
+        if (n_out) memcpy(n_out, no.data(), no.size() * 4);
+        return (int) r.size();
+    });
+}
+
+int bark_hip_tempo(struct bark_context * bctx, const float * pcm, int n, int speed_permille, float * out, int capacity) {
+    const int32_t sp = speed_permille;
+    const long long cap_bytes = std::min<long long>(4LL * std::max(capacity, 0), 0x7ffffffcLL);
+    const int r = bark_hip_tempo_many(bctx, &pcm, &n, 1, &sp, nullptr, out, (int) cap_bytes, nullptr);
+    return r < 0 ? -1 : r / 4;
+}
+
+int bark_hip_tempo_positions(struct bark_context * bctx, const float * pcm, int n, int speed_permille, int32_t * pos, int capacity) {
+    if (!bctx || !pcm || !pos) return -1;
+    const long long n24 = tempo_out_len(n, speed_permille);
+    if (n24 < 0 || (n24 + kTempoHop - 1) / kTempoHop > (long long) capacity) return -1;
+    return guarded("bark_hip_tempo_positions", -1, [&] {
+        const int32_t sp = speed_permille;
+        std::vector<int32_t> no, positions;
+        engine_tempo_many(bctx, &pcm, &n, 1, &sp, 24000, BARK_HIP_SAMPLE_F32, no, &positions);
+        memcpy(pos, positions.data(), positions.size() * 4);
+        return (int) positions.size();
+    });
+}
+
+int bark_hip_get_audio_at(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, int speed_permille, void * out, int capacity_bytes) {
+    if (!bctx) return -1;
+    return audio_at(bctx, "bark_hip_get_audio_at", bctx->audio, fmt, speed_permille, out, capacity_bytes);
+}
+
+int bark_hip_batch_audio_at(struct bark_context * bctx, int i, const struct bark_hip_audio_format * fmt, int speed_permille, void * out, int capacity_bytes) {
+    if (!bctx || i < 0 || i >= (int) bctx->batch_results.size() || !bctx->batch_results[(size_t) i].ok) return -1;
+    return audio_at(bctx, "bark_hip_batch_audio_at", bctx->batch_results[(size_t) i].audio, fmt, speed_permille, out, capacity_bytes);
+}
+
+int bark_hip_long_audio_at(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, int speed_permille, void * out, int capacity_bytes) {
+    if (!speed_valid(speed_permille)) return -1;
+    if (speed_permille == 1000) return bark_hip_long_audio_as(bctx, fmt, out, capacity_bytes);
+    if (!bctx || bctx->long_result.chunks.empty()) return -1;
+    const bark_hip_audio_format to = fmt ? *fmt : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
+    if (!sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    return guarded("bark_hip_long_audio_at", -1, [&] {
+        ensure_long_join(bctx, to, speed_permille);
+        const std::vector<uint8_t> & r = bctx->long_result.joined;
+        if (r.empty()) return 0;                                                          // every chunk trimmed away
+        if (!out || (size_t) std::max(capacity_bytes, 0) < r.size()) return -2 - (int) r.size();
+        memcpy(out, r.data(), r.size());
+        return (int) r.size();
+    });
+}
+
+double bark_hip_time_tempo(struct bark_context * bctx, int count, int n_each, int speed_permille, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_tempo", -1.0, [&] { return engine_time_tempo(bctx, count, n_each, speed_permille, iters); });
 }
 
 namespace {

@@ -10,6 +10,9 @@
 // engine_resample_many per distinct format among the job's requests; requests in {24000, f32} take the path they always took.
 // A long text (bark_hip_batcher_submit_long, rules C15s / C15j) is one ticket over several ordinary requests: the worker that finishes the last of them
 // joins their audio with engine_join_many on its own context.
+// A request may carry a speaking rate (bark_hip_batcher_submit_at, rule C16t): behind the job the worker runs one engine_tempo_many over all its requests with
+// a speed other than 1000 (64 segments a call), and the conversion above then reads the time-scaled samples; a long text's parts are time-scaled in front of
+// its join.  Speed 1000 takes the path it always took.
 // Job streams (bark_hip_batcher_create_ex, n_streams 1 .. 4): further workers on clones of the context (own streams, caches and graphs, the
 // same weights) serve the same queue - a lock step is a chain of ~100 small dependent kernels, so two jobs share the chip (two streams of
 // 64-slot jobs out of phase: 37.8 prompts/s against 33.2 from one, profiles/r04_staggered_jobs.txt).  Workers that start together stay in
@@ -40,6 +43,7 @@ struct bark_hip_batcher {
         bark_hip_audio_format fmt{24000, BARK_HIP_SAMPLE_F32};      // what the answer comes in (bark_hip_batcher_submit_as); the default keeps pcm, any other fills bytes
         std::vector<uint8_t> bytes;
         int n_parts = 1;                                            // the parts a long text's ticket stands for (bark_hip_batcher_ticket_chunks)
+        int speed = 1000;                                           // speaking rate in per mille (bark_hip_batcher_submit_at); a long text's ticket carries it, its parts do not
         bool plain() const { return fmt.sample_rate == 24000 && fmt.sample_format == BARK_HIP_SAMPLE_F32; }
     };
     bark_context * ctx = nullptr;                          // worker 0's context (the caller's); request defaults are read from it
@@ -96,20 +100,45 @@ struct bark_hip_batcher {
             try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit, flts.data(), voices.data()); }
             catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: batch failed: %s\n", e.what()); failed = true; }
             ctx->voice = ctx_voice;
+            // answers at another speaking rate: ONE tempo launch over all of them (64 segments a call), 24 kHz f32 out; what follows reads `scaled` for these
+            std::vector<std::vector<float>> scaled(batch.size());
+            std::vector<char> scaled_ok(batch.size(), 0);
+            auto has_audio = [&](size_t i) { return i < ctx->batch_results.size() && ctx->batch_results[i].ok && !ctx->batch_results[i].audio.empty(); };
+            std::vector<size_t> fast;
+            for (size_t i = 0; i < batch.size() && !failed; i++) if (batch[i]->speed != 1000 && has_audio(i)) fast.push_back(i);
+            for (size_t g0 = 0; g0 < fast.size(); g0 += kResampleMaxSegments) {
+                const size_t g1 = std::min(fast.size(), g0 + (size_t) kResampleMaxSegments);
+                std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> sp, n_out;
+                for (size_t g = g0; g < g1; g++) { ptr.push_back(ctx->batch_results[fast[g]].audio.data()); len.push_back((int) ctx->batch_results[fast[g]].audio.size()); sp.push_back(batch[fast[g]]->speed); }
+                try {
+                    const std::vector<uint8_t> r = engine_tempo_many(ctx, ptr.data(), len.data(), (int) ptr.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n_out);
+                    size_t off = 0;
+                    for (size_t g = g0; g < g1; g++) {
+                        const size_t nb = (size_t) n_out[g - g0] * sizeof(float);
+                        scaled[fast[g]].resize((size_t) n_out[g - g0]); memcpy(scaled[fast[g]].data(), r.data() + off, nb); scaled_ok[fast[g]] = 1; off += nb;
+                    }
+                } catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: time scaling failed: %s\n", e.what()); }
+            }
+            // the 24 kHz f32 samples request i answers with: its result, or the time-scaled form of it (empty: none)
+            auto source = [&](size_t i) -> const std::vector<float> & {
+                static const std::vector<float> none;
+                if (!has_audio(i)) return none;
+                return batch[i]->speed == 1000 ? ctx->batch_results[i].audio : (scaled_ok[i] ? scaled[i] : none);
+            };
             // answers in another rate / format: converted here, on the thread that owns the context, one resample_many per distinct format (64 segments a call)
             std::vector<std::vector<uint8_t>> conv(batch.size());
             std::vector<char> conv_ok(batch.size(), 0);
             for (size_t i = 0; i < batch.size() && !failed; i++) {
-                if (batch[i]->plain() || conv_ok[i] || !(i < ctx->batch_results.size() && ctx->batch_results[i].ok)) continue;
+                if (batch[i]->plain() || conv_ok[i] || source(i).empty()) continue;
                 const bark_hip_audio_format f = batch[i]->fmt;
                 std::vector<size_t> who;
                 for (size_t k = i; k < batch.size(); k++)
-                    if (!batch[k]->plain() && batch[k]->fmt.sample_rate == f.sample_rate && batch[k]->fmt.sample_format == f.sample_format && k < ctx->batch_results.size() &&
-                        ctx->batch_results[k].ok && !ctx->batch_results[k].audio.empty() && !conv_ok[k]) who.push_back(k);
+                    if (!batch[k]->plain() && batch[k]->fmt.sample_rate == f.sample_rate && batch[k]->fmt.sample_format == f.sample_format && !source(k).empty() && !conv_ok[k])
+                        who.push_back(k);
                 for (size_t g0 = 0; g0 < who.size(); g0 += kResampleMaxSegments) {
                     const size_t g1 = std::min(who.size(), g0 + (size_t) kResampleMaxSegments);
                     std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> n_out;
-                    for (size_t g = g0; g < g1; g++) { ptr.push_back(ctx->batch_results[who[g]].audio.data()); len.push_back((int) ctx->batch_results[who[g]].audio.size()); }
+                    for (size_t g = g0; g < g1; g++) { ptr.push_back(source(who[g]).data()); len.push_back((int) source(who[g]).size()); }
                     try {
                         const std::vector<uint8_t> r = engine_resample_many(ctx, ptr.data(), len.data(), (int) ptr.size(), 24000, f.sample_rate, f.sample_format, n_out);
                         size_t off = 0;
@@ -125,7 +154,7 @@ struct bark_hip_batcher {
             for (size_t i = 0; i < batch.size(); i++) {
                 Req & r = *batch[i];
                 if (!failed && i < ctx->batch_results.size() && ctx->batch_results[i].ok) {
-                    if (r.plain()) { r.pcm = ctx->batch_results[i].audio; r.ok = true; }
+                    if (r.plain()) { r.pcm = source(i); r.ok = r.speed == 1000 || scaled_ok[i]; }
                     else if (conv_ok[i]) { r.bytes = std::move(conv[i]); r.ok = true; }
                 }
                 r.done = true;
@@ -145,6 +174,14 @@ struct bark_hip_batcher {
                     std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> layout;
                     for (auto & p : lg->parts) { ptr.push_back(p->pcm.data()); len.push_back((int) p->pcm.size()); }
                     try {
+                        std::vector<uint8_t> fast_parts;            // the parts at the ticket's speaking rate (rule C16t: the join runs over the time-scaled chunks)
+                        if (w.speed != 1000) {
+                            const std::vector<int32_t> sp(ptr.size(), w.speed);
+                            std::vector<int32_t> n24;
+                            fast_parts = engine_tempo_many(ctx, ptr.data(), len.data(), (int) ptr.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24);
+                            size_t off = 0;
+                            for (size_t i = 0; i < ptr.size(); i++) { ptr[i] = reinterpret_cast<const float *>(fast_parts.data()) + off; len[i] = n24[i]; off += (size_t) n24[i]; }
+                        }
                         std::vector<uint8_t> joined = engine_join_many(ctx, ptr.data(), len.data(), (int) ptr.size(), lg->join, w.fmt.sample_rate, w.fmt.sample_format, layout);
                         if (w.plain()) { w.pcm.resize(joined.size() / sizeof(float)); if (!joined.empty()) memcpy(w.pcm.data(), joined.data(), joined.size()); }
                         else w.bytes = std::move(joined);
@@ -221,9 +258,9 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create(struct bark_context *
 }
 
 static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp, const bark_hip_sampling_filter * flt = nullptr,
-                               const VoicePtr * voice = nullptr, const bark_hip_audio_format * fmt = nullptr) {
+                               const VoicePtr * voice = nullptr, const bark_hip_audio_format * fmt = nullptr, int speed = 1000) {
     auto r = std::make_shared<bark_hip_batcher::Req>();
-    r->text = text; r->rp = rp;
+    r->text = text; r->rp = rp; r->speed = speed;
     if (fmt) r->fmt = *fmt;
     std::lock_guard<std::mutex> lk(b->mu);
     if (b->stop) return -1;
@@ -268,14 +305,19 @@ BARK_API int64_t bark_hip_batcher_submit_voiced(struct bark_hip_batcher * b, con
 BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
                                             const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
                                             const struct bark_hip_audio_format * fmt) {
-    if (!b || !text || (filter && !filter_valid(*filter))) return -1;
+    return bark_hip_batcher_submit_at(b, text, params, filter, voice, fmt, 1000);
+}
+BARK_API int64_t bark_hip_batcher_submit_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                            const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
+                                            const struct bark_hip_audio_format * fmt, int speed_permille) {
+    if (!b || !text || (filter && !filter_valid(*filter)) || speed_permille < kTempoMinSpeed || speed_permille > kTempoMaxSpeed) return -1;
     if (fmt && (!sample_format_bytes(fmt->sample_format) || !resample_pair_supported(24000, fmt->sample_rate))) return -1;
     VoicePtr v;
     if (voice) {
         try { v = engine_make_voice(b->ctx, voice); }
         catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher_submit_as: %s\n", e.what()); return -1; }
     }
-    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr, fmt);
+    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr, fmt, speed_permille);
 }
 
 // A long text as ONE ticket (rules C15s / C15j): split here, on the caller's thread (the vocabulary is immutable); the parts enter the queue as ordinary
@@ -284,7 +326,12 @@ BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const c
 BARK_API int64_t bark_hip_batcher_submit_long(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
                                               const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
                                               const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt) {
-    if (!b || !text || (filter && !filter_valid(*filter))) return -1;
+    return bark_hip_batcher_submit_long_at(b, text, long_params, params, filter, voice, fmt, 1000);
+}
+BARK_API int64_t bark_hip_batcher_submit_long_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
+                                                 const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                                 const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt, int speed_permille) {
+    if (!b || !text || (filter && !filter_valid(*filter)) || speed_permille < kTempoMinSpeed || speed_permille > kTempoMaxSpeed) return -1;
     if (fmt && (!sample_format_bytes(fmt->sample_format) || !resample_pair_supported(24000, fmt->sample_rate))) return -1;
     const bark_hip_long_params lp = long_params ? *long_params : bark_hip_long_params{0, 0, join_default_params()};
     if (lp.chain != 0 || !join_params_valid(lp.join)) return -1;
@@ -302,6 +349,7 @@ BARK_API int64_t bark_hip_batcher_submit_long(struct bark_hip_batcher * b, const
     lg->whole = std::make_shared<bark_hip_batcher::Req>();
     lg->whole->n_parts = (int) spans.size();
     if (fmt) lg->whole->fmt = *fmt;
+    lg->whole->speed = speed_permille;
     for (size_t i = 0; i < spans.size(); i++) {
         auto r = std::make_shared<bark_hip_batcher::Req>();
         r->of = lg; r->text = full.substr((size_t) spans[i].begin, (size_t) (spans[i].end - spans[i].begin)); r->rp = rp; r->rp.seed = rp.seed + (uint32_t) i;

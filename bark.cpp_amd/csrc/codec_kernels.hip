@@ -838,4 +838,214 @@ void launch_join_resample(hipStream_t s, const JoinResampleArgs & a) {
     hipLaunchKernelGGL(join_resample_kernel, dim3((unsigned) ((a.n_out + kResampleTile - 1) / kResampleTile)), dim3(256), 0, s, a);
 }
 
+// ---- speaking rate: waveform-similarity overlap-add (rule C16t) -------------------------------------------------------------------
+// Frame k's search reads the position frame k - 1 chose, so a segment is one sequential chain of frames: one persistent workgroup per segment, the
+// segments of a launch side by side.  Per frame LDS holds the template t[j] = x[pos[k - 1] + 360 + j] (360 floats) and the region x[a - 240 .. a + 240 + 720)
+// (1200 floats: the 840 the search reads and 360 more), zero outside the segment; work-item i of 512 runs the chain of candidate i (neighbouring lanes read
+// neighbouring LDS words; the template is read four values at a time as a broadcast), an fmaf chain from +0 over j ascending.  No global load sits on the
+// chain from frame to frame: the next frame's region depends on k alone and is loaded into registers before this frame's search, and the next template
+// x[pos[k] + 360 + j] lies inside this frame's region (winner + 360 + j <= 1199) and is copied from LDS (DESIGN.md section 6 has the times).  The winner is the maximum of the total order (score,
+// then scan rank: 0, -1, +1, .., -240, +240 - the first maximum of the rule's scan), which every fold below applies to pairs, so no tree shape changes it:
+// xor shuffles inside a wave, eight LDS entries across the waves.  The frame's 360 outputs are formed from the staged
+// values - fmaf(w[j], region[winner + j], w[360 + j] * template[j]): one rounded product (the file is built without contraction), one fmaf - and stored
+// side by side.  Frame 0 has no search (pos[0] = 0, its template is x[0 .. 360): pos[-1] = -360).
+// Where the recording runs past its end: frames whose position + 720 passes n read zeros there, and no frame behind supplies the other half of the
+// window, so the last few milliseconds of the output sit lower under the window than the recording does.
+// a = floor(360 k p / 1000) is formed in 64 bits (k < 7300, p <= 2000); positions stay below n + 1500 and above -241.
+// The window: the f32 roundings of 0.5 - 0.5 cos(2 pi k / 720) formed in double - a committed table, never computed at load time (as kResampleTaps).
+static const float kTempoWindow[kTempoFrame] = {
+    0.000000000e+00f, 1.903846714e-05f, 7.615242066e-05f, 1.713375095e-04f, 3.045864869e-04f, 4.758892173e-04f, 6.852326333e-04f, 9.326008148e-04f,
+    1.217974816e-03f, 1.541333157e-03f, 1.902650925e-03f, 2.301900880e-03f, 2.739052288e-03f, 3.214072203e-03f, 3.726924071e-03f, 4.277569242e-03f,
+    4.865965806e-03f, 5.492068361e-03f, 6.155829877e-03f, 6.857199129e-03f, 7.596123498e-03f, 8.372546174e-03f, 9.186408482e-03f, 1.003764756e-02f,
+    1.092620008e-02f, 1.185199618e-02f, 1.281496789e-02f, 1.381503977e-02f, 1.485213730e-02f, 1.592618041e-02f, 1.703708619e-02f, 1.818477362e-02f,
+    1.936915144e-02f, 2.059013210e-02f, 2.184762247e-02f, 2.314152382e-02f, 2.447174117e-02f, 2.583817206e-02f, 2.724071220e-02f, 2.867925353e-02f,
+    3.015368991e-02f, 3.166390583e-02f, 3.320978582e-02f, 3.479121625e-02f, 3.640807420e-02f, 3.806023300e-02f, 3.974757344e-02f, 4.146996140e-02f,
+    4.322727025e-02f, 4.501936585e-02f, 4.684610665e-02f, 4.870735854e-02f, 5.060297623e-02f, 5.253281817e-02f, 5.449673906e-02f, 5.649458244e-02f,
+    5.852620304e-02f, 6.059144437e-02f, 6.269014627e-02f, 6.482215226e-02f, 6.698729843e-02f, 6.918542087e-02f, 7.141634822e-02f, 7.367991656e-02f,
+    7.597595453e-02f, 7.830427587e-02f, 8.066471666e-02f, 8.305709064e-02f, 8.548121154e-02f, 8.793690801e-02f, 9.042397887e-02f, 9.294223785e-02f,
+    9.549150616e-02f, 9.807156771e-02f, 1.006822437e-01f, 1.033233330e-01f, 1.059946269e-01f, 1.086959243e-01f, 1.114270166e-01f, 1.141877100e-01f,
+    1.169777811e-01f, 1.197970137e-01f, 1.226452067e-01f, 1.255221367e-01f, 1.284275800e-01f, 1.313613355e-01f, 1.343231499e-01f, 1.373128146e-01f,
+    1.403301060e-01f, 1.433747709e-01f, 1.464466155e-01f, 1.495453715e-01f, 1.526708156e-01f, 1.558227092e-01f, 1.590008140e-01f, 1.622048914e-01f,
+    1.654347032e-01f, 1.686899811e-01f, 1.719704866e-01f, 1.752759814e-01f, 1.786061972e-01f, 1.819608957e-01f, 1.853398085e-01f, 1.887426823e-01f,
+    1.921692640e-01f, 1.956192851e-01f, 1.990924925e-01f, 2.025886029e-01f, 2.061073780e-01f, 2.096485198e-01f, 2.132117748e-01f, 2.167968750e-01f,
+    2.204035521e-01f, 2.240315080e-01f, 2.276804894e-01f, 2.313501984e-01f, 2.350403666e-01f, 2.387507111e-01f, 2.424809635e-01f, 2.462308258e-01f,
+    2.500000000e-01f, 2.537882328e-01f, 2.575951815e-01f, 2.614206076e-01f, 2.652642131e-01f, 2.691257000e-01f, 2.730047405e-01f, 2.769010961e-01f,
+    2.808144391e-01f, 2.847444415e-01f, 2.886908650e-01f, 2.926533818e-01f, 2.966316640e-01f, 3.006254733e-01f, 3.046344221e-01f, 3.086582720e-01f,
+    3.126966953e-01f, 3.167493939e-01f, 3.208160400e-01f, 3.248963058e-01f, 3.289899230e-01f, 3.330965638e-01f, 3.372159302e-01f, 3.413476646e-01f,
+    3.454914987e-01f, 3.496471047e-01f, 3.538141549e-01f, 3.579923213e-01f, 3.621813357e-01f, 3.663808107e-01f, 3.705904782e-01f, 3.748100102e-01f,
+    3.790390491e-01f, 3.832773268e-01f, 3.875244856e-01f, 3.917801976e-01f, 3.960441649e-01f, 4.003160298e-01f, 4.045954943e-01f, 4.088822305e-01f,
+    4.131759107e-01f, 4.174762070e-01f, 4.217827618e-01f, 4.260953069e-01f, 4.304134548e-01f, 4.347369075e-01f, 4.390653372e-01f, 4.433983862e-01f,
+    4.477357566e-01f, 4.520771205e-01f, 4.564221203e-01f, 4.607704580e-01f, 4.651217759e-01f, 4.694757164e-01f, 4.738320112e-01f, 4.781903028e-01f,
+    4.825502634e-01f, 4.869115353e-01f, 4.912737906e-01f, 4.956367314e-01f, 5.000000000e-01f, 5.043632388e-01f, 5.087261796e-01f, 5.130884647e-01f,
+    5.174497366e-01f, 5.218096972e-01f, 5.261679888e-01f, 5.305242538e-01f, 5.348782539e-01f, 5.392295718e-01f, 5.435778499e-01f, 5.479228497e-01f,
+    5.522642136e-01f, 5.566015840e-01f, 5.609346628e-01f, 5.652630925e-01f, 5.695865750e-01f, 5.739046931e-01f, 5.782172084e-01f, 5.825238228e-01f,
+    5.868240595e-01f, 5.911177397e-01f, 5.954045057e-01f, 5.996839404e-01f, 6.039558649e-01f, 6.082198024e-01f, 6.124755144e-01f, 6.167227030e-01f,
+    6.209609509e-01f, 6.251900196e-01f, 6.294095516e-01f, 6.336191893e-01f, 6.378186941e-01f, 6.420076489e-01f, 6.461858749e-01f, 6.503528953e-01f,
+    6.545084715e-01f, 6.586523056e-01f, 6.627840996e-01f, 6.669034362e-01f, 6.710100770e-01f, 6.751036644e-01f, 6.791839600e-01f, 6.832506061e-01f,
+    6.873033047e-01f, 6.913416982e-01f, 6.953655481e-01f, 6.993745565e-01f, 7.033683062e-01f, 7.073466182e-01f, 7.113091350e-01f, 7.152555585e-01f,
+    7.191855907e-01f, 7.230989337e-01f, 7.269952297e-01f, 7.308743000e-01f, 7.347357869e-01f, 7.385793924e-01f, 7.424048185e-01f, 7.462117672e-01f,
+    7.500000000e-01f, 7.537691593e-01f, 7.575190663e-01f, 7.612493038e-01f, 7.649596334e-01f, 7.686498165e-01f, 7.723194957e-01f, 7.759684920e-01f,
+    7.795964479e-01f, 7.832031250e-01f, 7.867882252e-01f, 7.903514504e-01f, 7.938926220e-01f, 7.974113822e-01f, 8.009074926e-01f, 8.043807149e-01f,
+    8.078307509e-01f, 8.112573028e-01f, 8.146601915e-01f, 8.180391192e-01f, 8.213937879e-01f, 8.247240186e-01f, 8.280295134e-01f, 8.313100338e-01f,
+    8.345652819e-01f, 8.377950788e-01f, 8.409991860e-01f, 8.441773057e-01f, 8.473291993e-01f, 8.504546285e-01f, 8.535534143e-01f, 8.566251993e-01f,
+    8.596699238e-01f, 8.626871705e-01f, 8.656768799e-01f, 8.686386943e-01f, 8.715724349e-01f, 8.744778633e-01f, 8.773548007e-01f, 8.802030087e-01f,
+    8.830222487e-01f, 8.858122826e-01f, 8.885729909e-01f, 8.913040757e-01f, 8.940053582e-01f, 8.966766596e-01f, 8.993177414e-01f, 9.019284248e-01f,
+    9.045084715e-01f, 9.070577621e-01f, 9.095759988e-01f, 9.120631218e-01f, 9.145187736e-01f, 9.169428945e-01f, 9.193353057e-01f, 9.216957092e-01f,
+    9.240240455e-01f, 9.263200760e-01f, 9.285836220e-01f, 9.308145642e-01f, 9.330127239e-01f, 9.351778626e-01f, 9.373098612e-01f, 9.394085407e-01f,
+    9.414737821e-01f, 9.435054064e-01f, 9.455032349e-01f, 9.474672079e-01f, 9.493970275e-01f, 9.512926340e-01f, 9.531539083e-01f, 9.549806118e-01f,
+    9.567727447e-01f, 9.585300088e-01f, 9.602524042e-01f, 9.619397521e-01f, 9.635919333e-01f, 9.652087688e-01f, 9.667901993e-01f, 9.683361053e-01f,
+    9.698463082e-01f, 9.713207483e-01f, 9.727593064e-01f, 9.741618037e-01f, 9.755282402e-01f, 9.768584967e-01f, 9.781523943e-01f, 9.794098735e-01f,
+    9.806308746e-01f, 9.818152189e-01f, 9.829629064e-01f, 9.840738177e-01f, 9.851478338e-01f, 9.861849546e-01f, 9.871850610e-01f, 9.881479740e-01f,
+    9.890738130e-01f, 9.899623394e-01f, 9.908136129e-01f, 9.916274548e-01f, 9.924038649e-01f, 9.931427836e-01f, 9.938441515e-01f, 9.945079088e-01f,
+    9.951340556e-01f, 9.957224131e-01f, 9.962731004e-01f, 9.967859387e-01f, 9.972609282e-01f, 9.976981282e-01f, 9.980973601e-01f, 9.984586835e-01f,
+    9.987820387e-01f, 9.990674257e-01f, 9.993147850e-01f, 9.995241165e-01f, 9.996954203e-01f, 9.998286366e-01f, 9.999238253e-01f, 9.999809861e-01f,
+    1.000000000e+00f, 9.999809861e-01f, 9.999238253e-01f, 9.998286366e-01f, 9.996954203e-01f, 9.995241165e-01f, 9.993147850e-01f, 9.990674257e-01f,
+    9.987820387e-01f, 9.984586835e-01f, 9.980973601e-01f, 9.976981282e-01f, 9.972609282e-01f, 9.967859387e-01f, 9.962731004e-01f, 9.957224131e-01f,
+    9.951340556e-01f, 9.945079088e-01f, 9.938441515e-01f, 9.931427836e-01f, 9.924038649e-01f, 9.916274548e-01f, 9.908136129e-01f, 9.899623394e-01f,
+    9.890738130e-01f, 9.881479740e-01f, 9.871850610e-01f, 9.861849546e-01f, 9.851478338e-01f, 9.840738177e-01f, 9.829629064e-01f, 9.818152189e-01f,
+    9.806308746e-01f, 9.794098735e-01f, 9.781523943e-01f, 9.768584967e-01f, 9.755282402e-01f, 9.741618037e-01f, 9.727593064e-01f, 9.713207483e-01f,
+    9.698463082e-01f, 9.683361053e-01f, 9.667901993e-01f, 9.652087688e-01f, 9.635919333e-01f, 9.619397521e-01f, 9.602524042e-01f, 9.585300088e-01f,
+    9.567727447e-01f, 9.549806118e-01f, 9.531539083e-01f, 9.512926340e-01f, 9.493970275e-01f, 9.474672079e-01f, 9.455032349e-01f, 9.435054064e-01f,
+    9.414737821e-01f, 9.394085407e-01f, 9.373098612e-01f, 9.351778626e-01f, 9.330127239e-01f, 9.308145642e-01f, 9.285836220e-01f, 9.263200760e-01f,
+    9.240240455e-01f, 9.216957092e-01f, 9.193353057e-01f, 9.169428945e-01f, 9.145187736e-01f, 9.120631218e-01f, 9.095759988e-01f, 9.070577621e-01f,
+    9.045084715e-01f, 9.019284248e-01f, 8.993177414e-01f, 8.966766596e-01f, 8.940053582e-01f, 8.913040757e-01f, 8.885729909e-01f, 8.858122826e-01f,
+    8.830222487e-01f, 8.802030087e-01f, 8.773548007e-01f, 8.744778633e-01f, 8.715724349e-01f, 8.686386943e-01f, 8.656768799e-01f, 8.626871705e-01f,
+    8.596699238e-01f, 8.566251993e-01f, 8.535534143e-01f, 8.504546285e-01f, 8.473291993e-01f, 8.441773057e-01f, 8.409991860e-01f, 8.377950788e-01f,
+    8.345652819e-01f, 8.313100338e-01f, 8.280295134e-01f, 8.247240186e-01f, 8.213937879e-01f, 8.180391192e-01f, 8.146601915e-01f, 8.112573028e-01f,
+    8.078307509e-01f, 8.043807149e-01f, 8.009074926e-01f, 7.974113822e-01f, 7.938926220e-01f, 7.903514504e-01f, 7.867882252e-01f, 7.832031250e-01f,
+    7.795964479e-01f, 7.759684920e-01f, 7.723194957e-01f, 7.686498165e-01f, 7.649596334e-01f, 7.612493038e-01f, 7.575190663e-01f, 7.537691593e-01f,
+    7.500000000e-01f, 7.462117672e-01f, 7.424048185e-01f, 7.385793924e-01f, 7.347357869e-01f, 7.308743000e-01f, 7.269952297e-01f, 7.230989337e-01f,
+    7.191855907e-01f, 7.152555585e-01f, 7.113091350e-01f, 7.073466182e-01f, 7.033683062e-01f, 6.993745565e-01f, 6.953655481e-01f, 6.913416982e-01f,
+    6.873033047e-01f, 6.832506061e-01f, 6.791839600e-01f, 6.751036644e-01f, 6.710100770e-01f, 6.669034362e-01f, 6.627840996e-01f, 6.586523056e-01f,
+    6.545084715e-01f, 6.503528953e-01f, 6.461858749e-01f, 6.420076489e-01f, 6.378186941e-01f, 6.336191893e-01f, 6.294095516e-01f, 6.251900196e-01f,
+    6.209609509e-01f, 6.167227030e-01f, 6.124755144e-01f, 6.082198024e-01f, 6.039558649e-01f, 5.996839404e-01f, 5.954045057e-01f, 5.911177397e-01f,
+    5.868240595e-01f, 5.825238228e-01f, 5.782172084e-01f, 5.739046931e-01f, 5.695865750e-01f, 5.652630925e-01f, 5.609346628e-01f, 5.566015840e-01f,
+    5.522642136e-01f, 5.479228497e-01f, 5.435778499e-01f, 5.392295718e-01f, 5.348782539e-01f, 5.305242538e-01f, 5.261679888e-01f, 5.218096972e-01f,
+    5.174497366e-01f, 5.130884647e-01f, 5.087261796e-01f, 5.043632388e-01f, 5.000000000e-01f, 4.956367314e-01f, 4.912737906e-01f, 4.869115353e-01f,
+    4.825502634e-01f, 4.781903028e-01f, 4.738320112e-01f, 4.694757164e-01f, 4.651217759e-01f, 4.607704580e-01f, 4.564221203e-01f, 4.520771205e-01f,
+    4.477357566e-01f, 4.433983862e-01f, 4.390653372e-01f, 4.347369075e-01f, 4.304134548e-01f, 4.260953069e-01f, 4.217827618e-01f, 4.174762070e-01f,
+    4.131759107e-01f, 4.088822305e-01f, 4.045954943e-01f, 4.003160298e-01f, 3.960441649e-01f, 3.917801976e-01f, 3.875244856e-01f, 3.832773268e-01f,
+    3.790390491e-01f, 3.748100102e-01f, 3.705904782e-01f, 3.663808107e-01f, 3.621813357e-01f, 3.579923213e-01f, 3.538141549e-01f, 3.496471047e-01f,
+    3.454914987e-01f, 3.413476646e-01f, 3.372159302e-01f, 3.330965638e-01f, 3.289899230e-01f, 3.248963058e-01f, 3.208160400e-01f, 3.167493939e-01f,
+    3.126966953e-01f, 3.086582720e-01f, 3.046344221e-01f, 3.006254733e-01f, 2.966316640e-01f, 2.926533818e-01f, 2.886908650e-01f, 2.847444415e-01f,
+    2.808144391e-01f, 2.769010961e-01f, 2.730047405e-01f, 2.691257000e-01f, 2.652642131e-01f, 2.614206076e-01f, 2.575951815e-01f, 2.537882328e-01f,
+    2.500000000e-01f, 2.462308258e-01f, 2.424809635e-01f, 2.387507111e-01f, 2.350403666e-01f, 2.313501984e-01f, 2.276804894e-01f, 2.240315080e-01f,
+    2.204035521e-01f, 2.167968750e-01f, 2.132117748e-01f, 2.096485198e-01f, 2.061073780e-01f, 2.025886029e-01f, 1.990924925e-01f, 1.956192851e-01f,
+    1.921692640e-01f, 1.887426823e-01f, 1.853398085e-01f, 1.819608957e-01f, 1.786061972e-01f, 1.752759814e-01f, 1.719704866e-01f, 1.686899811e-01f,
+    1.654347032e-01f, 1.622048914e-01f, 1.590008140e-01f, 1.558227092e-01f, 1.526708156e-01f, 1.495453715e-01f, 1.464466155e-01f, 1.433747709e-01f,
+    1.403301060e-01f, 1.373128146e-01f, 1.343231499e-01f, 1.313613355e-01f, 1.284275800e-01f, 1.255221367e-01f, 1.226452067e-01f, 1.197970137e-01f,
+    1.169777811e-01f, 1.141877100e-01f, 1.114270166e-01f, 1.086959243e-01f, 1.059946269e-01f, 1.033233330e-01f, 1.006822437e-01f, 9.807156771e-02f,
+    9.549150616e-02f, 9.294223785e-02f, 9.042397887e-02f, 8.793690801e-02f, 8.548121154e-02f, 8.305709064e-02f, 8.066471666e-02f, 7.830427587e-02f,
+    7.597595453e-02f, 7.367991656e-02f, 7.141634822e-02f, 6.918542087e-02f, 6.698729843e-02f, 6.482215226e-02f, 6.269014627e-02f, 6.059144437e-02f,
+    5.852620304e-02f, 5.649458244e-02f, 5.449673906e-02f, 5.253281817e-02f, 5.060297623e-02f, 4.870735854e-02f, 4.684610665e-02f, 4.501936585e-02f,
+    4.322727025e-02f, 4.146996140e-02f, 3.974757344e-02f, 3.806023300e-02f, 3.640807420e-02f, 3.479121625e-02f, 3.320978582e-02f, 3.166390583e-02f,
+    3.015368991e-02f, 2.867925353e-02f, 2.724071220e-02f, 2.583817206e-02f, 2.447174117e-02f, 2.314152382e-02f, 2.184762247e-02f, 2.059013210e-02f,
+    1.936915144e-02f, 1.818477362e-02f, 1.703708619e-02f, 1.592618041e-02f, 1.485213730e-02f, 1.381503977e-02f, 1.281496789e-02f, 1.185199618e-02f,
+    1.092620008e-02f, 1.003764756e-02f, 9.186408482e-03f, 8.372546174e-03f, 7.596123498e-03f, 6.857199129e-03f, 6.155829877e-03f, 5.492068361e-03f,
+    4.865965806e-03f, 4.277569242e-03f, 3.726924071e-03f, 3.214072203e-03f, 2.739052288e-03f, 2.301900880e-03f, 1.902650925e-03f, 1.541333157e-03f,
+    1.217974816e-03f, 9.326008148e-04f, 6.852326333e-04f, 4.758892173e-04f, 3.045864869e-04f, 1.713375095e-04f, 7.615242066e-05f, 1.903846714e-05f,
+};
+const float * tempo_window() { return kTempoWindow; }
+
+__device__ __forceinline__ int tempo_rank(int c) {                      // candidate c = delta + 240 -> its place in the scan 0, -1, +1, -2, +2, ..
+    const int d = c - kTempoRadius;
+    return d == 0 ? 0 : d < 0 ? -2 * d - 1 : 2 * d;
+}
+// b before a in the total order: the greater score, then the earlier place in the scan (scores are finite: |x| < 65520)
+__device__ __forceinline__ bool tempo_better(float sb, int rb, float sa, int ra) { return sb > sa || (sb == sa && rb < ra); }
+
+constexpr int kTempoThreads = 512, kTempoWide = kTempoCandidates + kTempoFrame - 1;      // the staged region: x[a - 240 .. a + 240 + 720), 1200 floats
+static_assert(kTempoThreads >= kTempoHop && 3 * kTempoThreads >= kTempoWide && 2 * kTempoThreads < kTempoWide, "one template value and up to three region values per work-item");
+__global__ __launch_bounds__(kTempoThreads) void tempo_kernel(const TempoArgs a) {
+    __shared__ float win[kTempoFrame];
+    __shared__ float4 tmpl4[kTempoHop / 4];
+    __shared__ float reg[kTempoWide];
+    __shared__ float red_s[kTempoThreads / 64];
+    __shared__ int red_r[kTempoThreads / 64];
+    constexpr int S = kResampleMaxSegments + 1, HS = kTempoHop, D = kTempoRadius, T = kTempoThreads;
+    const int t = (int) threadIdx.x, s = (int) blockIdx.x;
+    const int n = a.seg[s], n_out = a.seg[2 * S + s], p = a.seg[4 * S + s];
+    const float * x = a.x + a.seg[S + s];
+    float * y = a.y + a.seg[3 * S + s];
+    int * pos = a.pos + a.seg[5 * S + s];
+    const int K = (n_out + HS - 1) / HS;
+    if (p == 1000) {                                                     // the identity by definition: the samples themselves, the nominal positions
+        for (int i = t; i < n; i += T) y[i] = x[i];
+        for (int k = t; k < K; k += T) pos[k] = k * HS;
+        return;
+    }
+    auto sample = [&](int g) { return (g >= 0 && g < n) ? x[g] : 0.0f; };
+    for (int i = t; i < kTempoFrame; i += T) win[i] = a.win[i];
+    float * tmpl = reinterpret_cast<float *>(tmpl4);
+    const int c0 = t < kTempoCandidates ? t : kTempoCandidates - 1;       // work-items 481 .. 511 run the last candidate once more: the same score and rank
+    const int r0 = tempo_rank(c0);
+    // frame 0: pos[-1] = -360, so its template is x[0 .. 360); its region lies around a = 0
+    if (t < HS) tmpl[t] = sample(t);
+    for (int i = t; i < kTempoWide; i += T) reg[i] = sample(i - D);
+    int nom = 0;
+    for (int k = 0; k < K; k++) {
+        // the next frame's region, known before this frame's search ends: loaded now, stored behind the frame (the loads fly while the chains run)
+        const bool more = k + 1 < K;
+        const int nom1 = (int) ((long long) (k + 1) * HS * p / 1000);
+        float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+        if (more) {
+            f0 = sample(nom1 - D + t); f1 = sample(nom1 - D + t + T);
+            if (t + 2 * T < kTempoWide) f2 = sample(nom1 - D + t + 2 * T);
+        }
+        __syncthreads();
+        if (k > 0) {
+            const float * q0 = reg + c0;
+            float bs = 0.0f;
+            for (int q = 0; q < HS / 4; q++) {
+                const float4 tv = tmpl4[q];
+                bs = fmaf(tv.x, q0[4 * q], bs);
+                bs = fmaf(tv.y, q0[4 * q + 1], bs);
+                bs = fmaf(tv.z, q0[4 * q + 2], bs);
+                bs = fmaf(tv.w, q0[4 * q + 3], bs);
+            }
+            int br = r0;
+            for (int off = 32; off > 0; off >>= 1) {
+                const float os = __shfl_xor(bs, off, 64);
+                const int orr = __shfl_xor(br, off, 64);
+                if (tempo_better(os, orr, bs, br)) { bs = os; br = orr; }
+            }
+            if ((t & 63) == 0) { red_s[t >> 6] = bs; red_r[t >> 6] = br; }
+        }
+        __syncthreads();
+        int cb = D;                                                      // frame 0: delta = 0
+        if (k > 0) {
+            float bs = red_s[0]; int br = red_r[0];
+            for (int w = 1; w < T / 64; w++) if (tempo_better(red_s[w], red_r[w], bs, br)) { bs = red_s[w]; br = red_r[w]; }
+            cb = D + (br == 0 ? 0 : (br & 1) ? -((br + 1) >> 1) : (br >> 1));
+        }
+        float next_t = 0.0f;                                             // the next template x[pos[k] + 360 + j] lies in this frame's region
+        if (t < HS) {
+            const int m = k * HS + t;
+            if (m < n_out) y[m] = fmaf(win[t], reg[cb + t], win[HS + t] * tmpl[t]);
+            next_t = reg[cb + HS + t];
+        }
+        if (t == 0) pos[k] = nom + cb - D;
+        __syncthreads();                                                 // every read of this frame's template and region is done
+        if (more) {
+            if (t < HS) tmpl[t] = next_t;
+            reg[t] = f0; reg[t + T] = f1;
+            if (t + 2 * T < kTempoWide) reg[t + 2 * T] = f2;
+            nom = nom1;
+        }
+    }
+}
+void launch_tempo(hipStream_t s, const TempoArgs & a, const int (&h)[6][kResampleMaxSegments + 1]) {
+    bool ok = a.x && a.y && a.win && a.seg && a.pos && a.B >= 1 && a.B <= kResampleMaxSegments && h[1][0] == 0 && h[3][0] == 0 && h[5][0] == 0;
+    for (int i = 0; ok && i < a.B; i++) {
+        const int n = h[0][i], p = h[4][i];
+        ok = n >= 1 && n <= kResampleMaxSamples && p >= kTempoMinSpeed && p <= kTempoMaxSpeed;
+        if (!ok) break;
+        const int n_out = p == 1000 ? n : (int) ((1000LL * n + p - 1) / p);
+        ok = h[2][i] == n_out && h[1][i + 1] == h[1][i] + n && h[3][i + 1] == h[3][i] + n_out && h[5][i + 1] == h[5][i] + (n_out + kTempoHop - 1) / kTempoHop;
+    }
+    if (!ok) kernel_fail("bark-hip: the time-scale kernel takes 1 .. %d segments of 1 .. %d samples at 500 .. 2000 per mille and a table of prefix sums that follows rule C16t (got B %d)",
+                         kResampleMaxSegments, kResampleMaxSamples, a.B);
+    hipLaunchKernelGGL(tempo_kernel, dim3((unsigned) a.B), dim3(kTempoThreads), 0, s, a);
+}
+
 }  // namespace barkhip

@@ -243,6 +243,9 @@ struct bark_context : bark_context_memory {
     barkhip::DevBuf<float> rp_in; barkhip::DevBuf<uint8_t> rp_out; barkhip::DevBuf<int> rp_seg;
     // long-form join (C15j): the segment, activity and position tables of a call, the fade table of the last fade length used (jn_fade_F; -1: none yet)
     barkhip::DevBuf<int> jn_tab; barkhip::DevBuf<float> jn_fade; int jn_fade_F = -1;
+    // speaking rate (C16t): the segments' samples back to back, their time-scaled 24 kHz form (what the resampler then reads in place of rp_in), the segment
+    // table [6][kResampleMaxSegments + 1], the chosen positions (all grown on demand) and the window table (uploaded with the first use)
+    barkhip::DevBuf<float> tp_in, tp_out, tp_win; barkhip::DevBuf<int> tp_seg, tp_pos; bool tp_win_ready = false;
     struct CodecGraph { barkhip::GraphExec exec; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -287,6 +290,7 @@ struct bark_context : bark_context_memory {
     struct LongResult {
         std::vector<barkhip::TextSpan> spans; std::vector<BatchResult> chunks; bark_hip_join_params join{6000, 0, 0.0f, 0};
         std::vector<uint8_t> joined; std::vector<int32_t> layout; bark_hip_audio_format joined_fmt{0, 0};
+        int joined_speed = 1000;                         // the speed `joined` was made at (bark_hip_long_audio_at); layout is always that of speed 1000
     } long_result;
     // lock steps (batch_step calls) of the last bark_hip_generate_batch job: [0] semantic stage, [1] coarse stage; {0, 0}: the sequential fallback took
     // the job; -1: no job has run (bark_hip_batch_lock_steps)
@@ -384,6 +388,15 @@ std::vector<uint8_t> engine_join_many(bark_context * ctx, const float * const * 
 std::vector<int32_t> engine_join_layout(bark_context * ctx, const float * const * pcm, const int * n, int count, const bark_hip_join_params & p);
 // device time of the join launch (all a default call runs: threshold 0 needs no activity launch) or, activity: of the table's fill + the activity launch alone
 double engine_time_join(bark_context * ctx, int count, int n_each, int rate_out, int fmt, int iters, bool activity = false);
+// Speaking rate (C16t): count <= 64 segments of 24 kHz f32 (1 .. 1 310 720 finite samples each, |x| < 65520), a speed per segment in per mille (500 .. 2000;
+// 1000: the identity) -> format(C14r(C16t(x), 24000 -> rate_out)), the segments' results back to back: one tempo launch (none if every speed is 1000), then
+// what engine_resample_many runs, reading the time-scaled samples where they lie on the device.  n_out: samples per segment at rate_out.  positions (may
+// be null): the frames' chosen positions, K = ceil(ceil(1000 n / p) / 360) per segment back to back.  Throws on a refusal.  tempo_out_len: ceil(1000 n / p),
+// or -1 (n outside 1 .. 1 310 720, p outside 500 .. 2000).
+long long tempo_out_len(long long n, int speed_permille);
+std::vector<uint8_t> engine_tempo_many(bark_context * ctx, const float * const * pcm, const int * n, int count, const int32_t * speed_permille, int rate_out, int fmt,
+                                       std::vector<int32_t> & n_out, std::vector<int32_t> * positions = nullptr);
+double engine_time_tempo(bark_context * ctx, int count, int n_each, int speed_permille, int iters);
 // Long-form text (C15s + C15j): split, run the chunks (chain 0: ONE lock-step job, chunk i with seed rp.seed + i; chain 1: one job per chunk, chunk
 // i + 1 with the voice made of chunk i's three streams, the previous voice where that one is refused), keep the results in ctx->long_result.  Returns
 // the chunk count; throws if a chunk fails.  A text without a word runs as one chunk.

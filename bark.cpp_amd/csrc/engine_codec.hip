@@ -608,6 +608,21 @@ int fill_segment_table(int (&seg)[5][kResampleMaxSegments + 1], const int * n, i
     }
     return seg[4][count];
 }
+// the device half of a conversion: `count` segments lie back to back at dx (total_in samples) -> out (sized by the caller) in fmt; t == nullptr: no filter
+void convert_staged(bark_context * c, const float * dx, const int (&seg)[5][kResampleMaxSegments + 1], int n_tiles, int count, size_t total_in,
+                    const ResampleTable * t, int rate_in, int rate_out, int fmt, std::vector<uint8_t> & out) {
+    hipStream_t s = c->stream;
+    if (!t) launch_sample_format(s, dx, c->rp_out.p, total_in, fmt);
+    else {
+        HIP_OK(hipMemcpyAsync(c->rp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+        ResamplePairArgs a;
+        a.x = dx; a.y = c->rp_out.p; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg.p;
+        a.B = count; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
+        launch_resample_pair(s, a, n_tiles);
+    }
+    HIP_OK(hipMemcpyAsync(out.data(), c->rp_out.p, out.size(), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));                             // seg is a stack object of the caller
+}
 }  // namespace
 
 std::vector<uint8_t> engine_resample_many(bark_context * c, const float * const * pcm, const int * n, int count, int rate_in, int rate_out, int fmt,
@@ -635,16 +650,7 @@ std::vector<uint8_t> engine_resample_many(bark_context * c, const float * const 
     ensure_resample_buffers(c, total_in, out.size());
     hipStream_t s = c->stream;
     for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->rp_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
-    if (!t) launch_sample_format(s, c->rp_in.p, c->rp_out.p, total_in, fmt);
-    else {
-        HIP_OK(hipMemcpyAsync(c->rp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
-        ResamplePairArgs a;
-        a.x = c->rp_in.p; a.y = c->rp_out.p; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg.p;
-        a.B = count; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
-        launch_resample_pair(s, a, n_tiles);
-    }
-    HIP_OK(hipMemcpyAsync(out.data(), c->rp_out.p, out.size(), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));                             // seg is a stack object
+    convert_staged(c, c->rp_in.p, seg, n_tiles, count, total_in, t, rate_in, rate_out, fmt, out);
     return out;
 }
 
@@ -834,6 +840,99 @@ double engine_time_join(bark_context * c, int count, int n_each, int rate_out, i
     iters = std::max(1, iters);
     for (int i = 0; i < 2; i++) one();
     return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) one(); }) / iters;
+}
+
+// ---- speaking rate (rule C16t) ---------------------------------------------------------------------------------------------------------------------------
+long long tempo_out_len(long long n, int p) {
+    if (n < 1 || n > kResampleMaxSamples || p < kTempoMinSpeed || p > kTempoMaxSpeed) return -1;
+    return (1000 * n + p - 1) / p;
+}
+namespace {
+// the segment table of launch_tempo; returns the total frame count
+int fill_tempo_table(int (&seg)[6][kResampleMaxSegments + 1], const int * n, const int32_t * speed, int count) {
+    memset(seg, 0, sizeof(seg));
+    for (int i = 0; i < count; i++) {
+        const int n_out = (int) tempo_out_len(n[i], speed[i]);
+        seg[0][i] = n[i]; seg[2][i] = n_out; seg[4][i] = speed[i];
+        seg[1][i + 1] = seg[1][i] + n[i]; seg[3][i + 1] = seg[3][i] + n_out; seg[5][i + 1] = seg[5][i] + (n_out + kTempoHop - 1) / kTempoHop;
+    }
+    return seg[5][count];
+}
+TempoArgs tempo_args(bark_context * c, const int (&seg)[6][kResampleMaxSegments + 1], int count) {
+    c->tp_in.reserve(c, (size_t) seg[1][count]);
+    c->tp_out.reserve(c, (size_t) seg[3][count]);
+    c->tp_pos.reserve(c, (size_t) seg[5][count]);
+    c->tp_seg.reserve(c, 6 * (kResampleMaxSegments + 1));
+    if (!c->tp_win_ready) {
+        c->tp_win.reserve(c, (size_t) kTempoFrame);
+        HIP_OK(hipMemcpyAsync(c->tp_win.p, tempo_window(), kTempoFrame * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        c->tp_win_ready = true;
+    }
+    TempoArgs a;
+    a.x = c->tp_in.p; a.y = c->tp_out.p; a.win = c->tp_win.p; a.seg = c->tp_seg.p; a.pos = c->tp_pos.p; a.B = count;
+    return a;
+}
+}  // namespace
+
+std::vector<uint8_t> engine_tempo_many(bark_context * c, const float * const * pcm, const int * n, int count, const int32_t * speed, int rate_out, int fmt,
+                                       std::vector<int32_t> & n_out, std::vector<int32_t> * positions) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!pcm || !n || !speed || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("tempo: 1 .. 64 segments in one call");
+    if (!resample_pair_supported(24000, rate_out)) throw std::runtime_error("tempo: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
+    const int bytes_per = sample_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("tempo: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    bool all_identity = true;
+    for (int i = 0; i < count; i++) {
+        if (!pcm[i] || tempo_out_len(n[i], speed[i]) < 0) throw std::runtime_error("tempo: a segment needs 1 .. 1 310 720 samples and a speed of 500 .. 2000 per mille");
+        for (int k = 0; k < n[i]; k++) if (!(std::fabs(pcm[i][k]) < 65520.0f)) throw std::runtime_error("tempo: a sample that is not finite or not below 65520 in magnitude");
+        all_identity = all_identity && speed[i] == 1000;
+    }
+    if (all_identity && !positions) return engine_resample_many(c, pcm, n, count, 24000, rate_out, fmt, n_out);      // nothing of the rule runs
+    int seg[6][kResampleMaxSegments + 1];
+    const int n_frames = fill_tempo_table(seg, n, speed, count);
+    const TempoArgs a = tempo_args(c, seg, count);
+    hipStream_t s = c->stream;
+    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->tp_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->tp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+    launch_tempo(s, a, seg);
+    if (positions) {
+        positions->assign((size_t) n_frames, 0);
+        HIP_OK(hipMemcpyAsync(positions->data(), c->tp_pos.p, (size_t) n_frames * 4, hipMemcpyDeviceToHost, s));
+    }
+    const ResampleTable * t = resample_pair_table(24000, rate_out);
+    std::vector<uint8_t> out;
+    if (!t && fmt == BARK_HIP_SAMPLE_F32) {                      // 24 kHz f32: the time-scaled samples themselves
+        n_out.assign(seg[2], seg[2] + count);
+        out.resize((size_t) seg[3][count] * 4);
+        HIP_OK(hipMemcpyAsync(out.data(), c->tp_out.p, out.size(), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));                         // seg is a stack object
+        return out;
+    }
+    int rseg[5][kResampleMaxSegments + 1];
+    const int n_tiles = fill_segment_table(rseg, seg[2], count, 24000, rate_out, n_out);
+    out.resize((size_t) rseg[3][count] * (size_t) bytes_per);
+    c->rp_out.reserve(c, out.size());
+    c->rp_seg.reserve(c, 5 * (kResampleMaxSegments + 1));
+    convert_staged(c, c->tp_out.p, rseg, n_tiles, count, (size_t) seg[3][count], t, 24000, rate_out, fmt, out);
+    return out;
+}
+
+double engine_time_tempo(bark_context * c, int count, int n_each, int speed, int iters) {
+    HIP_OK(hipSetDevice(c->device));
+    if (count < 1 || count > kResampleMaxSegments || tempo_out_len(n_each, speed) < 0 || speed == 1000)
+        throw std::runtime_error("time_tempo: 1 .. 64 segments of 1 .. 1 310 720 samples at 500 .. 2000 per mille, not 1000 (which runs no search)");
+    const std::vector<int> n((size_t) count, n_each);
+    const std::vector<int32_t> sp((size_t) count, speed);
+    int seg[6][kResampleMaxSegments + 1];
+    fill_tempo_table(seg, n.data(), sp.data(), count);
+    const TempoArgs a = tempo_args(c, seg, count);
+    HIP_OK(hipMemsetAsync(c->tp_in.p, 0, (size_t) count * (size_t) n_each * 4, c->stream));       // the time does not depend on the values: every chain runs in full
+    HIP_OK(hipMemcpyAsync(c->tp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    iters = std::max(1, iters);
+    for (int i = 0; i < 2; i++) launch_tempo(c->stream, a, seg);
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) launch_tempo(c->stream, a, seg); }) / iters;
 }
 
 // ---- long-form text: split (C15s), run the chunks as lock-step jobs, keep the results for the join (C15j) -------------------------------------------------

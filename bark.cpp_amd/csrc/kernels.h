@@ -381,4 +381,17 @@ struct JoinResampleArgs {
 };
 void launch_join_resample(hipStream_t s, const JoinResampleArgs & a);
 
+// ---- speaking rate: waveform-similarity overlap-add over up to 64 segments in one launch (rule C16t; codec_kernels.hip) ----------
+// Segment s of n samples at speed p (per mille, 500 .. 2000) gives n_out = ceil(1000 n / p) samples in K = ceil(n_out / 360) frames: frame k >= 1 searches
+// the 481 positions a - 240 .. a + 240 around a = floor(360 k p / 1000) for the best continuation of frame k - 1 (one fmaf chain of 360 terms per position,
+// the first maximum in the order 0, -1, +1, .., -240, +240 wins) and y[360 k + j] = fmaf(w[j], x[pos[k] + j], w[360 + j] * x[pos[k - 1] + 360 + j]); samples
+// outside the segment are +0; p == 1000 copies the segment.  seg is a device table [6][kResampleMaxSegments + 1] of ints - input lengths, input offsets
+// (prefix sums), output lengths, output offsets (prefix sums), speeds and the offsets of the segments' K positions in pos (prefix sums); launch_tempo
+// checks the host copy it is given against the rule before anything runs.  win: the 720 window values on the device (tempo_window(): the committed table).
+constexpr int kTempoFrame = 720, kTempoHop = 360, kTempoRadius = 240, kTempoCandidates = 2 * kTempoRadius + 1, kTempoRegion = kTempoCandidates + kTempoHop - 1;
+constexpr int kTempoMinSpeed = 500, kTempoMaxSpeed = 2000;
+const float * tempo_window();
+struct TempoArgs { const float * x = nullptr; float * y = nullptr; const float * win = nullptr; const int * seg = nullptr; int * pos = nullptr; int B = 1; };
+void launch_tempo(hipStream_t s, const TempoArgs & a, const int (&host_seg)[6][kResampleMaxSegments + 1]);
+
 }  // namespace barkhip

@@ -27,9 +27,12 @@
 // (chunk i with seed + i) and their audio is joined on the device with "gap_ms" of silence between them (default --gap-ms, 250) at the request's
 // "sample_rate" / "format"; the answer carries X-Bark-Chunks: n.  More than 64 chunks or a malformed field is a 400.  Without "long" and --long a request
 // is served as before.
+// Speaking rate (rule C16t of bark_mi355x.h): "speed": a number in 0.5 .. 2.0 in a /bark request (default: --speed, 1.0), sent to the collector as
+// lround(1000 speed) per mille - the answer is time-scaled on the device before "sample_rate" / "format" apply (with "long": every chunk, before the join),
+// and the WAV header follows the actual sample count.  Anything else is a 400.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw] [--long] [--max-tokens n] [--gap-ms n]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw] [--long] [--max-tokens n] [--gap-ms n] [--speed x]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -41,6 +44,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -71,6 +75,7 @@ struct Options {
     bool voice_audio_resample = false;             // --voice-audio-resample: --voice-audio recordings at any supported rate
     int sample_rate = 24000; std::string format = "f32";      // --sample-rate / --format: what a request without "sample_rate" / "format" is answered in
     bool long_form = false; int max_tokens = 0, gap_ms = 250;  // --long / --max-tokens / --gap-ms: what a request without "long" / "max_tokens" / "gap_ms" gets
+    double speed = 1.0;                            // --speed: the speaking rate of a request without "speed"
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -97,6 +102,10 @@ bark_hip_audio_format format_defaults{24000, BARK_HIP_SAMPLE_F32};
 struct LongDefaults { bool on = false; int32_t max_tokens = 0, gap_ms = 250; } long_defaults;
 constexpr int kMaxGapMs = 60000;
 bool long_valid(int32_t max_tokens, int32_t gap_ms) { return max_tokens >= 0 && max_tokens <= 255 && gap_ms >= 0 && gap_ms <= kMaxGapMs; }
+// speaking rate (rule C16t): a factor in 0.5 .. 2.0, sent as lround(1000 speed); anything else (a NaN too) is refused
+double speed_default = 1.0;
+bool speed_valid(double speed) { return speed >= 0.5 && speed <= 2.0; }
+int speed_permille(double speed) { return (int) lround(1000.0 * speed); }
 bool format_valid(const bark_hip_audio_format & f) { return f.sample_format >= 0 && f.sample_format <= 2 && bark_hip_resample_out_len(1, 24000, f.sample_rate) >= 1; }
 // the voices by name: read by every /bark request, written by POST /voices.  An entry is never changed, only replaced: a request that has looked its
 // voice up keeps it alive through its shared_ptr while a later POST puts another one under the same name
@@ -248,7 +257,17 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 ::close(fd);
                 return;
             }
-            const bool plain = af.sample_rate == 24000 && af.sample_format == BARK_HIP_SAMPLE_F32;
+            // "speed": a number in 0.5 .. 2.0 - the speaking rate; checked here as well, for the same reason
+            double speed = speed_default;
+            const int hs = barkhttp::json_number(body, "speed", speed);
+            if (hs < 0 || !speed_valid(speed)) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"speed\" must be a number in 0.5 .. 2.0");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
+            const int permille = speed_permille(speed);
+            const bool plain = af.sample_rate == 24000 && af.sample_format == BARK_HIP_SAMPLE_F32 && permille == 1000;
             // "voice": absent - no voice; otherwise a string that names a voice of the table (held until the answer is sent)
             std::shared_ptr<const VoiceFile> vf;
             int has_voice = 0;
@@ -272,7 +291,8 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 if (vf) vp = bark_hip_voice_prompt{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
                                                    vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
                 const bark_hip_long_params lp{max_tokens, 0, {gap_ms * 24, 0, 0.0f, 0}};
-                ticket = bark_hip_batcher_submit_long(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af);
+                ticket = permille == 1000 ? bark_hip_batcher_submit_long(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af)
+                                          : bark_hip_batcher_submit_long_at(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af, permille);
                 if (ticket <= 0) {
                     respond(fd, 400, "Bad Request", "text/plain", "the text gives more than 64 chunks");
                 } else {
@@ -296,7 +316,8 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 bark_hip_voice_prompt vp{};
                 if (vf) vp = bark_hip_voice_prompt{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
                                                    vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
-                ticket = bark_hip_batcher_submit_as(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af);
+                ticket = permille == 1000 ? bark_hip_batcher_submit_as(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af)
+                                          : bark_hip_batcher_submit_at(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af, permille);
                 int nb = ticket > 0 ? bark_hip_batcher_wait_bytes(batcher, ticket, nullptr, 0) : -1;     // probe: -(2 + bytes)
                 if (nb <= -2) {
                     std::vector<char> bytes((size_t) (-nb - 2));
@@ -336,7 +357,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")] [--speed x (speaking rate 0.5 .. 2.0, default 1; a request's \"speed\")]\n", argv0);
 }
 
 }  // namespace
@@ -367,6 +388,7 @@ int main(int argc, char ** argv) {
         else if (a == "--long") o.long_form = true;
         else if (a == "--max-tokens") o.max_tokens = atoi(next("--max-tokens"));
         else if (a == "--gap-ms") o.gap_ms = atoi(next("--gap-ms"));
+        else if (a == "--speed") o.speed = atof(next("--speed"));
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
@@ -374,6 +396,8 @@ int main(int argc, char ** argv) {
     if (!format_valid(format_defaults)) { fprintf(stderr, "%s: --sample-rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and --format f32, s16 or mulaw\n", argv[0]); return 1; }
     long_defaults.on = o.long_form; long_defaults.max_tokens = o.max_tokens; long_defaults.gap_ms = o.gap_ms;
     if (!long_valid(o.max_tokens, o.gap_ms)) { fprintf(stderr, "%s: --max-tokens must be 0 .. 255 and --gap-ms 0 .. 60000\n", argv[0]); return 1; }
+    speed_default = o.speed;
+    if (!speed_valid(o.speed)) { fprintf(stderr, "%s: --speed must be 0.5 .. 2.0\n", argv[0]); return 1; }
     {
         std::map<std::string, VoiceFile> files;
         for (const std::string & v : o.voices) {

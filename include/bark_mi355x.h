@@ -248,6 +248,35 @@ BARK_API int bark_hip_join_many(struct bark_context * bctx, const float * const 
 BARK_API double bark_hip_time_join(struct bark_context * bctx, int count, int n_each, int rate_out, int sample_format, int iters);
 BARK_API double bark_hip_time_join_activity(struct bark_context * bctx, int count, int n_each, int iters);
 
+/* Speaking rate (rule C16t): time-scale modification of 24 kHz f32 audio on the device by waveform-similarity overlap-add - the
+ * duration changes, the pitch does not.  speed_permille p is an integer in 500 .. 2000 (2000: twice as fast); p == 1000 is the identity bit for bit and
+ * runs nothing.  n samples (1 .. 1 310 720, finite, |x| < 65520) give n_out = ceil(1000 n / p) samples in K = ceil(n_out / 360) frames of 720 samples
+ * (30 ms) hopped by 360.  Frame k >= 1 searches the 481 positions within +-240 samples (10 ms) of floor(360 k p / 1000) for the best continuation of frame
+ * k - 1: one fmaf chain of 360 terms per position, scanned 0, -1, +1, .., -240, +240, a later one wins only with a strictly greater score (silence stays
+ * nominal).  y[360 k + j] = fmaf(w[j], x[pos[k] + j], w[360 + j] * x[pos[k - 1] + 360 + j]) with the committed Hann table w and x = +0 outside the
+ * recording; the last few milliseconds may sit lower under the window.  Another rate or format is by definition format(C14r(C16t(x), 24000 -> rate)).
+ * Long form: the join (C15j) runs over the time-scaled chunks, its gap, fade, threshold and pad as given (in output samples, not scaled).
+ * bark_hip_tempo_out_len: n_out, or -1 (n or p out of range); needs no context.  bark_hip_tempo_window: the committed table; returns 720.
+ * bark_hip_tempo: returns n_out, or -1 with the context still usable (n, p or a sample out of range, capacity (in floats) too small).
+ * bark_hip_tempo_many: count <= 64 segments with a speed each in ONE tempo launch, then the resampler / format launches of bark_hip_resample_many for `to`
+ * (NULL: 24000 f32); bit-identical to `count` single calls; n_out (optional): samples per segment; returns the bytes written, or -1.
+ * bark_hip_tempo_positions: the K chosen positions pos[k] of a recording (k 360 at p == 1000); returns K, or -1. */
+BARK_API int bark_hip_tempo_out_len(int n, int speed_permille);
+BARK_API int bark_hip_tempo_window(float * out720);
+BARK_API int bark_hip_tempo(struct bark_context * bctx, const float * pcm, int n, int speed_permille, float * out, int capacity);
+BARK_API int bark_hip_tempo_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const int32_t * speed_permille,
+                                 const struct bark_hip_audio_format * to, void * out_concat, int capacity_bytes, int32_t * n_out);
+BARK_API int bark_hip_tempo_positions(struct bark_context * bctx, const float * pcm, int n, int speed_permille, int32_t * pos, int capacity);
+/* The results a context holds, at a speaking rate: the return conventions of bark_hip_get_audio_as / _batch_audio_as / _long_audio_as (-(2 + bytes) if
+ * capacity_bytes is too small, -1 also for a speed outside 500 .. 2000).  speed_permille == 1000: the bytes of the _as form, no further launch.
+ * bark_hip_long_audio_at is bark_hip_join_many over the bark_hip_tempo of every chunk. */
+BARK_API int bark_hip_get_audio_at(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, int speed_permille, void * out, int capacity_bytes);
+BARK_API int bark_hip_batch_audio_at(struct bark_context * bctx, int i, const struct bark_hip_audio_format * fmt, int speed_permille, void * out, int capacity_bytes);
+BARK_API int bark_hip_long_audio_at(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, int speed_permille, void * out, int capacity_bytes);
+/* Device time (us) of ONE tempo launch over `count` segments of n_each samples at speed_permille (not 1000), averaged over `iters` launches (hipEvents on
+ * the context's stream).  Returns < 0 on error. */
+BARK_API double bark_hip_time_tempo(struct bark_context * bctx, int count, int n_each, int speed_permille, int iters);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);
@@ -400,6 +429,16 @@ BARK_API int64_t bark_hip_batcher_submit_long(struct bark_hip_batcher * b, const
                                               const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
                                               const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt);
 BARK_API int bark_hip_batcher_ticket_chunks(struct bark_hip_batcher * b, int64_t ticket);
+/* bark_hip_batcher_submit_as / _submit_long with a speaking rate (rule C16t; -1 for a speed outside 500 .. 2000).  The worker runs ONE tempo launch per job
+ * over all its requests with a speed other than 1000, then one bark_hip_resample_many per distinct format as before; a long text's parts are time-scaled in
+ * one launch in front of its join.  speed_permille == 1000: the path of the form without a speed.  bark_hip_batcher_wait_bytes returns the result
+ * (bark_hip_batcher_wait too where the format is {24000, F32}). */
+BARK_API int64_t bark_hip_batcher_submit_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                            const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
+                                            const struct bark_hip_audio_format * fmt, int speed_permille);
+BARK_API int64_t bark_hip_batcher_submit_long_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
+                                                 const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                                 const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt, int speed_permille);
 BARK_API void bark_hip_batcher_stats(struct bark_hip_batcher * b, int * n_batches, int * n_requests, int * largest_batch);
 /* requests that joined a job that was already running (continuous admission: while the semantic stage of a job has free slots, requests
  * arriving in the meantime are taken along, up to max_batch per job) */
