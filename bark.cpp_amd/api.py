@@ -43,6 +43,12 @@ class BarkHipSamplingFilter(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
 
 
+class BarkHipSampleCall(C.Structure):
+    """struct bark_hip_sample_call (bark_mi355x.h): per-call settings of the sampler hook bark_hip_sample_rows_state."""
+    _fields_ = [("mode", C.c_int32), ("eos_token", C.c_int32), ("token_base", C.c_int32), ("prescaled", C.c_int32), ("n_past_add", C.c_int32),
+                ("per_row", C.c_int32)]
+
+
 class BarkHipVoicePrompt(C.Structure):
     """struct bark_hip_voice_prompt (bark_mi355x.h): speaker history of the three stages (rule C10v), time-major arrays."""
     _fields_ = [("semantic", C.c_void_p), ("n_semantic", C.c_int32), ("coarse_Tx2", C.c_void_p), ("n_coarse_frames", C.c_int32),
@@ -133,6 +139,7 @@ EXPORTS = [
     "bark_hip_time_decode_step", "bark_hip_time_gemv", "bark_hip_time_slots", "bark_hip_time_fine_pass", "bark_hip_time_fine_passes", "bark_hip_describe", "bark_hip_set_fine_order", "bark_hip_load_model_on_device", "bark_hip_batcher_create_multi",
     "bark_hip_batcher_create", "bark_hip_batcher_create_ex", "bark_hip_batcher_submit", "bark_hip_batcher_submit_ex", "bark_hip_batcher_wait", "bark_hip_batcher_stats", "bark_hip_batcher_admitted", "bark_hip_batcher_free",
     "bark_hip_set_sampling_filter", "bark_hip_generate_batch_filtered", "bark_hip_batcher_submit_filtered", "bark_hip_sample_rows_filtered", "bark_hip_time_sample_filter",
+    "bark_hip_sample_rows_state",
     "bark_hip_set_voice_prompt", "bark_hip_generate_batch_voiced", "bark_hip_batcher_submit_voiced", "bark_hip_pick_rows",
     "bark_hip_has_codec_encoder", "bark_hip_codec_encode", "bark_hip_codec_encode_many", "bark_hip_codec_encode_tap", "bark_hip_rvq_encode", "bark_hip_codec_encode_latents", "bark_hip_codec_encode_device_us",
     "bark_hip_load_semantic_encoder", "bark_hip_has_semantic_encoder", "bark_hip_semantic_encode", "bark_hip_semantic_encode_tap", "bark_hip_semantic_head", "bark_hip_semantic_encode_device_us",
@@ -294,6 +301,7 @@ def load_library() -> C.CDLL:
     lib.bark_hip_set_sampling_filter.argtypes = [vp, C.c_int32, C.c_float]
     lib.bark_hip_generate_batch_filtered.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter)]
     lib.bark_hip_sample_rows_filtered.argtypes = [vp, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]
+    lib.bark_hip_sample_rows_state.argtypes = [vp, fp, C.c_int, C.c_int, fp, ip, fp, fp, fp, C.POINTER(BarkHipSampleCall), ip, ip, fp]
     lib.bark_hip_time_sample_filter.restype = C.c_double
     lib.bark_hip_time_sample_filter.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_float, C.c_int, C.c_int]
     lib.bark_hip_set_voice_prompt.argtypes = [vp, C.POINTER(BarkHipVoicePrompt)]
@@ -1003,6 +1011,30 @@ class BarkContext:
                                                    ids.ctypes.data, eos.ctypes.data) != 0:
             raise RuntimeError("bark_hip_sample_rows_filtered failed")
         return ids, eos
+
+    STATE_FIELDS = ("n_past", "cur_token", "step", "eos_step", "near_tie", "n_out", "last_eos_p", "fault")      # struct StepState, eight 32-bit words
+
+    def sample_rows_state(self, logits, temp, top_k, top_p, u, min_eos_p, state, mode=0, eos_token=-1, token_base=0, prescaled=0, n_past_add=1,
+                          per_row=False):
+        """Kernel-level hook (bark_hip_sample_rows_state): rows of logits [n_rows, n] through the decode loop's filter + sampler launches with
+        per-row temp (0: greedy) / top_k / top_p / u / min_eos_p and the rows' stage states `state` int32 [n_rows, 8] (STATE_FIELDS; last_eos_p
+        as float bits) before the launch; per_row: one single-slot launch per row, as bark_generate_audio makes them.
+        Returns (ids int32 [n_rows], eos_p float32 [n_rows], state after the launch int32 [n_rows, 8])."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        nr, n = lg.shape
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(temp, np.float32), (nr,)))
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, np.int32), (nr,)))
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(top_p, np.float32), (nr,)))
+        uu = np.ascontiguousarray(np.broadcast_to(np.asarray(u, np.float64), (nr,)))
+        me = np.ascontiguousarray(np.broadcast_to(np.asarray(min_eos_p, np.float32), (nr,)))
+        st = np.array(np.broadcast_to(np.asarray(state, np.int32), (nr, 8)), np.int32, order="C")
+        call = BarkHipSampleCall(int(mode), int(eos_token), int(token_base), int(prescaled), int(n_past_add), 1 if per_row else 0)
+        ids = np.zeros(nr, np.int32)
+        eos = np.zeros(nr, np.float32)
+        if self._lib.bark_hip_sample_rows_state(self._h, lg.ctypes.data, nr, n, t.ctypes.data, k.ctypes.data, p.ctypes.data, uu.ctypes.data,
+                                                me.ctypes.data, C.byref(call), st.ctypes.data, ids.ctypes.data, eos.ctypes.data) != 0:
+            raise RuntimeError("bark_hip_sample_rows_state failed")
+        return ids, eos, st
 
     def time_sample_filter(self, n: int, n_slots: int, top_k: int, top_p: float, peaked: bool, iters: int) -> float:
         us = self._lib.bark_hip_time_sample_filter(self._h, n, n_slots, int(top_k), float(top_p), 1 if peaked else 0, iters)

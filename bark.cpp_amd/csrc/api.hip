@@ -808,6 +808,13 @@ int bark_hip_sample_rows_filtered(struct bark_context * bctx, const float * logi
     if (!bctx || !logits || !temp || !top_k || !top_p || !u || !out_ids || n_rows <= 0) return -1;
     return guarded("bark_hip_sample_rows_filtered", -1, [&] { engine_sample_rows_filtered(bctx, logits, n_rows, n, temp, top_k, top_p, u, out_ids, out_eos_p); return 0; });
 }
+int bark_hip_sample_rows_state(struct bark_context * bctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k,
+                               const float * top_p, const double * u, const float * min_eos_p, const struct bark_hip_sample_call * call,
+                               int32_t * state_io, int32_t * out_ids, float * out_eos_p) {
+    if (!bctx || !logits || !temp || !top_k || !top_p || !u || !min_eos_p || !call || !state_io || !out_ids || n_rows <= 0) return -1;
+    return guarded("bark_hip_sample_rows_state", -1, [&] {
+        engine_sample_rows_state(bctx, logits, n_rows, n, temp, top_k, top_p, u, min_eos_p, *call, state_io, out_ids, out_eos_p); return 0; });
+}
 double bark_hip_time_sample_filter(struct bark_context * bctx, int n, int n_slots, int32_t top_k, float top_p, int peaked, int iters) {
     if (!bctx) return -1.0;
     return guarded("bark_hip_time_sample_filter", -1.0, [&] { return engine_time_sample_filtered(bctx, n, n_slots, top_k, top_p, peaked, iters); });

@@ -420,6 +420,11 @@ inline bool filter_on(const bark_hip_sampling_filter & f) { return f.top_k > 0 |
 // the decode loop's filter + sampler launches on n_rows caller rows of n logits (bark_hip_sample_rows_filtered): ids, eos_p = p_{n-1}
 void engine_sample_rows_filtered(bark_context * ctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k, const float * top_p,
                                  const double * u, int32_t * out_ids, float * out_eos_p);
+// the same launches with per-row stop thresholds and stage states, per-call mode / eos token / slice base / prescaled / n_past_add, and optionally
+// one single-slot launch per row (bark_hip_sample_rows_state); state_io: eight int32 per row, before the launch in, after it out
+void engine_sample_rows_state(bark_context * ctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k, const float * top_p,
+                              const double * u, const float * min_eos_p, const bark_hip_sample_call & call, int32_t * state_io, int32_t * out_ids,
+                              float * out_eos_p);
 double engine_time_sample_filtered(bark_context * ctx, int n, int n_rows, int top_k, float top_p, int peaked, int iters);
 void engine_reserve_batch(bark_context * ctx, int slots);          // fixes the lock-step capacity (otherwise the first batch call does)
 

@@ -503,6 +503,94 @@ void engine_sample_rows_filtered(bark_context * c, const float * logits, int n_r
     }
 }
 
+// kernel-level hook that reaches the whole sampler (bark_hip_sample_rows_state): as engine_sample_rows_filtered, with per-row stop thresholds and
+// initial stage states and per-call mode / eos token / slice base / prescaled / n_past_add.  A row's state indexes its own kSlots entries of the id,
+// eos_p and u arrays (step, n_out < kSlots is checked: nothing else bounds those writes).  per_row: one launch per row in the form of
+// bark_generate_audio's run_sample (nbatch 1, no per-slot arrays, the scalars temp / min_eos_p; the filter only in front of a filtered sampled row)
+void engine_sample_rows_state(bark_context * c, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k, const float * top_p,
+                              const double * u, const float * min_eos_p, const bark_hip_sample_call & call, int32_t * state_io, int32_t * out_ids,
+                              float * out_eos_p) {
+    constexpr int kSlots = 8;
+    static_assert(sizeof(StepState) == 32, "bark_hip_sample_rows_state hands the state out as eight int32");
+    if (n_rows <= 0 || n < 1 || n > 12288) throw std::runtime_error("sample_rows_state: n must be in 1..12288");
+    if (call.per_row && n_rows > 256) throw std::runtime_error("sample_rows_state: the per-row form takes at most 256 rows");
+    if ((call.mode != 0 && call.mode != 1) || (call.prescaled != 0 && call.prescaled != 1) || (call.per_row != 0 && call.per_row != 1) ||
+        call.n_past_add < 0 || call.n_past_add > 1024 || call.token_base < 0 || call.token_base > (1 << 30))
+        throw std::runtime_error("sample_rows_state: bad call settings");
+    std::vector<StepState> sts((size_t) n_rows);
+    memcpy(sts.data(), state_io, (size_t) n_rows * sizeof(StepState));
+    for (int r = 0; r < n_rows; r++) {
+        if (!(temp[r] >= 0.0f) || !filter_valid(bark_hip_sampling_filter{top_k[r], top_p[r]}) || std::isnan(min_eos_p[r]))
+            throw std::runtime_error("sample_rows_state: bad settings");
+        const StepState & s = sts[(size_t) r];
+        if (s.step < 0 || s.step >= kSlots || s.n_out < 0 || s.n_out >= kSlots || s.n_past < 0 || s.n_past > (1 << 30))
+            throw std::runtime_error("sample_rows_state: step and n_out must be in 0..7, n_past in 0..2^30");
+    }
+    HIP_OK(hipSetDevice(c->device));
+    const int chunk = std::min(n_rows, 4096);
+    struct Buf { void * p = nullptr; ~Buf() { if (p) (void) hipFree(p); } };
+    Buf b_l, b_t, b_k, b_p, b_m, b_u, b_st, b_ids, b_eos;
+    HIP_OK(hipMalloc(&b_l.p, (size_t) chunk * n * 4)); HIP_OK(hipMalloc(&b_t.p, (size_t) chunk * 4)); HIP_OK(hipMalloc(&b_k.p, (size_t) chunk * 4));
+    HIP_OK(hipMalloc(&b_p.p, (size_t) chunk * 4)); HIP_OK(hipMalloc(&b_m.p, (size_t) chunk * 4)); HIP_OK(hipMalloc(&b_u.p, (size_t) chunk * kSlots * 8));
+    HIP_OK(hipMalloc(&b_st.p, (size_t) chunk * sizeof(StepState)));
+    HIP_OK(hipMalloc(&b_ids.p, (size_t) chunk * kSlots * 4)); HIP_OK(hipMalloc(&b_eos.p, (size_t) chunk * kSlots * 4));
+    std::vector<double> us((size_t) chunk * kSlots);
+    std::vector<int32_t> ids((size_t) chunk * kSlots);
+    std::vector<float> eos((size_t) chunk * kSlots);
+    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int nb = std::min(chunk, n_rows - r0);
+        hipStream_t st = c->stream;
+        for (int r = 0; r < nb; r++) for (int k = 0; k < kSlots; k++) us[(size_t) r * kSlots + k] = u[r0 + r];
+        HIP_OK(hipMemcpyAsync(b_l.p, logits + (size_t) r0 * n, (size_t) nb * n * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_t.p, temp + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_k.p, top_k + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_p.p, top_p + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_m.p, min_eos_p + r0, (size_t) nb * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_u.p, us.data(), (size_t) nb * kSlots * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(b_st.p, sts.data() + r0, (size_t) nb * sizeof(StepState), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(b_ids.p, 0xff, (size_t) nb * kSlots * 4, st));
+        HIP_OK(hipMemsetAsync(b_eos.p, 0xff, (size_t) nb * kSlots * 4, st));
+        SampleArgs a;
+        a.force_exact = exact_sampling();
+        a.n = n; a.mode = call.mode; a.eos_token = call.eos_token; a.token_base = call.token_base; a.n_past_add = call.n_past_add;
+        a.prescaled = call.prescaled; a.ld_logits = n; a.out_stride = kSlots; a.u_stride = kSlots; a.x = nullptr;
+        if (!call.per_row) {
+            a.logits = (const float *) b_l.p; a.out_tokens = (int32_t *) b_ids.p; a.eos_trace = call.mode == 0 ? (float *) b_eos.p : nullptr;
+            a.st = (StepState *) b_st.p; a.u = (const double *) b_u.p; a.nbatch = nb;
+            a.slot_temp = (const float *) b_t.p; a.slot_min_eos_p = (const float *) b_m.p;
+            a.kinds = 0;
+            for (int r = r0; r < r0 + nb; r++) {
+                a.kinds |= temp[r] > 0.0f ? 2 : 1;
+                if (temp[r] > 0.0f && filter_on(bark_hip_sampling_filter{top_k[r], top_p[r]})) a.kinds |= 4;
+            }
+            launch_sample_filtered(st, a, (const int32_t *) b_k.p, (const float *) b_p.p);
+        } else {
+            a.nbatch = 1; a.slot_temp = nullptr; a.slot_min_eos_p = nullptr; a.kinds = 0;
+            for (int r = 0; r < nb; r++) {
+                a.logits = (const float *) b_l.p + (size_t) r * n; a.out_tokens = (int32_t *) b_ids.p + (size_t) r * kSlots;
+                a.eos_trace = call.mode == 0 ? (float *) b_eos.p + (size_t) r * kSlots : nullptr;
+                a.st = (StepState *) b_st.p + r; a.u = (const double *) b_u.p + (size_t) r * kSlots;
+                a.temp = temp[r0 + r]; a.min_eos_p = min_eos_p[r0 + r];
+                if (a.temp > 0.0f && filter_on(bark_hip_sampling_filter{top_k[r0 + r], top_p[r0 + r]}))
+                    launch_sample_filtered(st, a, (const int32_t *) b_k.p + r, (const float *) b_p.p + r);
+                else launch_sample_greedy(st, a);
+            }
+        }
+        HIP_OK(hipMemcpyAsync(ids.data(), b_ids.p, (size_t) nb * kSlots * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(eos.data(), b_eos.p, (size_t) nb * kSlots * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(state_io + (size_t) r0 * 8, b_st.p, (size_t) nb * sizeof(StepState), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        for (int r = 0; r < nb; r++) {
+            const StepState & s = sts[(size_t) (r0 + r)];                // the entries the row's INITIAL state selects
+            out_ids[r0 + r] = ids[(size_t) r * kSlots + s.n_out];
+            StepState after;
+            memcpy(&after, state_io + (size_t) (r0 + r) * 8, sizeof(after));
+            // coarse steps keep no eos trace (run_sample): the value reported is the state's
+            if (out_eos_p) out_eos_p[r0 + r] = call.mode == 0 ? eos[(size_t) r * kSlots + s.step] : after.last_eos_p;
+        }
+    }
+}
+
 namespace detail {
 // one fine forward (bark_build_fine_gpt_graph, bark.cpp:1416-1584): tokens [8][plane] hold Z windows of 1024 positions back to back;
 // logits -> rb.logits [Z * 1024][n_rows]

@@ -494,6 +494,23 @@ BARK_API int bark_hip_profile_lock_step(struct bark_context * bctx, int which, i
  * context's stream.  out_ids[r]: the pick, out_eos_p[r]: the probability of the last id (0 if the filter removed it).  Returns 0, or -1. */
 BARK_API int bark_hip_sample_rows_filtered(struct bark_context * bctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k,
                                            const float * top_p, const double * u, int32_t * out_ids, float * out_eos_p);
+/* Kernel-level hook that reaches the whole semantic / coarse sampler (tests): as bark_hip_sample_rows_filtered, with temp[r] >= 0 (0: the greedy
+ * pick), a stop threshold min_eos_p[r] per row, the row's stage state before the launch and the per-call settings below.  state_io holds eight
+ * int32 per row in the order n_past, cur_token, step, eos_step, near_tie, n_out, last_eos_p (float bits), fault: the state before the launch on
+ * entry (step and n_out in 0..7, n_past in 0..2^30), the state after it on return.  near_tie counts the samples settled by the exact path.
+ * out_ids[r]: the id the launch stored, out_eos_p[r]: the probability of the last id (mode 1: the state's last_eos_p).  Returns 0, or -1. */
+struct bark_hip_sample_call {
+    int32_t mode;          /* 0 semantic (stop rule), 1 coarse (id = pick + token_base + 1024 * (step & 1), no stop rule) */
+    int32_t eos_token;     /* mode 0: a pick of this id stops (-1: none) */
+    int32_t token_base;    /* mode 1: start of the coarse ids, 0..2^30 */
+    int32_t prescaled;     /* 1: greedy rows hold logits already divided by 0.7 (the decode step's LM head), 0: raw logits */
+    int32_t n_past_add;    /* added to the state's n_past, 0..1024 */
+    int32_t per_row;       /* 1: one launch per row in the form of bark_generate_audio (one slot, scalar temp / min_eos_p), at most 256 rows;
+                              0: the rows are the slots of lock-step launches (per-slot arrays, chunks of up to 4096 rows) */
+};
+BARK_API int bark_hip_sample_rows_state(struct bark_context * bctx, const float * logits, int n_rows, int n, const float * temp, const int32_t * top_k,
+                                        const float * top_p, const double * u, const float * min_eos_p, const struct bark_hip_sample_call * call,
+                                        int32_t * state_io, int32_t * out_ids, float * out_eos_p);
 /* Device time (us) of ONE filter launch over n_slots rows of n logits (the filter kernel alone, averaged over `iters` launches on rows that are
  * restored in between); peaked != 0: logits with a nucleus of a few hundred ids, 0: nearly flat logits.  Returns < 0 on error. */
 BARK_API double bark_hip_time_sample_filter(struct bark_context * bctx, int n, int n_slots, int32_t top_k, float top_p, int peaked, int iters);
