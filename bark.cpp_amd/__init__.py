@@ -5,6 +5,7 @@ The directory name contains a dot, so import it through `load_package()` of the 
 `bark_amd_loader.py`, or put the directory itself on sys.path and `import api`.
 """
 from . import voice  # noqa: F401
-from .api import (BarkContext, Batcher, BarkContextParams, BarkHipAudioFormat, BarkHipJoinParams, BarkHipLongParams, BarkHipStats, BarkHipVoicePrompt, audio_format,  # noqa: F401
-                  build_library, default_params, join_params, library_path, load_library, speed_permille)
+from .api import (BarkContext, Batcher, BarkContextParams, BarkHipAudioFormat, BarkHipAudioRender, BarkHipJoinParams, BarkHipLongParams, BarkHipLoudnessInfo,  # noqa: F401
+                  BarkHipLoudnessParams, BarkHipStats, BarkHipVoicePrompt, audio_format, audio_render, build_library, default_params, join_params, library_path,
+                  load_library, loudness_params, speed_permille)
 from .voice import VoicePrompt  # noqa: F401

@@ -90,6 +90,42 @@ def speed_permille(speed) -> int:
     return int(math.floor(1000.0 * float(speed) + 0.5))
 
 
+class BarkHipLoudnessParams(C.Structure):
+    """struct bark_hip_loudness_params (bark_mi355x.h): the target in hundredths of a LUFS (0: off), the peak ceiling and the gain cap (rule C17l)."""
+    _fields_ = [("target_centilufs", C.c_int32), ("peak_ceiling", C.c_float), ("max_gain", C.c_float)]
+
+
+class BarkHipLoudnessInfo(C.Structure):
+    """struct bark_hip_loudness_info (bark_mi355x.h): what the device measured of a recording and the gain it applied."""
+    _fields_ = [("mean_square", C.c_double), ("lufs", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("n_blocks", C.c_int32), ("n_abs", C.c_int32),
+                ("n_gated", C.c_int32), ("flags", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BarkHipAudioRender(C.Structure):
+    """struct bark_hip_audio_render (bark_mi355x.h): rate and format, speaking rate, levelling of a held result."""
+    _fields_ = [("fmt", BarkHipAudioFormat), ("speed_permille", C.c_int32), ("loudness", BarkHipLoudnessParams)]
+
+
+LOUDNESS_UNMEASURABLE, LOUDNESS_CAP_BOUND, LOUDNESS_CEILING_BOUND = 1, 2, 4          # flags of bark_hip_loudness_info
+LOUDNESS_PEAK_CEILING, LOUDNESS_MAX_GAIN = 1.0, 10.0                                  # the defaults, bark_batch_server's too: full scale, +20 dB
+
+
+def loudness_params(lufs=None, peak_ceiling: float = LOUDNESS_PEAK_CEILING, max_gain: float = LOUDNESS_MAX_GAIN) -> BarkHipLoudnessParams:
+    """A target in LUFS (-40 .. -5) as the C interface takes it: lround(100 lufs), as bark_batch_server converts its "loudness" field; None: off."""
+    if lufs is None:
+        return BarkHipLoudnessParams(0, 0.0, 0.0)
+    return BarkHipLoudnessParams(int(math.floor(100.0 * float(lufs) + 0.5)), float(peak_ceiling), float(max_gain))
+
+
+def audio_render(rate: int = 24000, fmt="f32", speed: float = 1.0, loudness=None, peak_ceiling: float = LOUDNESS_PEAK_CEILING,
+                 max_gain: float = LOUDNESS_MAX_GAIN) -> BarkHipAudioRender:
+    lp = loudness if isinstance(loudness, BarkHipLoudnessParams) else loudness_params(loudness, peak_ceiling, max_gain)
+    return BarkHipAudioRender(audio_format(rate, fmt), speed_permille(speed), lp)
+
+
 def _voice_struct(voice):
     """(struct, arrays that must stay alive while it is used) for a voice.VoicePrompt or any object with semantic / coarse [T][2] / fine [T][8]."""
     sem = np.ascontiguousarray(voice.semantic, dtype=np.int32).reshape(-1)
@@ -151,6 +187,8 @@ EXPORTS = [
     "bark_hip_join_many", "bark_hip_time_join", "bark_hip_batcher_submit_long", "bark_hip_batcher_ticket_chunks", "bark_hip_time_join_activity",
     "bark_hip_tempo_out_len", "bark_hip_tempo_window", "bark_hip_tempo", "bark_hip_tempo_many", "bark_hip_tempo_positions", "bark_hip_get_audio_at",
     "bark_hip_batch_audio_at", "bark_hip_long_audio_at", "bark_hip_batcher_submit_at", "bark_hip_batcher_submit_long_at", "bark_hip_time_tempo",
+    "bark_hip_loudness_constants", "bark_hip_loudness_target_ms", "bark_hip_loudness_many", "bark_hip_loudness_hops", "bark_hip_level_many", "bark_hip_get_audio_with",
+    "bark_hip_batch_audio_with", "bark_hip_long_audio_with", "bark_hip_batcher_submit_with", "bark_hip_batcher_submit_long_with", "bark_hip_time_loudness",
 ]
 
 
@@ -257,6 +295,24 @@ def load_library() -> C.CDLL:
                                                     C.POINTER(BarkHipVoicePrompt), C.POINTER(BarkHipAudioFormat), C.c_int]
     lib.bark_hip_time_tempo.restype = C.c_double
     lib.bark_hip_time_tempo.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.bark_hip_loudness_constants.argtypes = [C.POINTER(C.c_double)]
+    lib.bark_hip_loudness_target_ms.restype = C.c_double
+    lib.bark_hip_loudness_target_ms.argtypes = [C.c_int]
+    lib.bark_hip_loudness_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.POINTER(BarkHipLoudnessParams), C.POINTER(BarkHipLoudnessInfo)]
+    lib.bark_hip_loudness_hops.argtypes = [vp, fp, C.c_int, C.POINTER(C.c_double), C.c_int]
+    lib.bark_hip_level_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.POINTER(BarkHipLoudnessParams), ip, C.POINTER(BarkHipAudioFormat), vp, C.c_int, ip,
+                                        C.POINTER(BarkHipLoudnessInfo)]
+    lib.bark_hip_get_audio_with.argtypes = [vp, C.POINTER(BarkHipAudioRender), vp, C.c_int, C.POINTER(BarkHipLoudnessInfo)]
+    lib.bark_hip_batch_audio_with.argtypes = [vp, C.c_int, C.POINTER(BarkHipAudioRender), vp, C.c_int, C.POINTER(BarkHipLoudnessInfo)]
+    lib.bark_hip_long_audio_with.argtypes = [vp, C.POINTER(BarkHipAudioRender), vp, C.c_int, C.POINTER(BarkHipLoudnessInfo), C.c_int]
+    lib.bark_hip_batcher_submit_with.restype = C.c_int64
+    lib.bark_hip_batcher_submit_with.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter), C.POINTER(BarkHipVoicePrompt),
+                                                 C.POINTER(BarkHipAudioRender)]
+    lib.bark_hip_batcher_submit_long_with.restype = C.c_int64
+    lib.bark_hip_batcher_submit_long_with.argtypes = [vp, C.c_char_p, C.POINTER(BarkHipLongParams), C.POINTER(BarkHipRequestParams), C.POINTER(BarkHipSamplingFilter),
+                                                      C.POINTER(BarkHipVoicePrompt), C.POINTER(BarkHipAudioRender)]
+    lib.bark_hip_time_loudness.restype = C.c_double
+    lib.bark_hip_time_loudness.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_time_join.restype = C.c_double
     lib.bark_hip_time_join.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
@@ -860,6 +916,94 @@ class BarkContext:
             raise RuntimeError("bark_hip_time_tempo failed")
         return us
 
+    # ---- loudness (rule C17l): gated BS.1770 measure and the gain to a target on the device; a target is in LUFS (-16.0), sent as lround(100 lufs) ----
+    def loudness_many(self, pcm_list, lufs=None, peak_ceiling: float = LOUDNESS_PEAK_CEILING, max_gain: float = LOUDNESS_MAX_GAIN) -> list:
+        """Measures up to 64 recordings in two launches (bark_hip_loudness_many): one dict per recording - mean_square, lufs, peak, gain (what levelling to
+        `lufs` would apply; 1 without a target), n_blocks, n_abs, n_gated, flags."""
+        xs = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in pcm_list]
+        ptrs = (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
+        ns = np.asarray([len(x) for x in xs], np.int32)
+        par = (BarkHipLoudnessParams * max(len(xs), 1))(*[loudness_params(lufs, peak_ceiling, max_gain) for _ in xs])
+        info = (BarkHipLoudnessInfo * max(len(xs), 1))()
+        if self._lib.bark_hip_loudness_many(self._h, ptrs, ns.ctypes.data, len(xs), None if lufs is None else par, info) != len(xs) or not xs:
+            raise ValueError("bark_hip_loudness_many refused the call (segment count or length, a sample out of range, the target, the ceiling or the cap)")
+        return [info[i].as_dict() for i in range(len(xs))]
+
+    def loudness(self, pcm, lufs=None, peak_ceiling: float = LOUDNESS_PEAK_CEILING, max_gain: float = LOUDNESS_MAX_GAIN) -> dict:
+        """One recording measured (see loudness_many)."""
+        return self.loudness_many([pcm], lufs, peak_ceiling, max_gain)[0]
+
+    def loudness_hops(self, pcm) -> np.ndarray:
+        """The z table of one recording: the K-weighted sum of squares of every 100 ms hop, f64 (bark_hip_loudness_hops)."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        z = np.zeros(max(len(x) // 2400, 1), np.float64)
+        k = self._lib.bark_hip_loudness_hops(self._h, x.ctypes.data, len(x), z.ctypes.data_as(C.POINTER(C.c_double)), z.size)
+        if k < 0:
+            raise ValueError("bark_hip_loudness_hops refused the recording")
+        return z[:k]
+
+    def level_many(self, pcm_list, lufs, speeds=None, rate: int = 24000, fmt="f32", peak_ceiling: float = LOUDNESS_PEAK_CEILING, max_gain: float = LOUDNESS_MAX_GAIN,
+                   want_info: bool = False):
+        """Up to 64 recordings levelled to `lufs` (one target, or one per recording; None: that one is not levelled), then at `speeds` (None: 1.0), `rate`
+        and `fmt` in one call (bark_hip_level_many): one array per recording in the format's dtype; want_info: (arrays, dicts as loudness_many gives)."""
+        xs = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in pcm_list]
+        targets = list(lufs) if isinstance(lufs, (list, tuple, np.ndarray)) else [lufs] * len(xs)
+        sp = np.asarray([speed_permille(v) for v in (speeds if speeds is not None else [1.0] * len(xs))], np.int32)
+        if len(sp) != len(xs) or len(targets) != len(xs):
+            raise ValueError("one target and one speed per recording")
+        to = audio_format(rate, fmt)
+        dt = np.dtype(SAMPLE_DTYPES[to.sample_format])
+        lens = [self._lib.bark_hip_resample_out_len(max(self._lib.bark_hip_tempo_out_len(len(x), int(p)), 0), 24000, int(rate)) for x, p in zip(xs, sp)]
+        cap = sum(max(v, 0) for v in lens) * dt.itemsize
+        out = np.zeros(max(cap, 1), np.uint8)
+        ptrs = (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
+        ns = np.asarray([len(x) for x in xs], np.int32)
+        n_out = np.zeros(max(len(xs), 1), np.int32)
+        par = (BarkHipLoudnessParams * max(len(xs), 1))(*[loudness_params(t, peak_ceiling, max_gain) for t in targets])
+        info = (BarkHipLoudnessInfo * max(len(xs), 1))()
+        got = self._lib.bark_hip_level_many(self._h, ptrs, ns.ctypes.data, len(xs), par, sp.ctypes.data, C.byref(to), out.ctypes.data, cap, n_out.ctypes.data, info)
+        if got < 0:
+            raise ValueError("bark_hip_level_many refused the call (segment count or length, a target, ceiling, cap or speed, a sample out of range, the rate or the format)")
+        res, off = [], 0
+        for k in n_out[:len(xs)]:
+            res.append(out[off:off + int(k) * dt.itemsize].view(dt).copy()); off += int(k) * dt.itemsize
+        return (res, [info[i].as_dict() for i in range(len(xs))]) if want_info else res
+
+    def audio_with(self, rate: int = 24000, fmt="f32", speed: float = 1.0, loudness=None, want_info: bool = False, **limits):
+        """The last generate_audio result levelled to `loudness` LUFS (None: not), at `speed`, `rate` and `fmt` (bark_hip_get_audio_with)."""
+        how, info = audio_render(rate, fmt, speed, loudness, **limits), BarkHipLoudnessInfo()
+        out = self._audio_as(lambda o, cap: self._lib.bark_hip_get_audio_with(self._h, C.byref(how), o, cap, C.byref(info)), how.fmt)
+        return (out, info.as_dict()) if want_info else out
+
+    def batch_audio_with(self, i: int, rate: int = 24000, fmt="f32", speed: float = 1.0, loudness=None, want_info: bool = False, **limits):
+        """Utterance i of the last job levelled to `loudness` LUFS (None: not), at `speed`, `rate` and `fmt` (bark_hip_batch_audio_with)."""
+        how, info = audio_render(rate, fmt, speed, loudness, **limits), BarkHipLoudnessInfo()
+        out = self._audio_as(lambda o, cap: self._lib.bark_hip_batch_audio_with(self._h, int(i), C.byref(how), o, cap, C.byref(info)), how.fmt)
+        return (out, info.as_dict()) if want_info else out
+
+    def long_audio_with(self, rate: int = 24000, fmt="f32", speed: float = 1.0, loudness=None, want_info: bool = False, **limits):
+        """The join of the last generate_long's chunks, each levelled to `loudness` LUFS on its own and at `speed`, at `rate` in `fmt` (bark_hip_long_audio_with);
+        want_info: (audio, one dict per chunk)."""
+        how = audio_render(rate, fmt, speed, loudness, **limits)
+        info = (BarkHipLoudnessInfo * SPLIT_MAX_CHUNKS)()
+        n_chunks = len(self.long_chunks()) if want_info else 0
+        n = self._lib.bark_hip_long_audio_with(self._h, C.byref(how), None, 0, info, SPLIT_MAX_CHUNKS)
+        if n == -1:
+            raise RuntimeError("no long result held, or an unsupported loudness / speed / rate / format")
+        buf = np.zeros(max(-n - 2, 1), np.uint8)
+        if n < -1:
+            n = self._lib.bark_hip_long_audio_with(self._h, C.byref(how), buf.ctypes.data, buf.size, info, SPLIT_MAX_CHUNKS)
+            if n < 0:
+                raise RuntimeError("bark_hip_long_audio_with failed")
+        out = buf[:n].view(SAMPLE_DTYPES[how.fmt.sample_format]).copy()
+        return (out, [info[i].as_dict() for i in range(n_chunks)]) if want_info else out
+
+    def time_loudness(self, count: int, n_each: int, level: bool = False, iters: int = 20) -> float:
+        us = self._lib.bark_hip_time_loudness(self._h, int(count), int(n_each), int(bool(level)), int(iters))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_loudness failed")
+        return us
+
     def request_params(self, **over) -> BarkHipRequestParams:
         """The context's own values of the per-utterance parameters, with overrides (temp, fine_temp, min_eos_p, n_steps_text_encoder, seed)."""
         p = self._params if self._params is not None else default_params()
@@ -1120,15 +1264,35 @@ class Batcher:
             pass
 
     def submit(self, text: str, seed: int = 0, params: "BarkHipRequestParams | None" = None, top_k: "int | None" = None, top_p: "float | None" = None,
-               voice=None, audio_format: "BarkHipAudioFormat | None" = None, long=None, speed: "float | None" = None) -> int:
+               voice=None, audio_format: "BarkHipAudioFormat | None" = None, long=None, speed: "float | None" = None, loudness=None) -> int:
         """audio_format: the rate / sample format of the answer (api.audio_format(rate, "s16"); bark_hip_batcher_submit_as) - fetch it with wait_bytes().
         top_k / top_p: the request's own top-k / nucleus filter (bark_hip_batcher_submit_filtered; an omitted one of the two is off);
         neither given: the context's filter.  Without params the request takes the context's parameters with `seed`, as the plain submit does.
         voice: the request's own voice.VoicePrompt (bark_hip_batcher_submit_voiced; None: the context's).
         long: True or a BarkHipLongParams - a text of any length as one ticket (bark_hip_batcher_submit_long): its parts travel as ordinary requests, the
         answer is their joined audio.
-        speed: the speaking rate of the answer, 0.5 .. 2.0 (bark_hip_batcher_submit_at / _submit_long_at, rule C16t) - fetch it with wait_bytes()."""
-        if speed is not None:
+        speed: the speaking rate of the answer, 0.5 .. 2.0 (bark_hip_batcher_submit_at / _submit_long_at, rule C16t) - fetch it with wait_bytes().
+        loudness: the level of the answer in LUFS, -40 .. -5, or a BarkHipLoudnessParams (bark_hip_batcher_submit_with / _submit_long_with, rule C17l; the
+        ceiling 1.0 and the cap 10 unless the struct says otherwise) - fetch it with wait_bytes()."""
+        if loudness is not None:
+            fmt = audio_format if audio_format is not None else BarkHipAudioFormat(24000, 0)
+            lp_loud = loudness if isinstance(loudness, BarkHipLoudnessParams) else loudness_params(loudness)
+            how = BarkHipAudioRender(fmt, speed_permille(1.0 if speed is None else speed), lp_loud)
+            flt = None
+            if top_k is not None or top_p is not None:
+                flt = BarkHipSamplingFilter(0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p))
+            if params is None:
+                params = self._ctx[0].request_params(seed=int(seed))
+            st, keep = _voice_struct(voice) if voice is not None else (None, None)
+            common = (C.byref(params), None if flt is None else C.byref(flt), None if st is None else C.byref(st), C.byref(how))
+            if long is not None and long is not False:
+                lp = long if isinstance(long, BarkHipLongParams) else BarkHipLongParams(0, 0, join_params())
+                t = self._lib.bark_hip_batcher_submit_long_with(self._b, text.encode("utf-8"), C.byref(lp), *common)
+            else:
+                t = self._lib.bark_hip_batcher_submit_with(self._b, text.encode("utf-8"), *common)
+            if t > 0:
+                self._formats[t] = int(fmt.sample_format)
+        elif speed is not None:
             fmt = audio_format if audio_format is not None else BarkHipAudioFormat(24000, 0)
             flt = None
             if top_k is not None or top_p is not None:

@@ -464,24 +464,32 @@ bool join_call_valid(const int * n, int count, const bark_hip_join_params & p, c
 }
 // the joined audio of the context's long result in `to`, made once per format (the probe for the size and the call that fetches join once)
 // speed != 1000 (rule C16t): the join runs over the time-scaled chunks - one tempo launch in front of it; lr.layout stays that of the chunks as generated
-void ensure_long_join(struct bark_context * bctx, const bark_hip_audio_format & to, int speed = 1000) {
+// loudness on (rule C17l): every chunk is levelled on its own, untrimmed, in front of the tempo - engine_level_many gives both; the cache key holds the request
+void ensure_long_join(struct bark_context * bctx, const bark_hip_audio_format & to, int speed = 1000, const bark_hip_loudness_params & loud = bark_hip_loudness_params{0, 0.0f, 0.0f}) {
     bark_context::LongResult & lr = bctx->long_result;
-    if (lr.joined_fmt.sample_rate == to.sample_rate && lr.joined_fmt.sample_format == to.sample_format && lr.joined_speed == speed) return;
+    const bool same_loud = lr.joined_loudness.target_centilufs == loud.target_centilufs &&
+                           (loud.target_centilufs == 0 || (lr.joined_loudness.peak_ceiling == loud.peak_ceiling && lr.joined_loudness.max_gain == loud.max_gain));
+    if (lr.joined_fmt.sample_rate == to.sample_rate && lr.joined_fmt.sample_format == to.sample_format && lr.joined_speed == speed && same_loud) return;
     std::vector<const float *> pcm;
     std::vector<int> n;
     for (const bark_context::BatchResult & r : lr.chunks) { pcm.push_back(r.audio.data()); n.push_back((int) r.audio.size()); }
     lr.joined_fmt = bark_hip_audio_format{0, 0};
-    if (speed == 1000) lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, lr.layout);
+    lr.joined_info.clear();
+    if (speed == 1000 && loud.target_centilufs == 0) lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, lr.layout);
     else {
         const std::vector<int32_t> sp(n.size(), speed);
+        const std::vector<bark_hip_loudness_params> lp(n.size(), loud);
         std::vector<int32_t> n24, layout;
-        const std::vector<uint8_t> scaled = engine_tempo_many(bctx, pcm.data(), n.data(), (int) n.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24);
+        const std::vector<uint8_t> scaled = loud.target_centilufs == 0
+            ? engine_tempo_many(bctx, pcm.data(), n.data(), (int) n.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24)
+            : engine_level_many(bctx, pcm.data(), n.data(), (int) n.size(), lp.data(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24, &lr.joined_info);
         size_t off = 0;
         for (size_t i = 0; i < n.size(); i++) { pcm[i] = reinterpret_cast<const float *>(scaled.data()) + off; n[i] = n24[i]; off += (size_t) n24[i]; }
         lr.joined = engine_join_many(bctx, pcm.data(), n.data(), (int) n.size(), lr.join, to.sample_rate, to.sample_format, layout);
     }
     lr.joined_fmt = to;
     lr.joined_speed = speed;
+    lr.joined_loudness = loud;
 }
 }  // namespace
 
@@ -690,6 +698,136 @@ int bark_hip_long_audio_at(struct bark_context * bctx, const struct bark_hip_aud
 double bark_hip_time_tempo(struct bark_context * bctx, int count, int n_each, int speed_permille, int iters) {
     if (!bctx) return -1.0;
     return guarded("bark_hip_time_tempo", -1.0, [&] { return engine_time_tempo(bctx, count, n_each, speed_permille, iters); });
+}
+
+// ---- loudness (rule C17l) ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+const bark_hip_loudness_info kLoudnessOffInfo{0.0, 0.0, 0.0f, 1.0f, 0, 0, 0, 0};
+bool render_valid(const bark_hip_audio_render & h) { return speed_valid(h.speed_permille) && loudness_params_valid(h.loudness); }
+// audio_at with levelling: 24 kHz f32 samples held by the context -> C17l -> C16t -> `fmt`
+int audio_with(struct bark_context * bctx, const char * what, const std::vector<float> & pcm, const struct bark_hip_audio_render * how, void * out, int capacity_bytes,
+               struct bark_hip_loudness_info * info) {
+    if (!how || !render_valid(*how)) return -1;
+    if (how->loudness.target_centilufs == 0) {
+        const int r = audio_at(bctx, what, pcm, &how->fmt, how->speed_permille, out, capacity_bytes);
+        if (info && r != -1) *info = kLoudnessOffInfo;
+        return r;
+    }
+    if (pcm.empty()) return -1;
+    const int n = (int) pcm.size();
+    const int32_t sp = how->speed_permille;
+    const long long bytes = tempo_bytes(&n, &sp, 1, how->fmt);
+    if (bytes < 0 || bytes > 0x7ffffff0LL) return -1;
+    if (!out || (long long) capacity_bytes < bytes) return -2 - (int) bytes;
+    return guarded(what, -1, [&] {
+        const float * p = pcm.data();
+        std::vector<int32_t> n_out;
+        std::vector<bark_hip_loudness_info> inf;
+        const std::vector<uint8_t> r = engine_level_many(bctx, &p, &n, 1, &how->loudness, &sp, how->fmt.sample_rate, how->fmt.sample_format, n_out, &inf);
+        memcpy(out, r.data(), r.size());
+        if (info) *info = inf[0];
+        return (int) r.size();
+    });
+}
+}  // namespace
+
+int bark_hip_loudness_constants(double * out9) {
+    if (!out9) return -1;
+    memcpy(out9, loudness_constants(), 9 * sizeof(double));
+    return 9;
+}
+
+double bark_hip_loudness_target_ms(int target_centilufs) {
+    return target_centilufs >= kLoudMinTarget && target_centilufs <= kLoudMaxTarget ? loudness_target_ms(target_centilufs) : -1.0;
+}
+
+namespace {
+// what the loudness calls refuse before any work (the samples' values apart)
+bool loudness_call_valid(const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params) {
+    if (!pcm || !n || count < 1 || count > kResampleMaxSegments) return false;
+    for (int i = 0; i < count; i++) if (!pcm[i] || n[i] < 1 || n[i] > kResampleMaxSamples || (params && !loudness_params_valid(params[i]))) return false;
+    return true;
+}
+}  // namespace
+
+int bark_hip_loudness_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const struct bark_hip_loudness_params * params,
+                           struct bark_hip_loudness_info * info) {
+    if (!bctx || !info || !loudness_call_valid(pcm, n, count, params)) return -1;
+    return guarded("bark_hip_loudness_many", -1, [&] {
+        const std::vector<bark_hip_loudness_info> r = engine_loudness_many(bctx, pcm, n, count, params);
+        memcpy(info, r.data(), r.size() * sizeof(bark_hip_loudness_info));
+        return count;
+    });
+}
+
+int bark_hip_loudness_hops(struct bark_context * bctx, const float * pcm, int n, double * z, int capacity) {
+    if (!bctx || !loudness_call_valid(&pcm, &n, 1, nullptr) || n / kLoudHop > capacity || (n >= kLoudHop && !z)) return -1;
+    return guarded("bark_hip_loudness_hops", -1, [&] {
+        std::vector<double> zs;
+        engine_loudness_many(bctx, &pcm, &n, 1, nullptr, &zs);
+        if (!zs.empty()) memcpy(z, zs.data(), zs.size() * sizeof(double));
+        return (int) zs.size();
+    });
+}
+
+int bark_hip_level_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const struct bark_hip_loudness_params * params,
+                        const int32_t * speed_permille, const struct bark_hip_audio_format * to, void * out_concat, int capacity_bytes, int32_t * n_out,
+                        struct bark_hip_loudness_info * info) {
+    if (!bctx || !params || !out_concat || !loudness_call_valid(pcm, n, count, params)) return -1;
+    const bark_hip_audio_format f = to ? *to : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
+    const std::vector<int32_t> unit((size_t) count, 1000);
+    const int32_t * sp = speed_permille ? speed_permille : unit.data();
+    const long long bytes = tempo_bytes(n, sp, count, f);
+    if (bytes < 0 || bytes > (long long) capacity_bytes) return -1;                       // refused before any work
+    return guarded("bark_hip_level_many", -1, [&] {
+        std::vector<int32_t> no;
+        std::vector<bark_hip_loudness_info> inf;
+        const std::vector<uint8_t> r = engine_level_many(bctx, pcm, n, count, params, sp, f.sample_rate, f.sample_format, no, &inf);
+        memcpy(out_concat, r.data(), r.size());
+        if (n_out) memcpy(n_out, no.data(), no.size() * 4);
+        if (info) memcpy(info, inf.data(), inf.size() * sizeof(bark_hip_loudness_info));
+        return (int) r.size();
+    });
+}
+
+int bark_hip_get_audio_with(struct bark_context * bctx, const struct bark_hip_audio_render * how, void * out, int capacity_bytes, struct bark_hip_loudness_info * info) {
+    if (!bctx) return -1;
+    return audio_with(bctx, "bark_hip_get_audio_with", bctx->audio, how, out, capacity_bytes, info);
+}
+
+int bark_hip_batch_audio_with(struct bark_context * bctx, int i, const struct bark_hip_audio_render * how, void * out, int capacity_bytes, struct bark_hip_loudness_info * info) {
+    if (!bctx || i < 0 || i >= (int) bctx->batch_results.size() || !bctx->batch_results[(size_t) i].ok) return -1;
+    return audio_with(bctx, "bark_hip_batch_audio_with", bctx->batch_results[(size_t) i].audio, how, out, capacity_bytes, info);
+}
+
+int bark_hip_long_audio_with(struct bark_context * bctx, const struct bark_hip_audio_render * how, void * out, int capacity_bytes, struct bark_hip_loudness_info * info,
+                             int info_capacity) {
+    if (!how || !render_valid(*how)) return -1;
+    if (!bctx || bctx->long_result.chunks.empty()) return -1;
+    const size_t n_chunks = bctx->long_result.chunks.size();
+    if (info && (size_t) std::max(info_capacity, 0) < n_chunks) return -1;
+    if (how->loudness.target_centilufs == 0) {
+        const int r = bark_hip_long_audio_at(bctx, &how->fmt, how->speed_permille, out, capacity_bytes);
+        if (info && r != -1) for (size_t i = 0; i < n_chunks; i++) info[i] = kLoudnessOffInfo;
+        return r;
+    }
+    const bark_hip_audio_format to = how->fmt;
+    if (!sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    return guarded("bark_hip_long_audio_with", -1, [&] {
+        ensure_long_join(bctx, to, how->speed_permille, how->loudness);
+        const bark_context::LongResult & lr = bctx->long_result;
+        if (info) memcpy(info, lr.joined_info.data(), lr.joined_info.size() * sizeof(bark_hip_loudness_info));
+        const std::vector<uint8_t> & r = lr.joined;
+        if (r.empty()) return 0;                                                          // every chunk trimmed away
+        if (!out || (size_t) std::max(capacity_bytes, 0) < r.size()) return -2 - (int) r.size();
+        memcpy(out, r.data(), r.size());
+        return (int) r.size();
+    });
+}
+
+double bark_hip_time_loudness(struct bark_context * bctx, int count, int n_each, int level, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_loudness", -1.0, [&] { return engine_time_loudness(bctx, count, n_each, iters, level != 0); });
 }
 
 namespace {

@@ -13,6 +13,9 @@
 // A request may carry a speaking rate (bark_hip_batcher_submit_at, rule C16t): behind the job the worker runs one engine_tempo_many over all its requests with
 // a speed other than 1000 (64 segments a call), and the conversion above then reads the time-scaled samples; a long text's parts are time-scaled in front of
 // its join.  Speed 1000 takes the path it always took.
+// A request may ask for a loudness (bark_hip_batcher_submit_with, rule C17l): the same call behind the job becomes engine_level_many over all its requests with
+// levelling on or a speed other than 1000 - one measure launch and one level launch in front of the single tempo launch; a long text's parts are levelled, each
+// on its own, in front of tempo and join.  Levelling off takes the path it always took.
 // Job streams (bark_hip_batcher_create_ex, n_streams 1 .. 4): further workers on clones of the context (own streams, caches and graphs, the
 // same weights) serve the same queue - a lock step is a chain of ~100 small dependent kernels, so two jobs share the chip (two streams of
 // 64-slot jobs out of phase: 37.8 prompts/s against 33.2 from one, profiles/r04_staggered_jobs.txt).  Workers that start together stay in
@@ -44,6 +47,8 @@ struct bark_hip_batcher {
         std::vector<uint8_t> bytes;
         int n_parts = 1;                                            // the parts a long text's ticket stands for (bark_hip_batcher_ticket_chunks)
         int speed = 1000;                                           // speaking rate in per mille (bark_hip_batcher_submit_at); a long text's ticket carries it, its parts do not
+        bark_hip_loudness_params loud{0, 0.0f, 0.0f};               // levelling (bark_hip_batcher_submit_with; target 0: none), carried like the speed
+        bool rendered() const { return speed != 1000 || loud.target_centilufs != 0; }
         bool plain() const { return fmt.sample_rate == 24000 && fmt.sample_format == BARK_HIP_SAMPLE_F32; }
     };
     bark_context * ctx = nullptr;                          // worker 0's context (the caller's); request defaults are read from it
@@ -100,18 +105,24 @@ struct bark_hip_batcher {
             try { engine_generate_batch(ctx, texts.data(), (int) texts.size(), nullptr, rps.data(), &admit, flts.data(), voices.data()); }
             catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: batch failed: %s\n", e.what()); failed = true; }
             ctx->voice = ctx_voice;
-            // answers at another speaking rate: ONE tempo launch over all of them (64 segments a call), 24 kHz f32 out; what follows reads `scaled` for these
+            // answers at another speaking rate or level: ONE tempo launch over all of them (64 segments a call), behind one measure and one level launch if any
+            // of them levels; 24 kHz f32 out; what follows reads `scaled` for these
             std::vector<std::vector<float>> scaled(batch.size());
             std::vector<char> scaled_ok(batch.size(), 0);
             auto has_audio = [&](size_t i) { return i < ctx->batch_results.size() && ctx->batch_results[i].ok && !ctx->batch_results[i].audio.empty(); };
             std::vector<size_t> fast;
-            for (size_t i = 0; i < batch.size() && !failed; i++) if (batch[i]->speed != 1000 && has_audio(i)) fast.push_back(i);
+            for (size_t i = 0; i < batch.size() && !failed; i++) if (batch[i]->rendered() && has_audio(i)) fast.push_back(i);
             for (size_t g0 = 0; g0 < fast.size(); g0 += kResampleMaxSegments) {
                 const size_t g1 = std::min(fast.size(), g0 + (size_t) kResampleMaxSegments);
-                std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> sp, n_out;
-                for (size_t g = g0; g < g1; g++) { ptr.push_back(ctx->batch_results[fast[g]].audio.data()); len.push_back((int) ctx->batch_results[fast[g]].audio.size()); sp.push_back(batch[fast[g]]->speed); }
+                std::vector<const float *> ptr; std::vector<int> len; std::vector<int32_t> sp, n_out; std::vector<bark_hip_loudness_params> loud;
+                bool levels = false;
+                for (size_t g = g0; g < g1; g++) {
+                    ptr.push_back(ctx->batch_results[fast[g]].audio.data()); len.push_back((int) ctx->batch_results[fast[g]].audio.size()); sp.push_back(batch[fast[g]]->speed);
+                    loud.push_back(batch[fast[g]]->loud); levels = levels || loud.back().target_centilufs != 0;
+                }
                 try {
-                    const std::vector<uint8_t> r = engine_tempo_many(ctx, ptr.data(), len.data(), (int) ptr.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n_out);
+                    const std::vector<uint8_t> r = levels ? engine_level_many(ctx, ptr.data(), len.data(), (int) ptr.size(), loud.data(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n_out)
+                                                          : engine_tempo_many(ctx, ptr.data(), len.data(), (int) ptr.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n_out);
                     size_t off = 0;
                     for (size_t g = g0; g < g1; g++) {
                         const size_t nb = (size_t) n_out[g - g0] * sizeof(float);
@@ -123,7 +134,7 @@ struct bark_hip_batcher {
             auto source = [&](size_t i) -> const std::vector<float> & {
                 static const std::vector<float> none;
                 if (!has_audio(i)) return none;
-                return batch[i]->speed == 1000 ? ctx->batch_results[i].audio : (scaled_ok[i] ? scaled[i] : none);
+                return !batch[i]->rendered() ? ctx->batch_results[i].audio : (scaled_ok[i] ? scaled[i] : none);
             };
             // answers in another rate / format: converted here, on the thread that owns the context, one resample_many per distinct format (64 segments a call)
             std::vector<std::vector<uint8_t>> conv(batch.size());
@@ -154,7 +165,7 @@ struct bark_hip_batcher {
             for (size_t i = 0; i < batch.size(); i++) {
                 Req & r = *batch[i];
                 if (!failed && i < ctx->batch_results.size() && ctx->batch_results[i].ok) {
-                    if (r.plain()) { r.pcm = source(i); r.ok = r.speed == 1000 || scaled_ok[i]; }
+                    if (r.plain()) { r.pcm = source(i); r.ok = !r.rendered() || scaled_ok[i]; }
                     else if (conv_ok[i]) { r.bytes = std::move(conv[i]); r.ok = true; }
                 }
                 r.done = true;
@@ -175,10 +186,13 @@ struct bark_hip_batcher {
                     for (auto & p : lg->parts) { ptr.push_back(p->pcm.data()); len.push_back((int) p->pcm.size()); }
                     try {
                         std::vector<uint8_t> fast_parts;            // the parts at the ticket's speaking rate (rule C16t: the join runs over the time-scaled chunks)
-                        if (w.speed != 1000) {
+                        if (w.rendered()) {                        // .. and level (rule C17l: each part on its own, in front of the tempo)
                             const std::vector<int32_t> sp(ptr.size(), w.speed);
+                            const std::vector<bark_hip_loudness_params> loud(ptr.size(), w.loud);
                             std::vector<int32_t> n24;
-                            fast_parts = engine_tempo_many(ctx, ptr.data(), len.data(), (int) ptr.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24);
+                            fast_parts = w.loud.target_centilufs != 0
+                                ? engine_level_many(ctx, ptr.data(), len.data(), (int) ptr.size(), loud.data(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24)
+                                : engine_tempo_many(ctx, ptr.data(), len.data(), (int) ptr.size(), sp.data(), 24000, BARK_HIP_SAMPLE_F32, n24);
                             size_t off = 0;
                             for (size_t i = 0; i < ptr.size(); i++) { ptr[i] = reinterpret_cast<const float *>(fast_parts.data()) + off; len[i] = n24[i]; off += (size_t) n24[i]; }
                         }
@@ -258,9 +272,10 @@ BARK_API struct bark_hip_batcher * bark_hip_batcher_create(struct bark_context *
 }
 
 static int64_t batcher_enqueue(struct bark_hip_batcher * b, const char * text, const bark_hip_request_params & rp, const bark_hip_sampling_filter * flt = nullptr,
-                               const VoicePtr * voice = nullptr, const bark_hip_audio_format * fmt = nullptr, int speed = 1000) {
+                               const VoicePtr * voice = nullptr, const bark_hip_audio_format * fmt = nullptr, int speed = 1000,
+                               const bark_hip_loudness_params & loud = bark_hip_loudness_params{0, 0.0f, 0.0f}) {
     auto r = std::make_shared<bark_hip_batcher::Req>();
-    r->text = text; r->rp = rp; r->speed = speed;
+    r->text = text; r->rp = rp; r->speed = speed; r->loud = loud;
     if (fmt) r->fmt = *fmt;
     std::lock_guard<std::mutex> lk(b->mu);
     if (b->stop) return -1;
@@ -310,14 +325,20 @@ BARK_API int64_t bark_hip_batcher_submit_as(struct bark_hip_batcher * b, const c
 BARK_API int64_t bark_hip_batcher_submit_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
                                             const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
                                             const struct bark_hip_audio_format * fmt, int speed_permille) {
-    if (!b || !text || (filter && !filter_valid(*filter)) || speed_permille < kTempoMinSpeed || speed_permille > kTempoMaxSpeed) return -1;
-    if (fmt && (!sample_format_bytes(fmt->sample_format) || !resample_pair_supported(24000, fmt->sample_rate))) return -1;
+    const bark_hip_audio_render how{fmt ? *fmt : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32}, speed_permille, {0, 0.0f, 0.0f}};
+    return bark_hip_batcher_submit_with(b, text, params, filter, voice, &how);
+}
+BARK_API int64_t bark_hip_batcher_submit_with(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                              const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
+                                              const struct bark_hip_audio_render * how) {
+    if (!b || !text || !how || (filter && !filter_valid(*filter)) || how->speed_permille < kTempoMinSpeed || how->speed_permille > kTempoMaxSpeed) return -1;
+    if (!loudness_params_valid(how->loudness) || !sample_format_bytes(how->fmt.sample_format) || !resample_pair_supported(24000, how->fmt.sample_rate)) return -1;
     VoicePtr v;
     if (voice) {
         try { v = engine_make_voice(b->ctx, voice); }
         catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher_submit_as: %s\n", e.what()); return -1; }
     }
-    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr, fmt, speed_permille);
+    return batcher_enqueue(b, text, params ? *params : context_request_params(b->ctx, 0), filter, voice ? &v : nullptr, &how->fmt, how->speed_permille, how->loudness);
 }
 
 // A long text as ONE ticket (rules C15s / C15j): split here, on the caller's thread (the vocabulary is immutable); the parts enter the queue as ordinary
@@ -331,8 +352,14 @@ BARK_API int64_t bark_hip_batcher_submit_long(struct bark_hip_batcher * b, const
 BARK_API int64_t bark_hip_batcher_submit_long_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
                                                  const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
                                                  const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt, int speed_permille) {
-    if (!b || !text || (filter && !filter_valid(*filter)) || speed_permille < kTempoMinSpeed || speed_permille > kTempoMaxSpeed) return -1;
-    if (fmt && (!sample_format_bytes(fmt->sample_format) || !resample_pair_supported(24000, fmt->sample_rate))) return -1;
+    const bark_hip_audio_render how{fmt ? *fmt : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32}, speed_permille, {0, 0.0f, 0.0f}};
+    return bark_hip_batcher_submit_long_with(b, text, long_params, params, filter, voice, &how);
+}
+BARK_API int64_t bark_hip_batcher_submit_long_with(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
+                                                   const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                                   const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_render * how) {
+    if (!b || !text || !how || (filter && !filter_valid(*filter)) || how->speed_permille < kTempoMinSpeed || how->speed_permille > kTempoMaxSpeed) return -1;
+    if (!loudness_params_valid(how->loudness) || !sample_format_bytes(how->fmt.sample_format) || !resample_pair_supported(24000, how->fmt.sample_rate)) return -1;
     const bark_hip_long_params lp = long_params ? *long_params : bark_hip_long_params{0, 0, join_default_params()};
     if (lp.chain != 0 || !join_params_valid(lp.join)) return -1;
     VoicePtr v;
@@ -348,8 +375,9 @@ BARK_API int64_t bark_hip_batcher_submit_long_at(struct bark_hip_batcher * b, co
     lg->join = lp.join; lg->left = (int) spans.size();
     lg->whole = std::make_shared<bark_hip_batcher::Req>();
     lg->whole->n_parts = (int) spans.size();
-    if (fmt) lg->whole->fmt = *fmt;
-    lg->whole->speed = speed_permille;
+    lg->whole->fmt = how->fmt;
+    lg->whole->speed = how->speed_permille;
+    lg->whole->loud = how->loudness;
     for (size_t i = 0; i < spans.size(); i++) {
         auto r = std::make_shared<bark_hip_batcher::Req>();
         r->of = lg; r->text = full.substr((size_t) spans[i].begin, (size_t) (spans[i].end - spans[i].begin)); r->rp = rp; r->rp.seed = rp.seed + (uint32_t) i;

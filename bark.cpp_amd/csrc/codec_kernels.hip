@@ -1048,4 +1048,150 @@ void launch_tempo(hipStream_t s, const TempoArgs & a, const int (&h)[6][kResampl
     hipLaunchKernelGGL(tempo_kernel, dim3((unsigned) a.B), dim3(kTempoThreads), 0, s, a);
 }
 
+// ---- loudness (rule C17l) -------------------------------------------------------------------------------------------------------------------------------
+// The constants are committed as hexadecimal literals, so no libm decides a bit: the K-weighting prototypes of BS.1770 evaluated at 24 kHz in double
+// (tests/loudness_ref.py formulas(), which gives the ITU's 48 kHz table to 9e-16), the absolute gate 10^((-70 + 0.691) / 10) and 9600 times it.
+constexpr double kLoudConst[9] = {
+    0x1.7ce70764be80ap+0, -0x1.1f83a928e19b5p+1, 0x1.cf503fa464169p-1, -0x1.63e66a4312152p+0, 0x1.12dc7e507ed4ep-1,       // shelf b0, b1, b2, a1, a2
+    -0x1.faeab9b7850f0p+0, 0x1.f5e262f9b05f4p-1,                                                                             // high-pass a1, a2
+    0x1.f791ec6e1d5b7p-24, 0x1.270f808885339p-10,                                                                            // A, 9600 A
+};
+const double * loudness_constants() { return kLoudConst; }
+
+// One wave per workgroup: the chain of a lane is 7200 dependent steps, so the waves of a launch should spread over the CUs.  A lane reads 7200 floats that
+// lie 2400 floats from its neighbour's: the wave stages a tile of 16 samples per lane through LDS, 16 consecutive work-items fetching the 64 bytes of one
+// lane (rows 17 floats apart: the owner's reads are free of bank conflicts), the next tile's loads in flight while the chains of this one run.
+constexpr int kLoudLanes = 64, kLoudTile = 16, kLoudRow = kLoudTile + 1, kLoudTiles = kLoudRun / kLoudTile, kLoudPreTiles = kLoudPre / kLoudTile;
+static_assert(kLoudRun % kLoudTile == 0 && kLoudPre % kLoudTile == 0 && kLoudLanes % kLoudTile == 0, "whole tiles in the warm-up and in the hop");
+__global__ __launch_bounds__(kLoudLanes) void loudness_hops_kernel(const LoudnessArgs a) {
+    __shared__ float tile[kLoudLanes * kLoudRow];
+    __shared__ long long row_first[kLoudLanes];                          // index into a.x of a lane's step 0 (may lie in front of its segment)
+    __shared__ long long row_lo[kLoudLanes], row_hi[kLoudLanes];         // the samples a lane may read: [lo, hi) in a.x, everything else is +0
+    constexpr int S = kResampleMaxSegments + 1, R = kLoudLanes / kLoudTile;
+    const int t = (int) threadIdx.x;
+    const int lane = (int) blockIdx.x * kLoudLanes + t;
+    int s = -1, h = 0, Hn = 0;
+    if (lane < a.seg[4 * S + a.B]) {
+        s = 0;
+        while (lane >= a.seg[4 * S + s + 1]) s++;                        // at most 64 steps
+        h = lane - a.seg[4 * S + s];
+        Hn = a.seg[2 * S + s];
+    }
+    {
+        long long first = 0, lo = 0, hi = 0;                             // a lane without work reads nothing
+        if (s >= 0) {
+            const long long off = a.seg[S + s];
+            first = off + (long long) (h - 2) * kLoudHop;
+            if (h < Hn) { lo = off + (long long) (h > 2 ? h - 2 : 0) * kLoudHop; hi = off + (long long) (h + 1) * kLoudHop; }
+            else { lo = off + (long long) Hn * kLoudHop; hi = off + a.seg[s]; }      // the samples behind the last hop: their peak alone
+        }
+        row_first[t] = first; row_lo[t] = lo; row_hi[t] = hi;
+    }
+    __syncthreads();
+    const int col = t % kLoudTile, sub = t / kLoudTile;
+    auto fetch = [&](int tl, float (&f)[kLoudTile]) {
+#pragma unroll
+        for (int i = 0; i < kLoudTile; i++) {
+            const int r = i * R + sub;
+            const long long g = row_first[r] + (long long) tl * kLoudTile + col;
+            f[i] = (g >= row_lo[r] && g < row_hi[r]) ? a.x[g] : 0.0f;
+        }
+    };
+    const double b0 = kLoudConst[0], b1 = kLoudConst[1], b2 = kLoudConst[2], a1 = kLoudConst[3], a2 = kLoudConst[4], ha1 = kLoudConst[5], ha2 = kLoudConst[6];
+    double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0, z = 0.0;
+    float pk = 0.0f;
+    float f[kLoudTile];
+    fetch(0, f);
+    for (int tl = 0; tl < kLoudTiles; tl++) {
+#pragma unroll
+        for (int i = 0; i < kLoudTile; i++) tile[(i * R + sub) * kLoudRow + col] = f[i];
+        __syncthreads();
+        if (tl + 1 < kLoudTiles) fetch(tl + 1, f);
+        const bool own = tl >= kLoudPreTiles;                            // the hop's own outputs: the last 2400 steps
+#pragma unroll
+        for (int i = 0; i < kLoudTile; i++) {
+            const float xf = tile[t * kLoudRow + i];
+            const double x = (double) xf;
+            const double y = b0 * x + s1;                                // shelf
+            s1 = (b1 * x - a1 * y) + s2;
+            s2 = b2 * x - a2 * y;
+            const double y2 = y + t1;                                    // high-pass, b = 1, -2, 1
+            t1 = (-2.0 * y - ha1 * y2) + t2;
+            t2 = y - ha2 * y2;
+            if (own) { z = z + y2 * y2; pk = fmaxf(pk, fabsf(xf)); }
+        }
+        __syncthreads();                                                 // every read of the tile is done
+    }
+    if (s >= 0) {
+        if (h < Hn) a.z[a.seg[3 * S + s] + h] = z;
+        atomicMax(a.peak + s, __builtin_bit_cast(unsigned, pk));         // |x| >= +0: the order of the bits is the order of the values
+    }
+}
+
+constexpr int kLoudLevelThreads = 256;
+__global__ __launch_bounds__(kLoudLevelThreads) void loudness_level_kernel(const LoudnessArgs a) {
+    __shared__ float g_sh;
+    constexpr int S = kResampleMaxSegments + 1;
+    const int t = (int) threadIdx.x, s = (int) blockIdx.x;
+    const int n = a.seg[s], Hn = a.seg[2 * S + s];
+    if (t == 0) {
+        const double * z = a.z + a.seg[3 * S + s];
+        const double gate = kLoudConst[8];
+        const int J = Hn >= kLoudBlockHops ? Hn - (kLoudBlockHops - 1) : 0;
+        int c1 = 0, c2 = 0;
+        double sum1 = 0.0, sum2 = 0.0;
+        for (int j = 0; j < J; j++) {
+            const double Sj = ((z[j] + z[j + 1]) + z[j + 2]) + z[j + 3];
+            if (Sj > gate) { c1++; sum1 = sum1 + Sj; }
+        }
+        const double rel = 0.1 * sum1;
+        for (int j = 0; j < J; j++) {
+            const double Sj = ((z[j] + z[j + 1]) + z[j + 2]) + z[j + 3];
+            if (Sj > gate && Sj * (double) c1 > rel) { c2++; sum2 = sum2 + Sj; }
+        }
+        const float peak = __builtin_bit_cast(float, a.peak[s]);
+        const LoudnessReq rq = a.req[s];
+        LoudnessInfo inf;
+        inf.mean_square = 0.0; inf.peak = peak; inf.gain = 1.0f; inf.n_blocks = J; inf.n_abs = c1; inf.n_gated = c2; inf.flags = c2 ? 0 : kLoudUnmeasurable;
+        if (c2) {
+            const double M = sum2 / (9600.0 * (double) c2);
+            inf.mean_square = M;
+            if (rq.tms > 0.0) {
+                double g = sqrt(rq.tms / M);
+                if (rq.max_gain > 0.0f && (double) rq.max_gain < g) { g = (double) rq.max_gain; inf.flags |= kLoudCapBound; }
+                if (rq.peak_ceiling > 0.0f && peak > 0.0f) {
+                    const double lim = (double) rq.peak_ceiling / (double) peak;
+                    if (lim < g) { g = lim; inf.flags = (inf.flags & ~kLoudCapBound) | kLoudCeilingBound; }
+                }
+                inf.gain = (float) g;
+            }
+        }
+        a.info[s] = inf;
+        g_sh = inf.gain;
+    }
+    __syncthreads();
+    if (!a.y) return;
+    const float g32 = g_sh;
+    const float * x = a.x + a.seg[S + s];
+    float * y = a.y + a.seg[S + s];
+    for (int i = t; i < n; i += kLoudLevelThreads) y[i] = x[i] * g32;
+}
+
+void launch_loudness_hops(hipStream_t s, const LoudnessArgs & a, const int (&h)[5][kResampleMaxSegments + 1]) {
+    bool ok = a.x && a.seg && a.z && a.peak && a.B >= 1 && a.B <= kResampleMaxSegments && h[1][0] == 0 && h[3][0] == 0 && h[4][0] == 0;
+    for (int i = 0; ok && i < a.B; i++) {
+        const int n = h[0][i];
+        ok = n >= 1 && n <= kResampleMaxSamples && h[2][i] == n / kLoudHop && h[1][i + 1] == h[1][i] + n && h[3][i + 1] == h[3][i] + n / kLoudHop &&
+             h[4][i + 1] == h[4][i] + n / kLoudHop + 1;
+    }
+    if (!ok) kernel_fail("bark-hip: the loudness kernel takes 1 .. %d segments of 1 .. %d samples and a table of prefix sums that follows rule C17l (got B %d)",
+                         kResampleMaxSegments, kResampleMaxSamples, a.B);
+    hipLaunchKernelGGL(loudness_hops_kernel, dim3((unsigned) ((h[4][a.B] + kLoudLanes - 1) / kLoudLanes)), dim3(kLoudLanes), 0, s, a);
+}
+void launch_loudness_level(hipStream_t s, const LoudnessArgs & a) {
+    if (!a.x || !a.seg || !a.z || !a.peak || !a.req || !a.info || a.B < 1 || a.B > kResampleMaxSegments)
+        kernel_fail("bark-hip: the level kernel takes 1 .. %d segments, their z table, peaks and requests (got B %d)", kResampleMaxSegments, a.B);
+    hipLaunchKernelGGL(loudness_level_kernel, dim3((unsigned) a.B), dim3(kLoudLevelThreads), 0, s, a);
+}
+
 }  // namespace barkhip

@@ -246,6 +246,10 @@ struct bark_context : bark_context_memory {
     // speaking rate (C16t): the segments' samples back to back, their time-scaled 24 kHz form (what the resampler then reads in place of rp_in), the segment
     // table [6][kResampleMaxSegments + 1], the chosen positions (all grown on demand) and the window table (uploaded with the first use)
     barkhip::DevBuf<float> tp_in, tp_out, tp_win; barkhip::DevBuf<int> tp_seg, tp_pos; bool tp_win_ready = false;
+    // loudness (C17l): the segments' samples back to back as given (the levelled ones go where the next stage reads: tp_in or rp_in), the segment table
+    // [5][kResampleMaxSegments + 1], the z table, and one peak, request and info record per segment (the first three grown on demand)
+    barkhip::DevBuf<float> lv_in; barkhip::DevBuf<int> lv_seg; barkhip::DevBuf<double> lv_z; barkhip::DevBuf<unsigned> lv_peak;
+    barkhip::DevBuf<barkhip::LoudnessReq> lv_req; barkhip::DevBuf<barkhip::LoudnessInfo> lv_info;
     struct CodecGraph { barkhip::GraphExec exec; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -291,6 +295,8 @@ struct bark_context : bark_context_memory {
         std::vector<barkhip::TextSpan> spans; std::vector<BatchResult> chunks; bark_hip_join_params join{6000, 0, 0.0f, 0};
         std::vector<uint8_t> joined; std::vector<int32_t> layout; bark_hip_audio_format joined_fmt{0, 0};
         int joined_speed = 1000;                         // the speed `joined` was made at (bark_hip_long_audio_at); layout is always that of speed 1000
+        bark_hip_loudness_params joined_loudness{0, 0.0f, 0.0f};      // and the levelling (bark_hip_long_audio_with; target 0: none)
+        std::vector<bark_hip_loudness_info> joined_info;               // one record per chunk of that levelling
     } long_result;
     // lock steps (batch_step calls) of the last bark_hip_generate_batch job: [0] semantic stage, [1] coarse stage; {0, 0}: the sequential fallback took
     // the job; -1: no job has run (bark_hip_batch_lock_steps)
@@ -397,6 +403,20 @@ long long tempo_out_len(long long n, int speed_permille);
 std::vector<uint8_t> engine_tempo_many(bark_context * ctx, const float * const * pcm, const int * n, int count, const int32_t * speed_permille, int rate_out, int fmt,
                                        std::vector<int32_t> & n_out, std::vector<int32_t> * positions = nullptr);
 double engine_time_tempo(bark_context * ctx, int count, int n_each, int speed_permille, int iters);
+// Loudness (C17l): count <= 64 segments of 24 kHz f32 under the tempo calls' limits, a request per segment (target_centilufs 0: off - measured, gain 1).
+// loudness_params_valid: target 0 or -4000 .. -500, ceiling and cap >= 0 and finite.  loudness_target_ms: 10^((t / 100 + 0.691) / 10) in double.
+// engine_loudness_many: the two launches without the scaled copy (params may be null: every gain 1); z (may be null): the hop tables back to back.
+// engine_level_many: the two launches, the levelled samples written where the next stage reads them, then what engine_tempo_many runs behind its upload
+// (the tempo launch if a speed is not 1000, the resampler / format launches) - nothing returns to the host in between.  Every request off: the call IS
+// engine_tempo_many and info is {gain 1, all else 0}.  Both throw on a refusal.
+bool loudness_params_valid(const bark_hip_loudness_params & p);
+double loudness_target_ms(int target_centilufs);
+std::vector<bark_hip_loudness_info> engine_loudness_many(bark_context * ctx, const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params,
+                                                         std::vector<double> * z = nullptr);
+std::vector<uint8_t> engine_level_many(bark_context * ctx, const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params,
+                                       const int32_t * speed_permille, int rate_out, int fmt, std::vector<int32_t> & n_out, std::vector<bark_hip_loudness_info> * info = nullptr);
+// device time of ONE loudness_hops launch (level false) or ONE loudness_level launch with its scaled copy (level true) over `count` segments of n_each samples
+double engine_time_loudness(bark_context * ctx, int count, int n_each, int iters, bool level);
 // Long-form text (C15s + C15j): split, run the chunks (chain 0: ONE lock-step job, chunk i with seed rp.seed + i; chain 1: one job per chunk, chunk
 // i + 1 with the voice made of chunk i's three streams, the previous voice where that one is refused), keep the results in ctx->long_result.  Returns
 // the chunk count; throws if a chunk fails.  A text without a word runs as one chunk.

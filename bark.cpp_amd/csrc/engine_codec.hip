@@ -873,6 +873,8 @@ TempoArgs tempo_args(bark_context * c, const int (&seg)[6][kResampleMaxSegments 
     a.x = c->tp_in.p; a.y = c->tp_out.p; a.win = c->tp_win.p; a.seg = c->tp_seg.p; a.pos = c->tp_pos.p; a.B = count;
     return a;
 }
+std::vector<uint8_t> tempo_staged(bark_context * c, const TempoArgs & a, const int (&seg)[6][kResampleMaxSegments + 1], int count, int rate_out, int fmt,
+                                  std::vector<int32_t> & n_out, std::vector<int32_t> * positions);
 }  // namespace
 
 std::vector<uint8_t> engine_tempo_many(bark_context * c, const float * const * pcm, const int * n, int count, const int32_t * speed, int rate_out, int fmt,
@@ -890,10 +892,18 @@ std::vector<uint8_t> engine_tempo_many(bark_context * c, const float * const * p
     }
     if (all_identity && !positions) return engine_resample_many(c, pcm, n, count, 24000, rate_out, fmt, n_out);      // nothing of the rule runs
     int seg[6][kResampleMaxSegments + 1];
-    const int n_frames = fill_tempo_table(seg, n, speed, count);
+    fill_tempo_table(seg, n, speed, count);
     const TempoArgs a = tempo_args(c, seg, count);
+    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->tp_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, c->stream));
+    return tempo_staged(c, a, seg, count, rate_out, fmt, n_out, positions);
+}
+
+namespace {
+// the device half of engine_tempo_many: the segments lie back to back in tp_in
+std::vector<uint8_t> tempo_staged(bark_context * c, const TempoArgs & a, const int (&seg)[6][kResampleMaxSegments + 1], int count, int rate_out, int fmt,
+                                  std::vector<int32_t> & n_out, std::vector<int32_t> * positions) {
+    const int bytes_per = sample_format_bytes(fmt), n_frames = seg[5][count];
     hipStream_t s = c->stream;
-    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->tp_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(c->tp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
     launch_tempo(s, a, seg);
     if (positions) {
@@ -916,6 +926,158 @@ std::vector<uint8_t> engine_tempo_many(bark_context * c, const float * const * p
     c->rp_seg.reserve(c, 5 * (kResampleMaxSegments + 1));
     convert_staged(c, c->tp_out.p, rseg, n_tiles, count, (size_t) seg[3][count], t, 24000, rate_out, fmt, out);
     return out;
+}
+}  // namespace
+
+// ---- loudness (rule C17l) ----------------------------------------------------------------------------------------------------------------------------------
+bool loudness_params_valid(const bark_hip_loudness_params & p) {
+    return (p.target_centilufs == 0 || (p.target_centilufs >= kLoudMinTarget && p.target_centilufs <= kLoudMaxTarget)) &&
+           std::isfinite(p.peak_ceiling) && p.peak_ceiling >= 0.0f && std::isfinite(p.max_gain) && p.max_gain >= 0.0f;
+}
+double loudness_target_ms(int t) { return std::pow(10.0, ((double) t / 100.0 + 0.691) / 10.0); }
+namespace {
+// the segment table of launch_loudness_hops
+void fill_loudness_table(int (&seg)[5][kResampleMaxSegments + 1], const int * n, int count) {
+    memset(seg, 0, sizeof(seg));
+    for (int i = 0; i < count; i++) {
+        const int Hn = n[i] / kLoudHop;
+        seg[0][i] = n[i]; seg[2][i] = Hn;
+        seg[1][i + 1] = seg[1][i] + n[i]; seg[3][i + 1] = seg[3][i] + Hn; seg[4][i + 1] = seg[4][i] + Hn + 1;
+    }
+}
+LoudnessArgs loudness_args(bark_context * c, const int (&seg)[5][kResampleMaxSegments + 1], int count) {
+    c->lv_in.reserve(c, (size_t) seg[1][count]);
+    c->lv_z.reserve(c, (size_t) std::max(seg[3][count], 1));
+    c->lv_seg.reserve(c, 5 * (kResampleMaxSegments + 1));
+    c->lv_peak.reserve(c, (size_t) kResampleMaxSegments);
+    c->lv_req.reserve(c, (size_t) kResampleMaxSegments);
+    c->lv_info.reserve(c, (size_t) kResampleMaxSegments);
+    LoudnessArgs a;
+    a.x = c->lv_in.p; a.seg = c->lv_seg.p; a.z = c->lv_z.p; a.peak = c->lv_peak.p; a.req = c->lv_req.p; a.info = c->lv_info.p; a.B = count;
+    return a;
+}
+void loudness_check(const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params) {
+    if (!pcm || !n || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("loudness: 1 .. 64 segments in one call");
+    for (int i = 0; i < count; i++) {
+        if (!pcm[i] || n[i] < 1 || n[i] > kResampleMaxSamples) throw std::runtime_error("loudness: a segment needs 1 .. 1 310 720 samples");
+        if (params && !loudness_params_valid(params[i])) throw std::runtime_error("loudness: a target of -40 .. -5 LUFS (or 0: off), a ceiling and a cap that are >= 0 and finite");
+        for (int k = 0; k < n[i]; k++) if (!(std::fabs(pcm[i][k]) < 65520.0f)) throw std::runtime_error("loudness: a sample that is not finite or not below 65520 in magnitude");
+    }
+}
+// upload, measure, level: a.y (may be null) receives the levelled samples; `info` and (if wanted) `z` are read back behind the caller's next synchronisation
+void loudness_run(bark_context * c, LoudnessArgs a, const int (&seg)[5][kResampleMaxSegments + 1], const float * const * pcm, const int * n, int count,
+                  const bark_hip_loudness_params * params, LoudnessInfo (&info)[kResampleMaxSegments], std::vector<double> * z) {
+    hipStream_t s = c->stream;
+    LoudnessReq req[kResampleMaxSegments];
+    for (int i = 0; i < count; i++)
+        if (params && params[i].target_centilufs != 0) { req[i].tms = loudness_target_ms(params[i].target_centilufs); req[i].max_gain = params[i].max_gain; req[i].peak_ceiling = params[i].peak_ceiling; }
+    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->lv_in.p + seg[1][i], pcm[i], (size_t) n[i] * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->lv_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->lv_req.p, req, sizeof(LoudnessReq) * (size_t) count, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(c->lv_peak.p, 0, sizeof(unsigned) * (size_t) count, s));
+    launch_loudness_hops(s, a, seg);
+    launch_loudness_level(s, a);
+    HIP_OK(hipMemcpyAsync(info, c->lv_info.p, sizeof(LoudnessInfo) * (size_t) count, hipMemcpyDeviceToHost, s));
+    if (z) {
+        z->assign((size_t) seg[3][count], 0.0);
+        if (!z->empty()) HIP_OK(hipMemcpyAsync(z->data(), c->lv_z.p, z->size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipStreamSynchronize(s));                             // req is a stack object; a later launch on the stream still reads a.y in order
+}
+std::vector<bark_hip_loudness_info> public_info(const LoudnessInfo * info, int count) {
+    std::vector<bark_hip_loudness_info> out((size_t) count);
+    for (int i = 0; i < count; i++) {
+        bark_hip_loudness_info & o = out[(size_t) i];
+        o.mean_square = info[i].mean_square;
+        o.lufs = info[i].mean_square > 0.0 ? -0.691 + 10.0 * std::log10(info[i].mean_square) : -INFINITY;       // for information: the host's log10
+        o.peak = info[i].peak; o.gain = info[i].gain; o.n_blocks = info[i].n_blocks; o.n_abs = info[i].n_abs; o.n_gated = info[i].n_gated; o.flags = info[i].flags;
+    }
+    return out;
+}
+}  // namespace
+
+std::vector<bark_hip_loudness_info> engine_loudness_many(bark_context * c, const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params,
+                                                         std::vector<double> * z) {
+    HIP_OK(hipSetDevice(c->device));
+    loudness_check(pcm, n, count, params);
+    int seg[5][kResampleMaxSegments + 1];
+    fill_loudness_table(seg, n, count);
+    const LoudnessArgs a = loudness_args(c, seg, count);
+    LoudnessInfo info[kResampleMaxSegments];
+    loudness_run(c, a, seg, pcm, n, count, params, info, z);
+    return public_info(info, count);
+}
+
+std::vector<uint8_t> engine_level_many(bark_context * c, const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params,
+                                       const int32_t * speed, int rate_out, int fmt, std::vector<int32_t> & n_out, std::vector<bark_hip_loudness_info> * info_out) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!params || !speed) throw std::runtime_error("level: a request and a speed per segment");
+    loudness_check(pcm, n, count, params);
+    if (!resample_pair_supported(24000, rate_out)) throw std::runtime_error("level: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
+    const int bytes_per = sample_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("level: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    bool all_off = true, all_identity = true;
+    for (int i = 0; i < count; i++) {
+        if (tempo_out_len(n[i], speed[i]) < 0) throw std::runtime_error("level: a speed of 500 .. 2000 per mille");
+        all_off = all_off && params[i].target_centilufs == 0;
+        all_identity = all_identity && speed[i] == 1000;
+    }
+    if (all_off) {                                               // nothing of the rule runs
+        if (info_out) { bark_hip_loudness_info one{}; one.gain = 1.0f; info_out->assign((size_t) count, one); }
+        return engine_tempo_many(c, pcm, n, count, speed, rate_out, fmt, n_out);
+    }
+    int seg[5][kResampleMaxSegments + 1];
+    fill_loudness_table(seg, n, count);
+    LoudnessArgs a = loudness_args(c, seg, count);
+    LoudnessInfo info[kResampleMaxSegments];
+    const size_t total_in = (size_t) seg[1][count];
+    std::vector<uint8_t> out;
+    if (!all_identity) {                                         // the levelled samples are the tempo kernel's input
+        int tseg[6][kResampleMaxSegments + 1];
+        fill_tempo_table(tseg, n, speed, count);
+        const TempoArgs ta = tempo_args(c, tseg, count);
+        a.y = c->tp_in.p;
+        loudness_run(c, a, seg, pcm, n, count, params, info, nullptr);
+        out = tempo_staged(c, ta, tseg, count, rate_out, fmt, n_out, nullptr);
+    } else {                                                     // .. or the resampler's
+        int rseg[5][kResampleMaxSegments + 1];
+        const int n_tiles = fill_segment_table(rseg, n, count, 24000, rate_out, n_out);
+        out.resize((size_t) rseg[3][count] * (size_t) bytes_per);
+        ensure_resample_buffers(c, total_in, out.size());
+        a.y = c->rp_in.p;
+        loudness_run(c, a, seg, pcm, n, count, params, info, nullptr);
+        const ResampleTable * t = resample_pair_table(24000, rate_out);
+        if (!t && fmt == BARK_HIP_SAMPLE_F32) {                  // 24 kHz f32: the levelled samples themselves
+            HIP_OK(hipMemcpyAsync(out.data(), c->rp_in.p, out.size(), hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));
+        } else convert_staged(c, c->rp_in.p, rseg, n_tiles, count, total_in, t, 24000, rate_out, fmt, out);
+    }
+    if (info_out) *info_out = public_info(info, count);
+    return out;
+}
+
+double engine_time_loudness(bark_context * c, int count, int n_each, int iters, bool level) {
+    HIP_OK(hipSetDevice(c->device));
+    if (count < 1 || count > kResampleMaxSegments || n_each < 1 || n_each > kResampleMaxSamples) throw std::runtime_error("time_loudness: 1 .. 64 segments of 1 .. 1 310 720 samples");
+    const std::vector<int> n((size_t) count, n_each);
+    int seg[5][kResampleMaxSegments + 1];
+    fill_loudness_table(seg, n.data(), count);
+    LoudnessArgs a = loudness_args(c, seg, count);
+    c->rp_in.reserve(c, (size_t) seg[1][count]);
+    a.y = c->rp_in.p;
+    LoudnessReq req[kResampleMaxSegments];
+    for (int i = 0; i < count; i++) { req[i].tms = loudness_target_ms(-1600); req[i].max_gain = 10.0f; req[i].peak_ceiling = 1.0f; }
+    hipStream_t s = c->stream;
+    HIP_OK(hipMemsetAsync(c->lv_in.p, 0, (size_t) seg[1][count] * 4, s));      // the time does not depend on the values: every chain runs in full
+    HIP_OK(hipMemcpyAsync(c->lv_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->lv_req.p, req, sizeof(LoudnessReq) * (size_t) count, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(c->lv_peak.p, 0, sizeof(unsigned) * (size_t) count, s));
+    HIP_OK(hipStreamSynchronize(s));
+    iters = std::max(1, iters);
+    launch_loudness_hops(s, a, seg);                             // the level launch reads what a hops launch wrote
+    auto one = [&] { if (level) launch_loudness_level(s, a); else launch_loudness_hops(s, a, seg); };
+    for (int i = 0; i < 2; i++) one();
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) one(); }) / iters;
 }
 
 double engine_time_tempo(bark_context * c, int count, int n_each, int speed, int iters) {

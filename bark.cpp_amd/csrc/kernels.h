@@ -394,4 +394,27 @@ const float * tempo_window();
 struct TempoArgs { const float * x = nullptr; float * y = nullptr; const float * win = nullptr; const int * seg = nullptr; int * pos = nullptr; int B = 1; };
 void launch_tempo(hipStream_t s, const TempoArgs & a, const int (&host_seg)[6][kResampleMaxSegments + 1]);
 
+// ---- loudness: gated BS.1770 measure and the gain to a target over up to 64 segments in two launches (rule C17l; codec_kernels.hip) ----
+// Segment s of n samples has Hn = n / 2400 hops.  loudness_hops_kernel: one lane per (segment, hop) and one more per segment for the samples behind the
+// last hop; the lane of hop h runs both K-weighting biquads (f64, transposed direct form II, every product and sum rounded once) over the 7200 samples
+// that end with the hop, from zero state and +0 in front of the segment, and writes z[h] = the sum of squares of the hop's own 2400 outputs; every lane
+// folds max |x| of its own samples into peak[s] (atomicMax on the bits; the caller zeroes peak before the launch).  loudness_level_kernel: one workgroup
+// per segment - its first lane runs the blocks, both gates and the gain (req[s].tms == 0: measure only, gain 1) and writes info[s], then all lanes write
+// y[i] = x[i] g32 (y == nullptr: measure only).  seg is a device table [5][kResampleMaxSegments + 1] of ints: lengths, sample offsets (prefix sums, of
+// x and y alike), hop counts, offsets into z (prefix sums of Hn) and lane offsets (prefix sums of Hn + 1), each closed by its total; launch_loudness_hops
+// checks the host copy it is given against the rule before anything runs.
+constexpr int kLoudHop = 2400, kLoudPre = 4800, kLoudRun = kLoudPre + kLoudHop, kLoudBlockHops = 4;
+constexpr int kLoudMinTarget = -4000, kLoudMaxTarget = -500;
+enum { kLoudUnmeasurable = 1, kLoudCapBound = 2, kLoudCeilingBound = 4 };
+// the committed constants: shelf b0, b1, b2, a1, a2, high-pass a1, a2, the absolute gate A as a mean square, 9600 A
+const double * loudness_constants();
+struct LoudnessReq { double tms = 0.0; float max_gain = 0.0f, peak_ceiling = 0.0f; };
+struct LoudnessInfo { double mean_square; float peak, gain; int32_t n_blocks, n_abs, n_gated, flags; };
+struct LoudnessArgs {
+    const float * x = nullptr; float * y = nullptr; const int * seg = nullptr; double * z = nullptr; unsigned * peak = nullptr;
+    const LoudnessReq * req = nullptr; LoudnessInfo * info = nullptr; int B = 1;
+};
+void launch_loudness_hops(hipStream_t s, const LoudnessArgs & a, const int (&host_seg)[5][kResampleMaxSegments + 1]);
+void launch_loudness_level(hipStream_t s, const LoudnessArgs & a);
+
 }  // namespace barkhip

@@ -30,9 +30,12 @@
 // Speaking rate (rule C16t of bark_mi355x.h): "speed": a number in 0.5 .. 2.0 in a /bark request (default: --speed, 1.0), sent to the collector as
 // lround(1000 speed) per mille - the answer is time-scaled on the device before "sample_rate" / "format" apply (with "long": every chunk, before the join),
 // and the WAV header follows the actual sample count.  Anything else is a 400.
+// Loudness (rule C17l of bark_mi355x.h): "loudness": a number in -40 .. -5 (LUFS) in a /bark request (default: --loudness; off without it), sent to the
+// collector as lround(100 v) hundredths with a peak ceiling of 1.0 and a gain cap of 10 (+20 dB) - the answer is levelled on the device in front of "speed",
+// "sample_rate" and "format" (with "long": every chunk on its own, before the join).  Anything else is a 400 and draws no seed.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw] [--long] [--max-tokens n] [--gap-ms n] [--speed x]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw] [--long] [--max-tokens n] [--gap-ms n] [--speed x] [--loudness lufs]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -76,6 +79,7 @@ struct Options {
     int sample_rate = 24000; std::string format = "f32";      // --sample-rate / --format: what a request without "sample_rate" / "format" is answered in
     bool long_form = false; int max_tokens = 0, gap_ms = 250;  // --long / --max-tokens / --gap-ms: what a request without "long" / "max_tokens" / "gap_ms" gets
     double speed = 1.0;                            // --speed: the speaking rate of a request without "speed"
+    bool has_loudness = false; double loudness = 0.0;      // --loudness: the target of a request without "loudness" (none: no levelling)
 };
 
 bool send_all(int fd, const char * p, size_t n) {
@@ -106,6 +110,11 @@ bool long_valid(int32_t max_tokens, int32_t gap_ms) { return max_tokens >= 0 && 
 double speed_default = 1.0;
 bool speed_valid(double speed) { return speed >= 0.5 && speed <= 2.0; }
 int speed_permille(double speed) { return (int) lround(1000.0 * speed); }
+// loudness (rule C17l): a target in -40 .. -5 LUFS, sent as lround(100 v); ceiling 1.0, cap 10 (+20 dB); anything else (a NaN too) is refused
+bool loudness_default_on = false;
+double loudness_default = 0.0;
+bool loudness_valid(double v) { return v >= -40.0 && v <= -5.0; }
+bark_hip_loudness_params loudness_request(double v) { return bark_hip_loudness_params{(int32_t) lround(100.0 * v), 1.0f, 10.0f}; }
 bool format_valid(const bark_hip_audio_format & f) { return f.sample_format >= 0 && f.sample_format <= 2 && bark_hip_resample_out_len(1, 24000, f.sample_rate) >= 1; }
 // the voices by name: read by every /bark request, written by POST /voices.  An entry is never changed, only replaced: a request that has looked its
 // voice up keeps it alive through its shared_ptr while a later POST puts another one under the same name
@@ -267,7 +276,18 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 return;
             }
             const int permille = speed_permille(speed);
-            const bool plain = af.sample_rate == 24000 && af.sample_format == BARK_HIP_SAMPLE_F32 && permille == 1000;
+            // "loudness": a number in -40 .. -5 - the target in LUFS; checked here as well, for the same reason
+            double loudness = loudness_default;
+            const int hu = barkhttp::json_number(body, "loudness", loudness);
+            const bool levels = hu > 0 || loudness_default_on;
+            if (hu < 0 || (levels && !loudness_valid(loudness))) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"loudness\" must be a number in -40 .. -5");
+                ::shutdown(fd, SHUT_RDWR);
+                ::close(fd);
+                return;
+            }
+            const bark_hip_audio_render how{af, permille, levels ? loudness_request(loudness) : bark_hip_loudness_params{0, 0.0f, 0.0f}};
+            const bool plain = af.sample_rate == 24000 && af.sample_format == BARK_HIP_SAMPLE_F32 && permille == 1000 && !levels;
             // "voice": absent - no voice; otherwise a string that names a voice of the table (held until the answer is sent)
             std::shared_ptr<const VoiceFile> vf;
             int has_voice = 0;
@@ -291,7 +311,8 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 if (vf) vp = bark_hip_voice_prompt{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
                                                    vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
                 const bark_hip_long_params lp{max_tokens, 0, {gap_ms * 24, 0, 0.0f, 0}};
-                ticket = permille == 1000 ? bark_hip_batcher_submit_long(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af)
+                ticket = levels           ? bark_hip_batcher_submit_long_with(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &how)
+                       : permille == 1000 ? bark_hip_batcher_submit_long(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af)
                                           : bark_hip_batcher_submit_long_at(batcher, text.c_str(), &lp, &rp, &flt, vf ? &vp : nullptr, &af, permille);
                 if (ticket <= 0) {
                     respond(fd, 400, "Bad Request", "text/plain", "the text gives more than 64 chunks");
@@ -316,7 +337,8 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 bark_hip_voice_prompt vp{};
                 if (vf) vp = bark_hip_voice_prompt{vf->semantic.data(), (int32_t) vf->semantic.size(), vf->coarse.data(), (int32_t) (vf->coarse.size() / 2),
                                                    vf->fine.data(), (int32_t) (vf->fine.size() / 8)};
-                ticket = permille == 1000 ? bark_hip_batcher_submit_as(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af)
+                ticket = levels           ? bark_hip_batcher_submit_with(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &how)
+                       : permille == 1000 ? bark_hip_batcher_submit_as(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af)
                                           : bark_hip_batcher_submit_at(batcher, text.c_str(), &rp, &flt, vf ? &vp : nullptr, &af, permille);
                 int nb = ticket > 0 ? bark_hip_batcher_wait_bytes(batcher, ticket, nullptr, 0) : -1;     // probe: -(2 + bytes)
                 if (nb <= -2) {
@@ -357,7 +379,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")] [--speed x (speaking rate 0.5 .. 2.0, default 1; a request's \"speed\")]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")] [--speed x (speaking rate 0.5 .. 2.0, default 1; a request's \"speed\")] [--loudness lufs (target -40 .. -5, default: no levelling; a request's \"loudness\")]\n", argv0);
 }
 
 }  // namespace
@@ -389,6 +411,7 @@ int main(int argc, char ** argv) {
         else if (a == "--max-tokens") o.max_tokens = atoi(next("--max-tokens"));
         else if (a == "--gap-ms") o.gap_ms = atoi(next("--gap-ms"));
         else if (a == "--speed") o.speed = atof(next("--speed"));
+        else if (a == "--loudness") { o.loudness = atof(next("--loudness")); o.has_loudness = true; }
         else { usage(argv[0]); return a == "-h" || a == "--help" ? 0 : 1; }
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
@@ -398,6 +421,8 @@ int main(int argc, char ** argv) {
     if (!long_valid(o.max_tokens, o.gap_ms)) { fprintf(stderr, "%s: --max-tokens must be 0 .. 255 and --gap-ms 0 .. 60000\n", argv[0]); return 1; }
     speed_default = o.speed;
     if (!speed_valid(o.speed)) { fprintf(stderr, "%s: --speed must be 0.5 .. 2.0\n", argv[0]); return 1; }
+    loudness_default_on = o.has_loudness; loudness_default = o.loudness;
+    if (o.has_loudness && !loudness_valid(o.loudness)) { fprintf(stderr, "%s: --loudness must be -40 .. -5\n", argv[0]); return 1; }
     {
         std::map<std::string, VoiceFile> files;
         for (const std::string & v : o.voices) {

@@ -277,6 +277,48 @@ BARK_API int bark_hip_long_audio_at(struct bark_context * bctx, const struct bar
  * the context's stream).  Returns < 0 on error. */
 BARK_API double bark_hip_time_tempo(struct bark_context * bctx, int count, int n_each, int speed_permille, int iters);
 
+/* Loudness (rule C17l): the integrated loudness of 24 kHz f32 audio by ITU-R BS.1770 with both gates, measured on the device, and one
+ * gain per recording that brings it to a target.  Arithmetic: f64, every product and sum rounded once; the K-weighting biquads (BS.1770's prototypes
+ * evaluated at 24 kHz) run per 100 ms hop over the 7200 samples that end with the hop, from zero state, and z[h] is the sum of squares of the hop's own 2400
+ * outputs; 400 ms blocks S[j] = ((z[j] + z[j+1]) + z[j+2]) + z[j+3]; absolute gate S[j] > 9600 A, relative gate S[j] c1 > 0.1 sum1 (-10 LU), all in the
+ * mean-square domain; M = sum2 / (9600 c2).  Fewer than 4 hops (n < 9600) or no block behind the gates: unmeasurable, the gain is exactly 1 and flags has
+ * BARK_HIP_LOUDNESS_UNMEASURABLE.  Otherwise g = sqrt(Tms / M), at most max_gain (if > 0), at most peak_ceiling / peak (if both > 0), g32 = (float) g and
+ * y[i] = x[i] g32.  The samples obey the tempo calls' limits (1 .. 1 310 720, finite, |x| < 65520).
+ * target_centilufs: hundredths of a LUFS, -4000 .. -500; 0: off.  peak_ceiling, max_gain: >= 0 and finite; 0: none.
+ * info: mean_square M (0 if unmeasurable), lufs = -0.691 + 10 log10(M) formed on the host (-inf if unmeasurable), peak = max |x|, the gain applied (1
+ * where the request is off), n_blocks J, n_abs c1, n_gated c2, flags.
+ * bark_hip_loudness_constants: out9 = shelf b0, b1, b2, a1, a2, high-pass a1, a2, A, 9600 A (committed bit patterns); returns 9.  bark_hip_loudness_target_ms:
+ * Tms = 10^((t / 100 + 0.691) / 10), or -1 for a target outside the range.  Both need no context.
+ * bark_hip_loudness_many: measures count <= 64 recordings in the two launches (no scaled copy); params (NULL: none) only decide the gain that info reports.
+ * Returns count, or -1 with the context still usable.  bark_hip_loudness_hops: the z table of one recording; returns Hn = n / 2400, or -1.
+ * bark_hip_level_many: caller audio, a request and a speed (NULL: 1000 each) per recording -> level, C16t, `to` (NULL: 24000 f32) in one call without a round
+ * trip to the host in between; n_out, info optional; returns the bytes written, or -1.  Every request off: bark_hip_tempo_many itself. */
+enum { BARK_HIP_LOUDNESS_UNMEASURABLE = 1, BARK_HIP_LOUDNESS_CAP_BOUND = 2, BARK_HIP_LOUDNESS_CEILING_BOUND = 4 };
+struct bark_hip_loudness_params { int32_t target_centilufs; float peak_ceiling; float max_gain; };
+struct bark_hip_loudness_info { double mean_square, lufs; float peak, gain; int32_t n_blocks, n_abs, n_gated, flags; };
+/* how a held result is rendered: rate and format, speaking rate (1000: none), levelling (target 0: none) */
+struct bark_hip_audio_render { struct bark_hip_audio_format fmt; int32_t speed_permille; struct bark_hip_loudness_params loudness; };
+BARK_API int bark_hip_loudness_constants(double * out9);
+BARK_API double bark_hip_loudness_target_ms(int target_centilufs);
+BARK_API int bark_hip_loudness_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const struct bark_hip_loudness_params * params,
+                                    struct bark_hip_loudness_info * info);
+BARK_API int bark_hip_loudness_hops(struct bark_context * bctx, const float * pcm, int n, double * z, int capacity);
+BARK_API int bark_hip_level_many(struct bark_context * bctx, const float * const * pcm, const int * n, int count, const struct bark_hip_loudness_params * params,
+                                 const int32_t * speed_permille, const struct bark_hip_audio_format * to, void * out_concat, int capacity_bytes, int32_t * n_out,
+                                 struct bark_hip_loudness_info * info);
+/* The results a context holds, levelled, at a speaking rate, in a format: the return conventions of the _at forms (-1 also for a target outside the range
+ * or a negative or non-finite ceiling or cap) and info (optional): one record, for bark_hip_long_audio_with one per chunk (info_capacity records; fewer
+ * than the chunks: -1).  Loudness off: the bytes of the _at form, no further launch, info {gain 1, all else 0}.  A long text's chunks are levelled each
+ * on its own, untrimmed, in front of tempo and join: the join's threshold sees the levelled signal. */
+BARK_API int bark_hip_get_audio_with(struct bark_context * bctx, const struct bark_hip_audio_render * how, void * out, int capacity_bytes, struct bark_hip_loudness_info * info);
+BARK_API int bark_hip_batch_audio_with(struct bark_context * bctx, int i, const struct bark_hip_audio_render * how, void * out, int capacity_bytes,
+                                       struct bark_hip_loudness_info * info);
+BARK_API int bark_hip_long_audio_with(struct bark_context * bctx, const struct bark_hip_audio_render * how, void * out, int capacity_bytes,
+                                      struct bark_hip_loudness_info * info, int info_capacity);
+/* Device time (us) of ONE loudness_hops launch (level == 0) or ONE loudness_level launch with its scaled copy (level != 0) over `count` segments of n_each
+ * samples, averaged over `iters` launches (hipEvents on the context's stream).  Returns < 0 on error. */
+BARK_API double bark_hip_time_loudness(struct bark_context * bctx, int count, int n_each, int level, int iters);
+
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
 BARK_API struct bark_context * bark_hip_clone_context(struct bark_context * src, uint32_t seed);
@@ -439,6 +481,15 @@ BARK_API int64_t bark_hip_batcher_submit_at(struct bark_hip_batcher * b, const c
 BARK_API int64_t bark_hip_batcher_submit_long_at(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
                                                  const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
                                                  const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_format * fmt, int speed_permille);
+/* bark_hip_batcher_submit_at / _submit_long_at with a levelling too (rule C17l; `how` as for bark_hip_get_audio_with, -1 for what that call refuses).  The
+ * worker runs ONE measure launch and ONE level launch per job over all its requests with levelling on, in front of the single tempo launch; a long text's parts
+ * are levelled, each on its own, in front of tempo and join.  Levelling off: the path of the _at form. */
+BARK_API int64_t bark_hip_batcher_submit_with(struct bark_hip_batcher * b, const char * text, const struct bark_hip_request_params * params,
+                                              const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
+                                              const struct bark_hip_audio_render * how);
+BARK_API int64_t bark_hip_batcher_submit_long_with(struct bark_hip_batcher * b, const char * text, const struct bark_hip_long_params * long_params,
+                                                   const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
+                                                   const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_render * how);
 BARK_API void bark_hip_batcher_stats(struct bark_hip_batcher * b, int * n_batches, int * n_requests, int * largest_batch);
 /* requests that joined a job that was already running (continuous admission: while the semantic stage of a job has free slots, requests
  * arriving in the meantime are taken along, up to max_batch per job) */
