@@ -189,6 +189,7 @@ EXPORTS = [
     "bark_hip_batch_audio_at", "bark_hip_long_audio_at", "bark_hip_batcher_submit_at", "bark_hip_batcher_submit_long_at", "bark_hip_time_tempo",
     "bark_hip_loudness_constants", "bark_hip_loudness_target_ms", "bark_hip_loudness_many", "bark_hip_loudness_hops", "bark_hip_level_many", "bark_hip_get_audio_with",
     "bark_hip_batch_audio_with", "bark_hip_long_audio_with", "bark_hip_batcher_submit_with", "bark_hip_batcher_submit_long_with", "bark_hip_time_loudness",
+    "bark_hip_codec_decode_many",
 ]
 
 
@@ -231,6 +232,7 @@ def load_library() -> C.CDLL:
     lib.bark_hip_fine.argtypes = [vp, ip, C.c_int, ip, C.c_int]
     lib.bark_hip_fine_many.argtypes = [vp, ip, ip, C.c_int, ip, C.c_int]
     lib.bark_hip_codec_decode.argtypes = [vp, ip, C.c_int, C.c_int, fp, C.c_int]
+    lib.bark_hip_codec_decode_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.c_int, fp, C.c_int]
     lib.bark_hip_codec_tap.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int, fp, C.c_int]
     lib.bark_hip_has_codec_encoder.argtypes = [vp]
     lib.bark_hip_codec_encode.argtypes = [vp, fp, C.c_int, C.c_int, ip, C.c_int]
@@ -544,6 +546,24 @@ class BarkContext:
         if n < 0:
             raise RuntimeError("bark_hip_codec_decode failed")
         return pcm[:n].copy()
+
+    def codec_decode_many(self, codes_list) -> list:
+        """n <= 32 utterances in one pass, as a lock-step job decodes them (bark_hip_codec_decode_many): one [n_q][T_i] matrix each, all of one n_q;
+        one array of 320 T_i samples per utterance."""
+        cs = [_i32(x) for x in codes_list]
+        assert cs and all(x.ndim == 2 and x.shape[0] == cs[0].shape[0] for x in cs)
+        n_q = cs[0].shape[0]
+        T = _i32([x.shape[1] for x in cs])
+        ptrs = (C.c_void_p * len(cs))(*[x.ctypes.data for x in cs])
+        out = np.zeros(320 * max(int(T.sum()), 1), np.float32)
+        n = self._lib.bark_hip_codec_decode_many(self._h, ptrs, T.ctypes.data, len(cs), n_q, out.ctypes.data, out.size)
+        if n < 0:
+            raise RuntimeError("bark_hip_codec_decode_many failed")
+        assert n == 320 * int(T.sum())
+        res, off = [], 0
+        for t in T:
+            res.append(out[off:off + 320 * int(t)].copy()); off += 320 * int(t)
+        return res
 
     def codec_tap(self, codes_qxT, stage: int) -> np.ndarray:
         codes = _i32(codes_qxT)

@@ -245,6 +245,22 @@ int bark_hip_codec_decode(struct bark_context * bctx, const int32_t * codes, int
     });
 }
 
+int bark_hip_codec_decode_many(struct bark_context * bctx, const int32_t * const * codes, const int * T, int n, int n_q, float * pcm_concat, int capacity) {
+    if (!bctx || !codes || !T || !pcm_concat || n <= 0 || n > 32) return -1;
+    long total = 0;                                                 // refused before any work: a result that does not fit
+    for (int i = 0; i < n; i++) { if (!codes[i]) return -1; total += T[i] > 0 ? 320L * T[i] : 0; }
+    if (total > (long) capacity) return -1;
+    return guarded("bark_hip_codec_decode_many", -1, [&] {
+        std::vector<std::vector<float>> r = engine_codec_decode_many(bctx, std::vector<const int32_t *>(codes, codes + n), n_q, std::vector<int>(T, T + n), -1, nullptr);
+        size_t off = 0;
+        for (auto & v : r) {
+            if (off + v.size() > (size_t) capacity) throw std::runtime_error("output buffer too small");
+            memcpy(pcm_concat + off, v.data(), v.size() * 4); off += v.size();
+        }
+        return (int) off;
+    });
+}
+
 int bark_hip_codec_tap(struct bark_context * bctx, const int32_t * codes, int n_q, int T, int stage, float * out, int capacity) {
     if (!bctx || !codes || !out) return -1;
     return guarded("bark_hip_codec_tap", -1, [&] {

@@ -78,6 +78,12 @@ BARK_API int bark_hip_fine_many(struct bark_context * bctx, const int32_t * coar
 /* EnCodec decode: codes [n_q][T] (time contiguous) -> pcm (capacity floats; 320 * T are produced). Returns samples or -1. */
 BARK_API int bark_hip_codec_decode(struct bark_context * bctx, const int32_t * codes, int n_q, int T, float * pcm, int capacity);
 
+/* Test hook: the decoder's batched form, as every lock-step job runs it (one launch per operator for n <= 32 utterances, their rows back to back).
+ * codes[i]: [n_q][T[i]] (time contiguous); utterance i's 320 * T[i] samples are written back to back into pcm_concat (capacity floats), bit-identical
+ * to n single calls.  Returns 320 * sum T[i], or -1.  Refused before any work: a null argument or matrix, n outside 1 .. 32, capacity below
+ * 320 * sum T[i]; then as bark_hip_codec_decode: a T[i] outside 1 .. 4096, n_q outside 1 .. the file's codebook count, a code outside 0 .. 1023. */
+BARK_API int bark_hip_codec_decode_many(struct bark_context * bctx, const int32_t * const * codes, const int * T, int n, int n_q, float * pcm_concat, int capacity);
+
 /* Per-layer parity tap of the codec: activation [C][T'] after stage 0 (first conv), 1 (LSTM + skip),
  * 2..5 (the four upsampling blocks).  Returns the element count or -1. */
 BARK_API int bark_hip_codec_tap(struct bark_context * bctx, const int32_t * codes, int n_q, int T, int stage, float * out, int capacity);
