@@ -6,6 +6,6 @@ The directory name contains a dot, so import it through `load_package()` of the 
 """
 from . import voice  # noqa: F401
 from .api import (BarkContext, Batcher, BarkContextParams, BarkHipAudioFormat, BarkHipAudioRender, BarkHipJoinParams, BarkHipLongParams, BarkHipLoudnessInfo,  # noqa: F401
-                  BarkHipLoudnessParams, BarkHipStats, BarkHipVoicePrompt, audio_format, audio_render, build_library, default_params, join_params, library_path,
+                  BarkHipLoudnessParams, BarkHipStats, BarkHipVoicePrompt, audio_format, audio_render, build_library, default_params, flac_max_bytes, join_params, library_path,
                   load_library, loudness_params, speed_permille)
 from .voice import VoicePrompt  # noqa: F401

@@ -75,14 +75,21 @@ def join_params(gap_samples: int = 6000, fade_samples: int = 0, trim_threshold: 
 
 
 SPLIT_MAX_CHUNKS = 64
-SAMPLE_F32, SAMPLE_S16, SAMPLE_MULAW = 0, 1, 2          # enum bark_hip_sample_format
+SAMPLE_F32, SAMPLE_S16, SAMPLE_MULAW, SAMPLE_FLAC = 0, 1, 2, 3          # enum bark_hip_sample_format
 SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "mulaw": SAMPLE_MULAW}
-SAMPLE_DTYPES = {SAMPLE_F32: np.float32, SAMPLE_S16: np.int16, SAMPLE_MULAW: np.uint8}
+CONTAINER_FORMATS = {"flac": SAMPLE_FLAC}                                # enum bark_hip_container_format: a stream over the s16 samples (rule C18f)
+SAMPLE_DTYPES = {SAMPLE_F32: np.float32, SAMPLE_S16: np.int16, SAMPLE_MULAW: np.uint8, SAMPLE_FLAC: np.uint8}       # "flac": the bytes of a complete stream (rule C18f)
+FLAC_BLOCK = 4096                                                        # samples per frame
 
 
 def audio_format(rate: int = 24000, fmt="f32") -> BarkHipAudioFormat:
-    """fmt: "f32" | "s16" | "mulaw", or the enum's value"""
-    return BarkHipAudioFormat(int(rate), SAMPLE_FORMATS[fmt] if isinstance(fmt, str) else int(fmt))
+    """fmt: "f32" | "s16" | "mulaw" | "flac" (the routes that render a held result and the collector; rule C18f), or the enum's value"""
+    return BarkHipAudioFormat(int(rate), (CONTAINER_FORMATS[fmt] if fmt in CONTAINER_FORMATS else SAMPLE_FORMATS[fmt]) if isinstance(fmt, str) else int(fmt))
+
+
+def flac_max_bytes(n: int) -> int:
+    """The size no FLAC stream of n samples exceeds (bark_hip_flac_max_bytes), or -1 for n outside 1 .. 2^26."""
+    return int(load_library().bark_hip_flac_max_bytes(int(n)))
 
 
 def speed_permille(speed) -> int:
@@ -190,6 +197,7 @@ EXPORTS = [
     "bark_hip_loudness_constants", "bark_hip_loudness_target_ms", "bark_hip_loudness_many", "bark_hip_loudness_hops", "bark_hip_level_many", "bark_hip_get_audio_with",
     "bark_hip_batch_audio_with", "bark_hip_long_audio_with", "bark_hip_batcher_submit_with", "bark_hip_batcher_submit_long_with", "bark_hip_time_loudness",
     "bark_hip_codec_decode_many",
+    "bark_hip_flac_max_bytes", "bark_hip_flac_encode_many", "bark_hip_flac_frames", "bark_hip_time_flac", "bark_hip_time_flac_launch",
 ]
 
 
@@ -315,6 +323,13 @@ def load_library() -> C.CDLL:
                                                       C.POINTER(BarkHipVoicePrompt), C.POINTER(BarkHipAudioRender)]
     lib.bark_hip_time_loudness.restype = C.c_double
     lib.bark_hip_time_loudness.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.bark_hip_flac_max_bytes.argtypes = [C.c_int]
+    lib.bark_hip_flac_encode_many.argtypes = [vp, C.POINTER(C.c_void_p), ip, C.c_int, C.c_int, vp, C.c_int, ip]
+    lib.bark_hip_flac_frames.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int]
+    lib.bark_hip_time_flac.restype = C.c_double
+    lib.bark_hip_time_flac.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.bark_hip_time_flac_launch.restype = C.c_double
+    lib.bark_hip_time_flac_launch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_time_join.restype = C.c_double
     lib.bark_hip_time_join.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.bark_hip_generate_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
@@ -1022,6 +1037,45 @@ class BarkContext:
         us = self._lib.bark_hip_time_loudness(self._h, int(count), int(n_each), int(bool(level)), int(iters))
         if us < 0:
             raise RuntimeError("bark_hip_time_loudness failed")
+        return us
+
+    # ---- FLAC (rule C18f): the lossless encoder of the output path; the routes take it as fmt="flac", these calls take caller audio ----
+    def flac_encode_many(self, pcm_list, rate: int = 24000) -> list:
+        """Up to 64 recordings of int16 samples at `rate` -> one complete FLAC stream (bytes) each, in two launches (bark_hip_flac_encode_many)."""
+        xs = [np.ascontiguousarray(x, np.int16).reshape(-1) for x in pcm_list]
+        ptrs = (C.c_void_p * max(len(xs), 1))(*[x.ctypes.data for x in xs])
+        ns = np.asarray([len(x) for x in xs], np.int32)
+        cap = sum(max(self._lib.bark_hip_flac_max_bytes(len(x)), 0) for x in xs)
+        out = np.zeros(max(cap, 1), np.uint8)
+        lengths = np.zeros(max(len(xs), 1), np.int32)
+        got = self._lib.bark_hip_flac_encode_many(self._h, ptrs, ns.ctypes.data, len(xs), int(rate), out.ctypes.data, cap, lengths.ctypes.data)
+        if got < 0:
+            raise ValueError("bark_hip_flac_encode_many refused the call (recording count or length, the rate)")
+        res, off = [], 0
+        for k in lengths[:len(xs)]:
+            res.append(out[off:off + int(k)].tobytes()); off += int(k)
+        return res
+
+    def flac_encode(self, pcm, rate: int = 24000) -> bytes:
+        """One recording of int16 samples as a FLAC stream (see flac_encode_many)."""
+        return self.flac_encode_many([pcm], rate)[0]
+
+    def flac_frames(self, pcm, rate: int = 24000) -> np.ndarray:
+        """[frames][4]: subframe code (0 CONSTANT, 1 VERBATIM, 8 + o FIXED of order o), partition order, byte length and CRC-16 of every frame the device
+        makes of one recording (bark_hip_flac_frames)."""
+        x = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+        out = np.zeros((max((len(x) + FLAC_BLOCK - 1) // FLAC_BLOCK, 1), 4), np.int32)
+        k = self._lib.bark_hip_flac_frames(self._h, x.ctypes.data, len(x), int(rate), out.ctypes.data, len(out))
+        if k < 0:
+            raise ValueError("bark_hip_flac_frames refused the recording")
+        return out[:k]
+
+    def time_flac(self, count: int, n_each: int, iters: int = 20, which: int = 0) -> float:
+        """Device time (us) of the encoder's two launches (which 0), the frames launch (1) or the pack launch (2)."""
+        us = (self._lib.bark_hip_time_flac(self._h, int(count), int(n_each), int(iters)) if which == 0
+              else self._lib.bark_hip_time_flac_launch(self._h, int(count), int(n_each), int(which), int(iters)))
+        if us < 0:
+            raise RuntimeError("bark_hip_time_flac failed")
         return us
 
     def request_params(self, **over) -> BarkHipRequestParams:

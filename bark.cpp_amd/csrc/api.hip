@@ -417,10 +417,26 @@ long long resampled_bytes(const int * n, int count, int rate_in, const bark_hip_
     }
     return total;
 }
+// BARK_HIP_SAMPLE_FLAC (rule C18f): a stream's length is known once it is made, so these routes render first and check the capacity against the real length
+bool wants_flac(const struct bark_hip_audio_format * fmt) { return fmt && fmt->sample_format == BARK_HIP_SAMPLE_FLAC; }
+int deliver(const std::vector<uint8_t> & r, void * out, int capacity_bytes) {
+    if (r.size() > (size_t) 0x7ffffff0) return -1;
+    if (!out || (size_t) std::max(capacity_bytes, 0) < r.size()) return -2 - (int) r.size();
+    memcpy(out, r.data(), r.size());
+    return (int) r.size();
+}
 // 24 kHz f32 samples held by the context -> `fmt`: the byte count, -(2 + bytes) if it does not fit, -1
 int audio_as(struct bark_context * bctx, const char * what, const std::vector<float> & pcm, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes) {
     if (!fmt || pcm.empty()) return -1;
     const int n = (int) pcm.size();
+    if (wants_flac(fmt)) {
+        if (!resample_pair_supported(24000, fmt->sample_rate) || n > kResampleMaxSamples) return -1;
+        return guarded(what, -1, [&] {
+            const float * p = pcm.data();
+            std::vector<int32_t> n_out;
+            return deliver(engine_resample_many(bctx, &p, &n, 1, 24000, fmt->sample_rate, fmt->sample_format, n_out), out, capacity_bytes);
+        });
+    }
     const long long bytes = resampled_bytes(&n, 1, 24000, *fmt);
     if (bytes < 0 || bytes > 0x7ffffff0LL) return -1;
     if (!out || (long long) capacity_bytes < bytes) return -2 - (int) bytes;
@@ -534,7 +550,7 @@ int bark_hip_generate_long(struct bark_context * bctx, const char * text, const 
 int bark_hip_long_audio_as(struct bark_context * bctx, const struct bark_hip_audio_format * fmt, void * out, int capacity_bytes) {
     if (!bctx || bctx->long_result.chunks.empty()) return -1;
     const bark_hip_audio_format to = fmt ? *fmt : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
-    if (!sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    if (!render_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
     return guarded("bark_hip_long_audio_as", -1, [&] {
         ensure_long_join(bctx, to);
         const std::vector<uint8_t> & r = bctx->long_result.joined;
@@ -628,6 +644,14 @@ int audio_at(struct bark_context * bctx, const char * what, const std::vector<fl
     if (!fmt || pcm.empty()) return -1;
     const int n = (int) pcm.size();
     const int32_t sp = speed;
+    if (wants_flac(fmt)) {
+        if (!resample_pair_supported(24000, fmt->sample_rate) || tempo_out_len(n, speed) < 0) return -1;
+        return guarded(what, -1, [&] {
+            const float * p = pcm.data();
+            std::vector<int32_t> n_out;
+            return deliver(engine_tempo_many(bctx, &p, &n, 1, &sp, fmt->sample_rate, fmt->sample_format, n_out), out, capacity_bytes);
+        });
+    }
     const long long bytes = tempo_bytes(&n, &sp, 1, *fmt);
     if (bytes < 0 || bytes > 0x7ffffff0LL) return -1;
     if (!out || (long long) capacity_bytes < bytes) return -2 - (int) bytes;
@@ -700,7 +724,7 @@ int bark_hip_long_audio_at(struct bark_context * bctx, const struct bark_hip_aud
     if (speed_permille == 1000) return bark_hip_long_audio_as(bctx, fmt, out, capacity_bytes);
     if (!bctx || bctx->long_result.chunks.empty()) return -1;
     const bark_hip_audio_format to = fmt ? *fmt : bark_hip_audio_format{24000, BARK_HIP_SAMPLE_F32};
-    if (!sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    if (!render_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
     return guarded("bark_hip_long_audio_at", -1, [&] {
         ensure_long_join(bctx, to, speed_permille);
         const std::vector<uint8_t> & r = bctx->long_result.joined;
@@ -732,6 +756,17 @@ int audio_with(struct bark_context * bctx, const char * what, const std::vector<
     if (pcm.empty()) return -1;
     const int n = (int) pcm.size();
     const int32_t sp = how->speed_permille;
+    if (wants_flac(&how->fmt)) {
+        if (!resample_pair_supported(24000, how->fmt.sample_rate) || tempo_out_len(n, sp) < 0) return -1;
+        return guarded(what, -1, [&] {
+            const float * p = pcm.data();
+            std::vector<int32_t> n_out;
+            std::vector<bark_hip_loudness_info> inf;
+            const std::vector<uint8_t> r = engine_level_many(bctx, &p, &n, 1, &how->loudness, &sp, how->fmt.sample_rate, how->fmt.sample_format, n_out, &inf);
+            if (info) *info = inf[0];
+            return deliver(r, out, capacity_bytes);
+        });
+    }
     const long long bytes = tempo_bytes(&n, &sp, 1, how->fmt);
     if (bytes < 0 || bytes > 0x7ffffff0LL) return -1;
     if (!out || (long long) capacity_bytes < bytes) return -2 - (int) bytes;
@@ -828,7 +863,7 @@ int bark_hip_long_audio_with(struct bark_context * bctx, const struct bark_hip_a
         return r;
     }
     const bark_hip_audio_format to = how->fmt;
-    if (!sample_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
+    if (!render_format_bytes(to.sample_format) || !resample_pair_supported(24000, to.sample_rate)) return -1;
     return guarded("bark_hip_long_audio_with", -1, [&] {
         ensure_long_join(bctx, to, how->speed_permille, how->loudness);
         const bark_context::LongResult & lr = bctx->long_result;
@@ -839,6 +874,54 @@ int bark_hip_long_audio_with(struct bark_context * bctx, const struct bark_hip_a
         memcpy(out, r.data(), r.size());
         return (int) r.size();
     });
+}
+
+// ---- FLAC (rule C18f) ---------------------------------------------------------------------------------------------------------------------------------------
+int bark_hip_flac_max_bytes(int n) {
+    const long long b = flac_max_bytes(n);
+    return b < 0 || b > 0x7ffffff0LL ? -1 : (int) b;
+}
+
+namespace {
+// what the FLAC calls refuse before any work
+bool flac_call_valid(const int16_t * const * pcm, const int * n, int count, int rate) {
+    if (!pcm || !n || count < 1 || count > kResampleMaxSegments || !flac_rate_code(rate)) return false;
+    long long bound = 0;
+    for (int i = 0; i < count; i++) {
+        if (!pcm[i] || flac_max_bytes(n[i]) < 0) return false;
+        bound += flac_max_bytes(n[i]);
+    }
+    return bound <= 0x7ffffff0LL;
+}
+}  // namespace
+
+int bark_hip_flac_encode_many(struct bark_context * bctx, const int16_t * const * pcm, const int * n, int count, int rate, void * out, int capacity_bytes, int32_t * lengths) {
+    if (!bctx || !flac_call_valid(pcm, n, count, rate)) return -1;
+    return guarded("bark_hip_flac_encode_many", -1, [&] {
+        std::vector<int32_t> len;
+        const std::vector<uint8_t> r = engine_flac_encode_many(bctx, pcm, n, count, rate, len);
+        if (lengths) memcpy(lengths, len.data(), len.size() * 4);
+        return deliver(r, out, capacity_bytes);
+    });
+}
+
+int bark_hip_flac_frames(struct bark_context * bctx, const int16_t * pcm, int n, int rate, int32_t * out_Nx4, int capacity_frames) {
+    if (!bctx || !out_Nx4 || !flac_call_valid(&pcm, &n, 1, rate) || (long long) capacity_frames < ((long long) n + kFlacBlock - 1) / kFlacBlock) return -1;
+    return guarded("bark_hip_flac_frames", -1, [&] {
+        std::vector<int32_t> len, frames;
+        engine_flac_encode_many(bctx, &pcm, &n, 1, rate, len, &frames);
+        memcpy(out_Nx4, frames.data(), frames.size() * 4);
+        return (int) (frames.size() / 4);
+    });
+}
+
+double bark_hip_time_flac(struct bark_context * bctx, int count, int n_each, int iters) {
+    if (!bctx) return -1.0;
+    return guarded("bark_hip_time_flac", -1.0, [&] { return engine_time_flac(bctx, count, n_each, iters); });
+}
+double bark_hip_time_flac_launch(struct bark_context * bctx, int count, int n_each, int which, int iters) {
+    if (!bctx || which < 1 || which > 2) return -1.0;
+    return guarded("bark_hip_time_flac_launch", -1.0, [&] { return engine_time_flac(bctx, count, n_each, iters, which); });
 }
 
 double bark_hip_time_loudness(struct bark_context * bctx, int count, int n_each, int level, int iters) {

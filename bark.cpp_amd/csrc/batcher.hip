@@ -16,6 +16,8 @@
 // A request may ask for a loudness (bark_hip_batcher_submit_with, rule C17l): the same call behind the job becomes engine_level_many over all its requests with
 // levelling on or a speed other than 1000 - one measure launch and one level launch in front of the single tempo launch; a long text's parts are levelled, each
 // on its own, in front of tempo and join.  Levelling off takes the path it always took.
+// A request may ask for BARK_HIP_SAMPLE_FLAC (rule C18f): the conversion above then runs the encoder's two launches behind its format launch, once for
+// all requests of the job at that rate, and only the streams return to the host; a long text's ticket is one stream over its joined audio.
 // Job streams (bark_hip_batcher_create_ex, n_streams 1 .. 4): further workers on clones of the context (own streams, caches and graphs, the
 // same weights) serve the same queue - a lock step is a chain of ~100 small dependent kernels, so two jobs share the chip (two streams of
 // 64-slot jobs out of phase: 37.8 prompts/s against 33.2 from one, profiles/r04_staggered_jobs.txt).  Workers that start together stay in
@@ -154,7 +156,8 @@ struct bark_hip_batcher {
                         const std::vector<uint8_t> r = engine_resample_many(ctx, ptr.data(), len.data(), (int) ptr.size(), 24000, f.sample_rate, f.sample_format, n_out);
                         size_t off = 0;
                         for (size_t g = g0; g < g1; g++) {
-                            const size_t nb = (size_t) n_out[g - g0] * (size_t) sample_format_bytes(f.sample_format);
+                            const size_t nb = f.sample_format == BARK_HIP_SAMPLE_FLAC ? (size_t) ctx->flac_lengths[g - g0]      // a stream per request (rule C18f)
+                                                                                      : (size_t) n_out[g - g0] * (size_t) sample_format_bytes(f.sample_format);
                             conv[who[g]].assign(r.begin() + (long) off, r.begin() + (long) (off + nb)); conv_ok[who[g]] = 1; off += nb;
                         }
                     } catch (const std::exception & e) { fprintf(stderr, "bark_hip_batcher: conversion failed: %s\n", e.what()); }
@@ -332,7 +335,7 @@ BARK_API int64_t bark_hip_batcher_submit_with(struct bark_hip_batcher * b, const
                                               const struct bark_hip_sampling_filter * filter, const struct bark_hip_voice_prompt * voice,
                                               const struct bark_hip_audio_render * how) {
     if (!b || !text || !how || (filter && !filter_valid(*filter)) || how->speed_permille < kTempoMinSpeed || how->speed_permille > kTempoMaxSpeed) return -1;
-    if (!loudness_params_valid(how->loudness) || !sample_format_bytes(how->fmt.sample_format) || !resample_pair_supported(24000, how->fmt.sample_rate)) return -1;
+    if (!loudness_params_valid(how->loudness) || !render_format_bytes(how->fmt.sample_format) || !resample_pair_supported(24000, how->fmt.sample_rate)) return -1;
     VoicePtr v;
     if (voice) {
         try { v = engine_make_voice(b->ctx, voice); }
@@ -359,7 +362,7 @@ BARK_API int64_t bark_hip_batcher_submit_long_with(struct bark_hip_batcher * b, 
                                                    const struct bark_hip_request_params * params, const struct bark_hip_sampling_filter * filter,
                                                    const struct bark_hip_voice_prompt * voice, const struct bark_hip_audio_render * how) {
     if (!b || !text || !how || (filter && !filter_valid(*filter)) || how->speed_permille < kTempoMinSpeed || how->speed_permille > kTempoMaxSpeed) return -1;
-    if (!loudness_params_valid(how->loudness) || !sample_format_bytes(how->fmt.sample_format) || !resample_pair_supported(24000, how->fmt.sample_rate)) return -1;
+    if (!loudness_params_valid(how->loudness) || !render_format_bytes(how->fmt.sample_format) || !resample_pair_supported(24000, how->fmt.sample_rate)) return -1;
     const bark_hip_long_params lp = long_params ? *long_params : bark_hip_long_params{0, 0, join_default_params()};
     if (lp.chain != 0 || !join_params_valid(lp.join)) return -1;
     VoicePtr v;

@@ -1194,4 +1194,311 @@ void launch_loudness_level(hipStream_t s, const LoudnessArgs & a) {
     hipLaunchKernelGGL(loudness_level_kernel, dim3((unsigned) a.B), dim3(kLoudLevelThreads), 0, s, a);
 }
 
+// ---- FLAC (rule C18f) ------------------------------------------------------------------------------------------------------------------------------------
+int flac_rate_code(int rate) {
+    switch (rate) {
+        case 8000: return 4; case 12000: return 12; case 16000: return 5; case 22050: return 6; case 24000: return 7; case 32000: return 8; case 44100: return 9;
+        case 48000: return 10; default: return 0;
+    }
+}
+
+constexpr int kFlacThreads = 256, kFlacWords = kFlacFrameStride / 4;
+static_assert(kFlacBlock % kFlacThreads == 0 && kFlacFrameStride % 16 == 0 && (kFlacThreads >> kFlacMaxPartitionOrder) >= 1, "whole samples per lane, aligned slots");
+
+// v (nb bits, 1 .. 32, v < 2^nb) at bit `pos` of a big-endian bit string kept in zeroed LDS words.  The bits of different codes are disjoint, so an add is an
+// or: ds_add_u32 without a return value.  A code's neighbours belong to other lanes, so the two words it may touch are shared: hence the atomic.
+__device__ __forceinline__ void flac_put(unsigned * w, unsigned pos, unsigned v, int nb) {
+    const unsigned i = pos >> 5;
+    const int room = 32 - (int) (pos & 31u);
+    if (nb <= room) atomicAdd(w + i, v << (room - nb));
+    else { atomicAdd(w + i, v >> (nb - room)); atomicAdd(w + i + 1, v << (32 - (nb - room))); }
+}
+__device__ __forceinline__ unsigned flac_byte(const unsigned * w, int j) { return (w[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu; }
+// a b mod x^16 + x^15 + x^2 + 1 over GF(2), a and b reduced
+__device__ __forceinline__ unsigned flac_mulmod16(unsigned a, unsigned b) {
+    unsigned r = 0;
+    for (int bit = 15; bit >= 0; bit--) {
+        r <<= 1;
+        if (r & 0x10000u) r ^= 0x18005u;
+        if ((b >> bit) & 1u) r ^= a;
+    }
+    return r;
+}
+// the FIXED predictor's residual of sample i (i >= order)
+__device__ __forceinline__ int flac_residual(const short * s, int i, int order) {
+    switch (order) {
+        case 0: return s[i];
+        case 1: return s[i] - s[i - 1];
+        case 2: return s[i] - 2 * s[i - 1] + s[i - 2];
+        case 3: return s[i] - 3 * s[i - 1] + 3 * s[i - 2] - s[i - 3];
+        default: return s[i] - 4 * s[i - 1] + 6 * s[i - 2] - 4 * s[i - 3] + s[i - 4];
+    }
+}
+// what a frame's choices are, for the lanes that code its samples
+struct FlacPlan { int n, order, po, code; };
+// Sample i's code: its bit length, and (emit) the bits at `pos`.  FIXED: a warm-up sample in 16 bits, or the residual - behind the residual header and the
+// partition's parameter where it is the first of its partition - as q zero bits (skipped: the words are zero), a one and k bits, or raw in the escape width.
+template <bool emit>
+__device__ __forceinline__ unsigned flac_code(const FlacPlan & p, int i, const short * smp, const unsigned * zz, const unsigned * node_k, const unsigned * node_w,
+                                              unsigned * w, unsigned pos) {
+    if (p.code == 1 || i < p.order) {
+        if (emit) flac_put(w, pos, (unsigned) (unsigned short) smp[i], 16);
+        return 16;
+    }
+    const int psz = p.n >> p.po, part = i / psz, node = (1 << p.po) - 1 + part;
+    const unsigned k = node_k[node], wd = node_w[node];
+    unsigned len = 0;
+    if (i == (part == 0 ? p.order : part * psz)) {
+        const int hb = part == 0 ? 10 : 4;                                // coding method 00 and the partition order in front of the first parameter
+        if (emit) flac_put(w, pos, ((unsigned) (part == 0 ? p.po : 0) << 4) | k, hb);
+        len = (unsigned) hb;
+        if (k == 15u) { if (emit) flac_put(w, pos + len, wd, 5); len += 5; }
+    }
+    const unsigned u = zz[i];
+    if (k == 15u) {
+        if (emit && wd) flac_put(w, pos + len, ((u >> 1) ^ (0u - (u & 1u))) & (0xFFFFFFFFu >> (32 - wd)), (int) wd);
+        return len + wd;
+    }
+    const unsigned q = u >> k;
+    if (emit) flac_put(w, pos + len + q, (1u << k) | (u & ((1u << k) - 1u)), (int) k + 1);
+    return len + q + k + 1;
+}
+
+__global__ __launch_bounds__(kFlacThreads) void flac_frames_kernel(const FlacArgs a) {
+    __shared__ short smp[kFlacBlock];
+    __shared__ unsigned zz[kFlacBlock];                                  // the zigzag residuals of the chosen order
+    __shared__ unsigned words[kFlacWords];                               // the frame, big-endian bit string
+    __shared__ unsigned sums[6];                                         // the five absolute sums, and whether two samples differ
+    __shared__ unsigned part_sum[1 << kFlacMaxPartitionOrder][16];       // per finest partition: sum of u >> k for k 0 .. 14, and the largest u
+    __shared__ unsigned node_bits[32], node_k[32], node_w[32];           // the partition tree: node (1 << po) - 1 + q is partition q at order po
+    __shared__ unsigned scan[kFlacThreads];
+    __shared__ int plan_sh[2];
+    constexpr int S = kResampleMaxSegments + 1;
+    const int t = (int) threadIdx.x, g = (int) blockIdx.x;
+    int r = 0;
+    while (g >= a.seg[2 * S + r + 1]) r++;                               // at most 64 steps
+    const int f = g - a.seg[2 * S + r];
+    const int n = min(kFlacBlock, a.seg[r] - f * kFlacBlock);
+    const short * x = a.x + a.seg[S + r] + (long long) f * kFlacBlock;
+    for (int i = t; i < n; i += kFlacThreads) smp[i] = x[i];
+    for (int i = t; i < kFlacWords; i += kFlacThreads) words[i] = 0u;
+    if (t < 6) sums[t] = 0u;
+    if (t < 16 << kFlacMaxPartitionOrder) part_sum[t >> 4][t & 15] = 0u;
+    __syncthreads();
+    // the five absolute sums: |r4| <= 2^19 and 4096 of them stay below 2^32
+    {
+        unsigned acc[5] = {0u, 0u, 0u, 0u, 0u}, differ = 0u;
+        for (int i = t; i < n; i += kFlacThreads) {
+            differ |= (unsigned) (smp[i] != smp[0]);
+#pragma unroll
+            for (int o = 0; o < 5; o++) if (i >= o) { const int e = flac_residual(smp, i, o); acc[o] += (unsigned) (e < 0 ? -e : e); }
+        }
+#pragma unroll
+        for (int o = 0; o < 5; o++) atomicAdd(sums + o, acc[o]);
+        if (differ) atomicMax(sums + 5, 1u);
+    }
+    __syncthreads();
+    // the frame header: the same for every lane, written by the first
+    unsigned char head[12];
+    int hn = 0;
+    head[hn++] = 0xFF; head[hn++] = 0xF8;
+    head[hn++] = (unsigned char) (((n == kFlacBlock ? 12 : 7) << 4) | a.rate_code);
+    head[hn++] = 0x08;
+    if (f < 0x80) head[hn++] = (unsigned char) f;
+    else if (f < 0x800) { head[hn++] = (unsigned char) (0xC0 | (f >> 6)); head[hn++] = (unsigned char) (0x80 | (f & 0x3F)); }
+    else { head[hn++] = (unsigned char) (0xE0 | (f >> 12)); head[hn++] = (unsigned char) (0x80 | ((f >> 6) & 0x3F)); head[hn++] = (unsigned char) (0x80 | (f & 0x3F)); }
+    if (n != kFlacBlock) { head[hn++] = (unsigned char) ((n - 1) >> 8); head[hn++] = (unsigned char) ((n - 1) & 0xFF); }
+    if (a.rate_code == 12) head[hn++] = (unsigned char) a.rate_khz;
+    {
+        unsigned c = 0;                                                  // CRC-8, x^8 + x^2 + x + 1: ten bytes at most, so the serial form
+        for (int j = 0; j < hn; j++) { c ^= head[j]; for (int b = 0; b < 8; b++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) & 0xFFu : (c << 1) & 0xFFu; }
+        head[hn++] = (unsigned char) c;
+    }
+    if (t == 0) for (int j = 0; j < hn; j++) flac_put(words, 8u * (unsigned) j, head[j], 8);
+    const unsigned body_at = 8u * (unsigned) hn + 8u;                    // behind the subframe header
+    FlacPlan p{n, 0, 0, 0};
+    unsigned total_bits = body_at;
+    if (sums[5] == 0u) {                                                 // CONSTANT
+        if (t == 0) flac_put(words, body_at, (unsigned) (unsigned short) smp[0], 16);      // (the subframe header is eight zero bits)
+        total_bits += 16u;
+    } else {
+        const int omax = min(4, n - 1);
+        for (int o = 1; o <= omax; o++) if (sums[o] < sums[p.order]) p.order = o;
+        for (int i = t; i < n; i += kFlacThreads) if (i >= p.order) { const int e = flac_residual(smp, i, p.order); zz[i] = ((unsigned) e << 1) ^ (unsigned) (e >> 31); }
+        int P = 0;                                                       // the finest partition order the block size and the order allow
+        while (P < kFlacMaxPartitionOrder && n % (2 << P) == 0 && (n >> (P + 1)) > p.order) P++;
+        __syncthreads();
+        {   // sum of u >> k over every finest partition: kFlacThreads >> P lanes each
+            const int T = kFlacThreads >> P, part = t / T, l = t % T, psz = n >> P;
+            unsigned acc[15], mx = 0u;
+#pragma unroll
+            for (int k = 0; k < 15; k++) acc[k] = 0u;
+            for (int i = part * psz + l; i < (part + 1) * psz; i += T) if (i >= p.order) {
+                const unsigned u = zz[i];
+                mx = max(mx, u);
+#pragma unroll
+                for (int k = 0; k < 15; k++) acc[k] += u >> k;           // the chosen order's sum of u is at most 2^29: no overflow
+            }
+#pragma unroll
+            for (int k = 0; k < 15; k++) atomicAdd(&part_sum[part][k], acc[k]);
+            atomicMax(&part_sum[part][15], mx);
+        }
+        __syncthreads();
+        if (t < (2 << P) - 1) {                                          // one lane per node of the partition tree
+            int po = 0;
+            while ((2 << po) - 1 <= t) po++;
+            const int q = t - ((1 << po) - 1), span = 1 << (P - po);
+            const unsigned cnt = (unsigned) ((n >> po) - (q == 0 ? p.order : 0));
+            unsigned best_k = 0u, best = 0xFFFFFFFFu, mx = 0u;
+            for (int j = q * span; j < (q + 1) * span; j++) mx = max(mx, part_sum[j][15]);
+            for (int k = 0; k <= kFlacMaxRice; k++) {
+                unsigned sq = 0u;
+                for (int j = q * span; j < (q + 1) * span; j++) sq += part_sum[j][k];
+                const unsigned b = 4u + cnt * (unsigned) (k + 1) + sq;
+                if (b < best) { best = b; best_k = (unsigned) k; }
+            }
+            const unsigned wd = mx ? 32u - (unsigned) __builtin_clz(mx) : 0u;
+            const unsigned esc = 9u + cnt * wd;
+            if (esc < best) { best = esc; best_k = 15u; }
+            node_bits[t] = best; node_k[t] = best_k; node_w[t] = wd;
+        }
+        __syncthreads();
+        if (t == 0) {
+            unsigned best = 0xFFFFFFFFu;
+            int best_po = 0;
+            for (int po = 0; po <= P; po++) {
+                unsigned tot = 0u;
+                for (int q = 0; q < 1 << po; q++) tot += node_bits[(1 << po) - 1 + q];
+                if (tot < best) { best = tot; best_po = po; }
+            }
+            const bool fixed = 8u + 16u * (unsigned) p.order + 6u + best < 8u + 16u * (unsigned) n;
+            plan_sh[0] = fixed ? 8 + p.order : 1; plan_sh[1] = fixed ? best_po : 0;
+            flac_put(words, body_at - 8u, (unsigned) plan_sh[0] << 1, 8);
+        }
+        __syncthreads();
+        p.code = plan_sh[0]; p.po = plan_sh[1];
+        // every lane codes ceil(n / 256) consecutive samples: their bit lengths, an exclusive scan over the lanes, then the bits
+        const int spt = (n + kFlacThreads - 1) / kFlacThreads, i0 = min(n, t * spt), i1 = min(n, i0 + spt);
+        unsigned mine = 0u;
+        for (int i = i0; i < i1; i++) mine += flac_code<false>(p, i, smp, zz, node_k, node_w, words, 0u);
+        scan[t] = mine;
+        __syncthreads();
+        for (int d = 1; d < kFlacThreads; d <<= 1) {
+            const unsigned add = t >= d ? scan[t - d] : 0u;
+            __syncthreads();
+            scan[t] += add;
+            __syncthreads();
+        }
+        unsigned pos = body_at + scan[t] - mine;
+        for (int i = i0; i < i1; i++) pos += flac_code<true>(p, i, smp, zz, node_k, node_w, words, pos);
+        total_bits = body_at + scan[kFlacThreads - 1];
+    }
+    __syncthreads();
+    // CRC-16 (x^16 + x^15 + x^2 + 1) of the frame's bytes: every lane takes a run of bytes, bit by bit, and moves its remainder behind the bytes that
+    // follow by a multiplication with x^(8 m) - the remainders then add up
+    const int nbytes = (int) ((total_bits + 7u) >> 3);
+    {
+        const int L = (nbytes + kFlacThreads - 1) / kFlacThreads, b0 = min(nbytes, t * L), b1 = min(nbytes, b0 + L);
+        unsigned c = 0u;
+        for (int j = b0; j < b1; j++) {
+            c ^= flac_byte(words, j) << 8;
+            for (int b = 0; b < 8; b++) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) & 0xFFFFu : (c << 1) & 0xFFFFu;
+        }
+        unsigned pw = 1u, base = 2u;                                     // x^(8 m), m bytes behind this lane's run
+        for (unsigned e = 8u * (unsigned) (nbytes - b1); e && c; e >>= 1) { if (e & 1u) pw = flac_mulmod16(pw, base); base = flac_mulmod16(base, base); }
+        scan[t] = c ? flac_mulmod16(c, pw) : 0u;
+    }
+    __syncthreads();
+    for (int d = kFlacThreads / 2; d >= 1; d >>= 1) {
+        if (t < d) scan[t] ^= scan[t + d];
+        __syncthreads();
+    }
+    const unsigned crc = scan[0];
+    if (t == 0) flac_put(words, 8u * (unsigned) nbytes, crc, 16);
+    __syncthreads();
+    const int len = nbytes + 2;
+    unsigned * slot = a.scratch + (size_t) g * kFlacWords;
+    for (int i = t; i < (len + 3) / 4; i += kFlacThreads) slot[i] = __builtin_bswap32(words[i]);
+    if (t == 0) {
+        a.flen[g] = len;
+        a.finfo[4 * g] = p.code; a.finfo[4 * g + 1] = p.po; a.finfo[4 * g + 2] = len; a.finfo[4 * g + 3] = (int) crc;
+    }
+}
+
+// One workgroup per (result, y of `split`): all of them scan the result's frame lengths chunk by chunk (a chunk is one length per lane, the carry goes from
+// chunk to chunk), every y-th frame is copied by the workgroup y: destination words that the frame owns whole are gathered from two aligned source words and
+// written as one dword, the up to three bytes at either end byte by byte (the neighbouring frame writes the other bytes of that word).
+constexpr int kFlacPackThreads = 256;
+__global__ __launch_bounds__(kFlacPackThreads) void flac_pack_kernel(const FlacArgs a) {
+    __shared__ unsigned off_sh[kFlacPackThreads], len_sh[kFlacPackThreads];
+    __shared__ unsigned stat[3];                                         // bytes of the results in front, largest frame, 0xFFFFFFFF - smallest frame
+    constexpr int S = kResampleMaxSegments + 1;
+    const int t = (int) threadIdx.x, r = (int) blockIdx.x, y = (int) blockIdx.y, Y = (int) gridDim.y;
+    const int f0 = a.seg[2 * S + r], f1 = a.seg[2 * S + r + 1];
+    if (t < 3) stat[t] = 0u;
+    __syncthreads();
+    {
+        unsigned before = 0u;
+        for (int i = t; i < f0; i += kFlacPackThreads) before += (unsigned) a.flen[i];
+        atomicAdd(stat, before);
+    }
+    __syncthreads();
+    unsigned carry = stat[0];
+    const unsigned char * src8 = reinterpret_cast<const unsigned char *>(a.scratch);
+    for (int c0 = f0; c0 < f1; c0 += kFlacPackThreads) {
+        const unsigned mine = c0 + t < f1 ? (unsigned) a.flen[c0 + t] : 0u;
+        if (mine) { atomicMax(stat + 1, mine); atomicMax(stat + 2, 0xFFFFFFFFu - mine); }
+        off_sh[t] = mine; len_sh[t] = mine;
+        __syncthreads();
+        for (int d = 1; d < kFlacPackThreads; d <<= 1) {
+            const unsigned add = t >= d ? off_sh[t - d] : 0u;
+            __syncthreads();
+            off_sh[t] += add;
+            __syncthreads();
+        }
+        const int in_chunk = min(kFlacPackThreads, f1 - c0);
+        for (int j = 0; j < in_chunk; j++) {
+            if ((c0 + j - f0) % Y != y) continue;
+            const unsigned len = len_sh[j], D = carry + off_sh[j] - len;
+            const size_t src = (size_t) (c0 + j) * kFlacFrameStride;
+            const unsigned w0 = D >> 2, nw = ((D + len + 3u) >> 2) - w0;
+            for (unsigned q = (unsigned) t; q < nw; q += kFlacPackThreads) {
+                const unsigned wb = (w0 + q) * 4u, lo = max(wb, D), hi = min(wb + 4u, D + len);
+                if (hi - lo == 4u) {
+                    const unsigned so = lo - D, sh = 8u * (so & 3u);
+                    const unsigned * sw = a.scratch + (src >> 2) + (so >> 2);
+                    const unsigned v = sh ? (sw[0] >> sh) | (sw[1] << (32u - sh)) : sw[0];
+                    reinterpret_cast<unsigned *>(a.out)[w0 + q] = v;
+                } else {
+                    for (unsigned b = lo; b < hi; b++) a.out[b] = src8[src + (b - D)];
+                }
+            }
+        }
+        carry += off_sh[kFlacPackThreads - 1];
+        __syncthreads();                                                 // the tables are rewritten by the next chunk
+    }
+    if (y == 0 && t == 0) {
+        a.tot[r] = (int) (carry - stat[0]);
+        a.tot[kResampleMaxSegments + r] = (int) (0xFFFFFFFFu - stat[2]);
+        a.tot[2 * kResampleMaxSegments + r] = (int) stat[1];
+    }
+}
+
+void launch_flac_frames(hipStream_t s, const FlacArgs & a, const int (&h)[3][kResampleMaxSegments + 1]) {
+    bool ok = a.x && a.seg && a.scratch && a.flen && a.finfo && a.B >= 1 && a.B <= kResampleMaxSegments && h[1][0] == 0 && h[2][0] == 0 && a.rate_code >= 4 &&
+              a.rate_code <= 12 && a.rate_code != 11 && (a.rate_code != 12 || a.rate_khz == 12);
+    for (int i = 0; ok && i < a.B; i++) {
+        const int n = h[0][i];
+        ok = n >= 1 && n <= kFlacMaxSamples && h[1][i + 1] - h[1][i] == n && h[1][i + 1] > 0 && h[2][i + 1] == h[2][i] + (n + kFlacBlock - 1) / kFlacBlock;
+    }
+    if (!ok) kernel_fail("bark-hip: the FLAC kernel takes 1 .. %d results of 1 .. %d samples, a supported rate and a table of prefix sums that follows rule C18f (got B %d)",
+                         kResampleMaxSegments, kFlacMaxSamples, a.B);
+    hipLaunchKernelGGL(flac_frames_kernel, dim3((unsigned) h[2][a.B]), dim3(kFlacThreads), 0, s, a);
+}
+void launch_flac_pack(hipStream_t s, const FlacArgs & a, int split) {
+    if (!a.seg || !a.scratch || !a.flen || !a.out || !a.tot || a.B < 1 || a.B > kResampleMaxSegments || split < 1 || split > 64)
+        kernel_fail("bark-hip: the FLAC pack kernel takes 1 .. %d results, their frames and lengths and a split of 1 .. 64 (got B %d, split %d)", kResampleMaxSegments, a.B, split);
+    hipLaunchKernelGGL(flac_pack_kernel, dim3((unsigned) a.B, (unsigned) split), dim3(kFlacPackThreads), 0, s, a);
+}
+
 }  // namespace barkhip

@@ -250,6 +250,11 @@ struct bark_context : bark_context_memory {
     // [5][kResampleMaxSegments + 1], the z table, and one peak, request and info record per segment (the first three grown on demand)
     barkhip::DevBuf<float> lv_in; barkhip::DevBuf<int> lv_seg; barkhip::DevBuf<double> lv_z; barkhip::DevBuf<unsigned> lv_peak;
     barkhip::DevBuf<barkhip::LoudnessReq> lv_req; barkhip::DevBuf<barkhip::LoudnessInfo> lv_info;
+    // FLAC (C18f): caller samples back to back (the routes encode where the format launch left its s16: rp_out), the segment table
+    // [3][kResampleMaxSegments + 1], one slot of kFlacFrameStride bytes, a length and four ints per frame, the packed frames and [3][64] totals (grown on
+    // demand); flac_lengths: the byte length of every stream the last conversion to BARK_HIP_SAMPLE_FLAC returned, in segment order
+    barkhip::DevBuf<int16_t> fl_in; barkhip::DevBuf<int> fl_seg, fl_len, fl_info, fl_tot; barkhip::DevBuf<unsigned> fl_scratch; barkhip::DevBuf<uint8_t> fl_out;
+    std::vector<int32_t> flac_lengths;
     struct CodecGraph { barkhip::GraphExec exec; std::vector<int> T; const float * buf = nullptr; float * out = nullptr; int tmul = 0; } codec_graph;   // conv stack behind the LSTM
 
     // batched decode (several utterances in lock step on this context, bark_hip_generate_batch): per-slot KV caches and decode rows,
@@ -377,6 +382,11 @@ const ResampleTable * resample_pair_table(int rate_in, int rate_out);
 bool resample_pair_supported(int rate_in, int rate_out);
 long long resample_out_len(long long n, int rate_in, int rate_out);
 inline int sample_format_bytes(int fmt) { return fmt == BARK_HIP_SAMPLE_F32 ? 4 : fmt == BARK_HIP_SAMPLE_S16 ? 2 : fmt == BARK_HIP_SAMPLE_MULAW ? 1 : 0; }
+// BARK_HIP_SAMPLE_FLAC (rule C18f) is a container over the s16 samples: the format launches write pcm_format(fmt), and the calls that render a held result
+// (engine_resample_many, _tempo_many, _level_many, _join_many) then encode where those samples lie and return the streams back to back, their byte lengths
+// in ctx->flac_lengths.  sample_format_bytes stays 0 for it: a call that has not been taught the container refuses it.
+inline int pcm_format(int fmt) { return fmt == BARK_HIP_SAMPLE_FLAC ? BARK_HIP_SAMPLE_S16 : fmt; }
+inline int render_format_bytes(int fmt) { return sample_format_bytes(pcm_format(fmt)); }
 // count <= 64 segments (1 .. 1 310 720 finite samples each) in ONE launch -> their results back to back as bytes of the format, n_out[i] samples each;
 // bit-identical to count single calls.  Throws on a bad count / length / sample / pair / format.
 std::vector<uint8_t> engine_resample_many(bark_context * ctx, const float * const * pcm, const int * n, int count, int rate_in, int rate_out, int fmt,
@@ -415,6 +425,16 @@ std::vector<bark_hip_loudness_info> engine_loudness_many(bark_context * ctx, con
                                                          std::vector<double> * z = nullptr);
 std::vector<uint8_t> engine_level_many(bark_context * ctx, const float * const * pcm, const int * n, int count, const bark_hip_loudness_params * params,
                                        const int32_t * speed_permille, int rate_out, int fmt, std::vector<int32_t> & n_out, std::vector<bark_hip_loudness_info> * info = nullptr);
+// FLAC (C18f): count <= 64 results of 1 .. 2^26 mono s16 samples at one of the eight rates -> their streams (marker, STREAMINFO, frames) back to back, in the
+// two launches whatever the count; lengths: bytes per stream; frames (may be null): {subframe code, partition order, byte length, CRC-16} per frame, the
+// results' frames back to back.  Only the packed frames, the totals and (if asked for) the frame records return to the host, which writes the 42 bytes in
+// front of every stream.  Throws on a refusal.  flac_max_bytes: 42 + 14 ceil(n / 4096) + 2 n, or -1 for n outside 1 .. 2^26.
+long long flac_max_bytes(long long n);
+std::vector<uint8_t> engine_flac_encode_many(bark_context * ctx, const int16_t * const * pcm, const int * n, int count, int rate, std::vector<int32_t> & lengths,
+                                             std::vector<int32_t> * frames = nullptr);
+// device time of ONE pair of launches (which 0), ONE frames launch (1) or ONE pack launch (2) over `count` results of n_each samples of a synthetic voiced
+// signal at 24 kHz
+double engine_time_flac(bark_context * ctx, int count, int n_each, int iters, int which = 0);
 // device time of ONE loudness_hops launch (level false) or ONE loudness_level launch with its scaled copy (level true) over `count` segments of n_each samples
 double engine_time_loudness(bark_context * ctx, int count, int n_each, int iters, bool level);
 // Long-form text (C15s + C15j): split, run the chunks (chain 0: ONE lock-step job, chunk i with seed rp.seed + i; chain 1: one job per chunk, chunk

@@ -591,6 +591,8 @@ const float * device_taps(bark_context * c, int rate_in, int rate_out, const Res
     c->rp_taps[{rate_in, rate_out}] = d;
     return d;
 }
+// FLAC (rule C18f): the device half of the encoder, defined with engine_flac_encode_many below
+std::vector<uint8_t> flac_staged(bark_context * c, const int16_t * dx, const int * n, int count, int rate, std::vector<int32_t> & lengths, std::vector<int32_t> * frames);
 void ensure_resample_buffers(bark_context * c, size_t in_elems, size_t out_bytes) {
     c->rp_in.reserve(c, in_elems);
     c->rp_out.reserve(c, out_bytes);
@@ -612,13 +614,17 @@ int fill_segment_table(int (&seg)[5][kResampleMaxSegments + 1], const int * n, i
 void convert_staged(bark_context * c, const float * dx, const int (&seg)[5][kResampleMaxSegments + 1], int n_tiles, int count, size_t total_in,
                     const ResampleTable * t, int rate_in, int rate_out, int fmt, std::vector<uint8_t> & out) {
     hipStream_t s = c->stream;
-    if (!t) launch_sample_format(s, dx, c->rp_out.p, total_in, fmt);
+    if (!t) launch_sample_format(s, dx, c->rp_out.p, total_in, pcm_format(fmt));
     else {
         HIP_OK(hipMemcpyAsync(c->rp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
         ResamplePairArgs a;
         a.x = dx; a.y = c->rp_out.p; a.taps = device_taps(c, rate_in, rate_out, *t); a.seg = c->rp_seg.p;
-        a.B = count; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = fmt;
+        a.B = count; a.L = t->L; a.M = t->M; a.half = t->half; a.fmt = pcm_format(fmt);
         launch_resample_pair(s, a, n_tiles);
+    }
+    if (fmt == BARK_HIP_SAMPLE_FLAC) {                           // the s16 samples stay where they are: only the streams return (the call synchronises)
+        out = flac_staged(c, reinterpret_cast<const int16_t *>(c->rp_out.p), seg[2], count, rate_out, c->flac_lengths, nullptr);
+        return;
     }
     HIP_OK(hipMemcpyAsync(out.data(), c->rp_out.p, out.size(), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));                             // seg is a stack object of the caller
@@ -630,8 +636,8 @@ std::vector<uint8_t> engine_resample_many(bark_context * c, const float * const 
     HIP_OK(hipSetDevice(c->device));
     if (!pcm || !n || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("resampler: 1 .. 64 segments in one call");
     if (!resample_pair_supported(rate_in, rate_out)) throw std::runtime_error("resampler: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000, with 24000 on at least one side");
-    const int bytes_per = sample_format_bytes(fmt);
-    if (!bytes_per) throw std::runtime_error("resampler: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    const int bytes_per = render_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("resampler: the sample formats are f32 (0), s16 (1), mu-law (2) and FLAC (3)");
     size_t total_in = 0;
     for (int i = 0; i < count; i++) {
         if (!pcm[i] || n[i] < 1 || n[i] > kResampleMaxSamples) throw std::runtime_error("resampler: a segment needs 1 .. 1 310 720 samples");
@@ -734,7 +740,7 @@ JoinResampleArgs join_args(bark_context * c, const JoinPlan & pl, const bark_hip
     const ResampleTable * t = resample_pair_table(24000, rate_out);
     a.x = c->rp_in.p; a.y = c->rp_out.p; a.pos = c->jn_tab.p + kJoinPosAt; a.fade = device_fade(c, p.fade_samples);
     a.taps = t ? device_taps(c, 24000, rate_out, *t) : nullptr;
-    a.R = pl.R; a.F = p.fade_samples; a.N = (int) pl.N; a.n_out = (int) resample_out_len(pl.N, 24000, rate_out); a.fmt = fmt;
+    a.R = pl.R; a.F = p.fade_samples; a.N = (int) pl.N; a.n_out = (int) resample_out_len(pl.N, 24000, rate_out); a.fmt = pcm_format(fmt);
     if (t) { a.L = t->L; a.M = t->M; a.half = t->half; }
     return a;
 }
@@ -752,8 +758,8 @@ std::vector<uint8_t> join_impl(bark_context * c, const float * const * pcm, cons
     if (!pcm || !n || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("join: 1 .. 64 segments in one call");
     if (!join_params_valid(p)) throw std::runtime_error("join: gap_samples >= 0, fade_samples 0 .. 24000, trim_threshold >= 0 and finite, trim_pad_frames >= 0");
     if (!resample_pair_supported(24000, rate_out)) throw std::runtime_error("join: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
-    const int bytes_per = sample_format_bytes(fmt);
-    if (!bytes_per) throw std::runtime_error("join: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    const int bytes_per = render_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("join: the sample formats are f32 (0), s16 (1), mu-law (2) and FLAC (3)");
     long long total_in = 0;
     for (int i = 0; i < count; i++) {
         if (!pcm[i] || n[i] < 1 || n[i] > kResampleMaxSamples) throw std::runtime_error("join: a segment needs 1 .. 1 310 720 samples");
@@ -790,6 +796,10 @@ std::vector<uint8_t> join_impl(bark_context * c, const float * const * pcm, cons
     c->rp_out.reserve(c, out.size());
     HIP_OK(hipMemcpyAsync(c->jn_tab.p + kJoinPosAt, pl.pos, sizeof(pl.pos), hipMemcpyHostToDevice, s));
     launch_join_resample(s, join_args(c, pl, p, rate_out, fmt));
+    if (fmt == BARK_HIP_SAMPLE_FLAC) {                           // one stream over the joined signal
+        const int n_joined = (int) n_out;
+        return flac_staged(c, reinterpret_cast<const int16_t *>(c->rp_out.p), &n_joined, 1, rate_out, c->flac_lengths, nullptr);
+    }
     HIP_OK(hipMemcpyAsync(out.data(), c->rp_out.p, out.size(), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     return out;
@@ -882,8 +892,8 @@ std::vector<uint8_t> engine_tempo_many(bark_context * c, const float * const * p
     HIP_OK(hipSetDevice(c->device));
     if (!pcm || !n || !speed || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("tempo: 1 .. 64 segments in one call");
     if (!resample_pair_supported(24000, rate_out)) throw std::runtime_error("tempo: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
-    const int bytes_per = sample_format_bytes(fmt);
-    if (!bytes_per) throw std::runtime_error("tempo: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    const int bytes_per = render_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("tempo: the sample formats are f32 (0), s16 (1), mu-law (2) and FLAC (3)");
     bool all_identity = true;
     for (int i = 0; i < count; i++) {
         if (!pcm[i] || tempo_out_len(n[i], speed[i]) < 0) throw std::runtime_error("tempo: a segment needs 1 .. 1 310 720 samples and a speed of 500 .. 2000 per mille");
@@ -902,7 +912,7 @@ namespace {
 // the device half of engine_tempo_many: the segments lie back to back in tp_in
 std::vector<uint8_t> tempo_staged(bark_context * c, const TempoArgs & a, const int (&seg)[6][kResampleMaxSegments + 1], int count, int rate_out, int fmt,
                                   std::vector<int32_t> & n_out, std::vector<int32_t> * positions) {
-    const int bytes_per = sample_format_bytes(fmt), n_frames = seg[5][count];
+    const int bytes_per = render_format_bytes(fmt), n_frames = seg[5][count];
     hipStream_t s = c->stream;
     HIP_OK(hipMemcpyAsync(c->tp_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
     launch_tempo(s, a, seg);
@@ -1014,8 +1024,8 @@ std::vector<uint8_t> engine_level_many(bark_context * c, const float * const * p
     if (!params || !speed) throw std::runtime_error("level: a request and a speed per segment");
     loudness_check(pcm, n, count, params);
     if (!resample_pair_supported(24000, rate_out)) throw std::runtime_error("level: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
-    const int bytes_per = sample_format_bytes(fmt);
-    if (!bytes_per) throw std::runtime_error("level: the sample formats are f32 (0), s16 (1) and mu-law (2)");
+    const int bytes_per = render_format_bytes(fmt);
+    if (!bytes_per) throw std::runtime_error("level: the sample formats are f32 (0), s16 (1), mu-law (2) and FLAC (3)");
     bool all_off = true, all_identity = true;
     for (int i = 0; i < count; i++) {
         if (tempo_out_len(n[i], speed[i]) < 0) throw std::runtime_error("level: a speed of 500 .. 2000 per mille");
@@ -1076,6 +1086,135 @@ double engine_time_loudness(bark_context * c, int count, int n_each, int iters, 
     iters = std::max(1, iters);
     launch_loudness_hops(s, a, seg);                             // the level launch reads what a hops launch wrote
     auto one = [&] { if (level) launch_loudness_level(s, a); else launch_loudness_hops(s, a, seg); };
+    for (int i = 0; i < 2; i++) one();
+    return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) one(); }) / iters;
+}
+
+// ---- FLAC (rule C18f) --------------------------------------------------------------------------------------------------------------------------------------
+long long flac_max_bytes(long long n) {
+    if (n < 1 || n > kFlacMaxSamples) return -1;
+    return kFlacStreamHeader + kFlacFrameOverhead * ((n + kFlacBlock - 1) / kFlacBlock) + 2 * n;
+}
+namespace {
+// the segment table of launch_flac_frames; returns the frame count, or -1 where the samples or the frames would not fit the kernels' int offsets
+long long fill_flac_table(int (&seg)[3][kResampleMaxSegments + 1], const int * n, int count) {
+    memset(seg, 0, sizeof(seg));
+    long long samples = 0, frames = 0;
+    for (int i = 0; i < count; i++) {
+        samples += n[i]; frames += (n[i] + kFlacBlock - 1) / kFlacBlock;
+        if (samples > (1LL << 30)) return -1;
+        seg[0][i] = n[i]; seg[1][i + 1] = (int) samples; seg[2][i + 1] = (int) frames;
+    }
+    return frames;
+}
+// the marker and the STREAMINFO block, marked last: block sizes 4096 and 4096, the smallest and the largest frame, rate, one channel, 16 bits, the sample
+// count, and an MD5 field of zeros (not computed)
+void flac_stream_header(uint8_t * h, long long n, int rate, int min_frame, int max_frame) {
+    memset(h, 0, kFlacStreamHeader);
+    memcpy(h, "fLaC", 4);
+    h[4] = 0x80; h[7] = 34;
+    h[8] = kFlacBlock >> 8; h[9] = kFlacBlock & 0xFF; h[10] = kFlacBlock >> 8; h[11] = kFlacBlock & 0xFF;
+    h[12] = (uint8_t) (min_frame >> 16); h[13] = (uint8_t) (min_frame >> 8); h[14] = (uint8_t) min_frame;
+    h[15] = (uint8_t) (max_frame >> 16); h[16] = (uint8_t) (max_frame >> 8); h[17] = (uint8_t) max_frame;
+    const uint64_t v = ((uint64_t) rate << 44) | ((uint64_t) 15 << 36) | (uint64_t) n;        // 20 bits of rate, channels - 1 = 0, bits - 1 = 15, 36 bits of samples
+    for (int i = 0; i < 8; i++) h[18 + i] = (uint8_t) (v >> (56 - 8 * i));
+}
+FlacArgs flac_args(bark_context * c, const int16_t * dx, int count, long long frames, long long samples, int rate) {
+    c->fl_seg.reserve(c, 3 * (kResampleMaxSegments + 1));
+    c->fl_scratch.reserve(c, (size_t) frames * (kFlacFrameStride / 4) + 4);       // the pack kernel reads whole words: one beyond the last frame's bytes
+    c->fl_len.reserve(c, (size_t) frames);
+    c->fl_info.reserve(c, (size_t) frames * 4);
+    c->fl_tot.reserve(c, 3 * (size_t) kResampleMaxSegments);
+    c->fl_out.reserve(c, (size_t) (frames * kFlacFrameOverhead + 2 * samples) + 4);
+    FlacArgs a;
+    a.x = dx; a.seg = c->fl_seg.p; a.scratch = c->fl_scratch.p; a.flen = c->fl_len.p; a.finfo = c->fl_info.p; a.out = c->fl_out.p; a.tot = c->fl_tot.p;
+    a.B = count; a.rate_code = flac_rate_code(rate); a.rate_khz = rate / 1000;
+    return a;
+}
+// the workgroups that share a result's copy in the pack launch: one per 4 frames of the longest result, at most 64 (one workgroup copying the 30 frames
+// of a 5.12 s result alone took 45 us)
+int flac_pack_split(const int (&seg)[3][kResampleMaxSegments + 1], int count) {
+    int most = 1;
+    for (int i = 0; i < count; i++) most = std::max(most, seg[2][i + 1] - seg[2][i]);
+    return std::min(64, (most + 3) / 4);
+}
+std::vector<uint8_t> flac_staged(bark_context * c, const int16_t * dx, const int * n, int count, int rate, std::vector<int32_t> & lengths, std::vector<int32_t> * frames_out) {
+    if (!flac_rate_code(rate)) throw std::runtime_error("flac: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
+    int seg[3][kResampleMaxSegments + 1];
+    const long long frames = fill_flac_table(seg, n, count);
+    if (frames < 0) throw std::runtime_error("flac: more than 2^30 samples in one call");
+    const FlacArgs a = flac_args(c, dx, count, frames, seg[1][count], rate);
+    hipStream_t s = c->stream;
+    HIP_OK(hipMemcpyAsync(c->fl_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+    launch_flac_frames(s, a, seg);
+    launch_flac_pack(s, a, flac_pack_split(seg, count));
+    int tot[3][kResampleMaxSegments];
+    HIP_OK(hipMemcpyAsync(tot, c->fl_tot.p, sizeof(tot), hipMemcpyDeviceToHost, s));
+    if (frames_out) {
+        frames_out->assign((size_t) frames * 4, 0);
+        HIP_OK(hipMemcpyAsync(frames_out->data(), c->fl_info.p, frames_out->size() * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipStreamSynchronize(s));                             // the totals size the copy below; seg is a stack object
+    size_t packed = 0;
+    for (int i = 0; i < count; i++) packed += (size_t) tot[0][i];
+    if (packed > c->fl_out.n) throw std::runtime_error("flac: the device reports more bytes than the bound");
+    std::vector<uint8_t> body(packed);
+    HIP_OK(hipMemcpyAsync(body.data(), c->fl_out.p, packed, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    std::vector<uint8_t> out(packed + (size_t) count * kFlacStreamHeader);
+    lengths.assign((size_t) count, 0);
+    size_t at = 0, from = 0;
+    for (int i = 0; i < count; i++) {
+        flac_stream_header(out.data() + at, n[i], rate, tot[1][i], tot[2][i]);
+        memcpy(out.data() + at + kFlacStreamHeader, body.data() + from, (size_t) tot[0][i]);
+        lengths[(size_t) i] = kFlacStreamHeader + tot[0][i];
+        at += (size_t) lengths[(size_t) i]; from += (size_t) tot[0][i];
+    }
+    return out;
+}
+}  // namespace
+
+std::vector<uint8_t> engine_flac_encode_many(bark_context * c, const int16_t * const * pcm, const int * n, int count, int rate, std::vector<int32_t> & lengths,
+                                             std::vector<int32_t> * frames) {
+    HIP_OK(hipSetDevice(c->device));
+    if (!pcm || !n || count < 1 || count > kResampleMaxSegments) throw std::runtime_error("flac: 1 .. 64 results in one call");
+    if (!flac_rate_code(rate)) throw std::runtime_error("flac: the rates are 8000, 12000, 16000, 22050, 24000, 32000, 44100 and 48000");
+    long long samples = 0;
+    for (int i = 0; i < count; i++) {
+        if (!pcm[i] || flac_max_bytes(n[i]) < 0) throw std::runtime_error("flac: a result needs 1 .. 2^26 samples");
+        samples += n[i];
+    }
+    if (samples > (1LL << 30)) throw std::runtime_error("flac: more than 2^30 samples in one call");
+    c->fl_in.reserve(c, (size_t) samples);
+    size_t off = 0;
+    for (int i = 0; i < count; i++) { HIP_OK(hipMemcpyAsync(c->fl_in.p + off, pcm[i], (size_t) n[i] * 2, hipMemcpyHostToDevice, c->stream)); off += (size_t) n[i]; }
+    return flac_staged(c, c->fl_in.p, n, count, rate, lengths, frames);
+}
+
+double engine_time_flac(bark_context * c, int count, int n_each, int iters, int which) {
+    HIP_OK(hipSetDevice(c->device));
+    if (count < 1 || count > kResampleMaxSegments || n_each < 1 || n_each > kResampleMaxSamples) throw std::runtime_error("time_flac: 1 .. 64 results of 1 .. 1 310 720 samples");
+    // the time depends on the values (the codes' lengths): a voiced tone under a slow envelope with a little noise on top, the same for every result
+    std::vector<int16_t> x((size_t) n_each);
+    uint32_t lcg = 12345u;
+    for (int i = 0; i < n_each; i++) {
+        lcg = lcg * 1664525u + 1013904223u;
+        const double env = 0.5 + 0.5 * sin(2.0 * M_PI * 3.0 * i / 24000.0);
+        x[(size_t) i] = (int16_t) lround(6000.0 * env * sin(2.0 * M_PI * 220.0 * i / 24000.0) + 1500.0 * env * sin(2.0 * M_PI * 1870.0 * i / 24000.0) + (double) ((int) (lcg >> 25) - 64));
+    }
+    const std::vector<int> n((size_t) count, n_each);
+    int seg[3][kResampleMaxSegments + 1];
+    const long long frames = fill_flac_table(seg, n.data(), count);
+    c->fl_in.reserve(c, (size_t) count * (size_t) n_each);
+    const FlacArgs a = flac_args(c, c->fl_in.p, count, frames, seg[1][count], 24000);
+    hipStream_t s = c->stream;
+    for (int i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(c->fl_in.p + (size_t) i * (size_t) n_each, x.data(), x.size() * 2, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->fl_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));
+    const int split = flac_pack_split(seg, count);
+    iters = std::max(1, iters);
+    launch_flac_frames(s, a, seg);                               // the pack launch reads what a frames launch wrote
+    auto one = [&] { if (which != 2) launch_flac_frames(s, a, seg); if (which != 1) launch_flac_pack(s, a, split); };
     for (int i = 0; i < 2; i++) one();
     return time_on_stream_us(c, [&] { for (int i = 0; i < iters; i++) one(); }) / iters;
 }

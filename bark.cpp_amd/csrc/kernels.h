@@ -417,4 +417,25 @@ struct LoudnessArgs {
 void launch_loudness_hops(hipStream_t s, const LoudnessArgs & a, const int (&host_seg)[5][kResampleMaxSegments + 1]);
 void launch_loudness_level(hipStream_t s, const LoudnessArgs & a);
 
+// ---- FLAC: the lossless encoder of the output path over up to 64 results in two launches (rule C18f; codec_kernels.hip) ----
+// Result s of n mono s16 samples has ceil(n / 4096) frames.  flac_frames_kernel: one workgroup per (result, frame) - the samples to LDS, the five fixed
+// predictors' absolute sums, the order, the per-partition Rice counts for parameters 0 .. 14, partition order and parameters (or escape, or VERBATIM, or
+// CONSTANT), every code's bit length, an exclusive scan, the bits into zeroed LDS words, both CRCs - and writes the frame to its slot of kFlacFrameStride
+// bytes in `scratch`, its byte length to flen and {subframe code, partition order, byte length, CRC-16} to finfo.  flac_pack_kernel: grid (results, y) - a
+// chunked exclusive scan of a result's frame lengths and a compacting copy: result s starts where the frames of the results in front of it end, its frames
+// back to back; tot[s], tot[64 + s], tot[128 + s]: the result's bytes, its smallest and its largest frame.  seg is a device table
+// [3][kResampleMaxSegments + 1] of ints: lengths, sample offsets into x and frame offsets (prefix sums, each closed by its total); launch_flac_frames checks
+// the host copy it is given against the rule before anything runs.  Subframe code: 0 CONSTANT, 1 VERBATIM, 8 + o FIXED of order o.
+constexpr int kFlacBlock = 4096, kFlacMaxPartitionOrder = 4, kFlacMaxRice = 14, kFlacMaxSamples = 1 << 26;
+constexpr int kFlacFrameStride = 8208;                   // 11 header bytes + 1 subframe byte + 2 * 4096 verbatim + 2 of CRC-16 = 8206, rounded up to 16
+constexpr int kFlacFrameOverhead = 14, kFlacStreamHeader = 42;
+// the code of the frame header's sample-rate field: the explicit code, or 12 ("kHz in 8 bits at the end of the header") for 12000; 0: not a supported rate
+int flac_rate_code(int rate);
+struct FlacArgs {
+    const short * x = nullptr; const int * seg = nullptr; unsigned * scratch = nullptr; int * flen = nullptr; int * finfo = nullptr;
+    unsigned char * out = nullptr; int * tot = nullptr; int B = 1; int rate_code = 0, rate_khz = 0;
+};
+void launch_flac_frames(hipStream_t s, const FlacArgs & a, const int (&host_seg)[3][kResampleMaxSegments + 1]);
+void launch_flac_pack(hipStream_t s, const FlacArgs & a, int split);
+
 }  // namespace barkhip

@@ -19,7 +19,7 @@
 // The recording is encoded by bark_hip_voice_from_audio on a clone kept for that purpose behind its own mutex: the contexts the collector owns are never
 // touched by a connection thread.
 // Output rate and sample format (bark_hip_audio_format, rule C14r): "sample_rate": 8000 | 12000 | 16000 | 22050 | 24000 | 32000 | 44100 | 48000 and "format": "f32" |
-// "s16" | "mulaw" in a /bark request (defaults: --sample-rate / --format, 24000 and f32) - the answer is a WAV with the matching header (IEEE float; 16-bit PCM;
+// "s16" | "mulaw" | "flac" in a /bark request (defaults: --sample-rate / --format, 24000 and f32) - the answer is a WAV with the matching header (IEEE float; 16-bit PCM;
 // 8-bit mu-law with a fact chunk), an unsupported value is answered 400.  POST /voices?name=NAME&resample=1 (for --voice-audio: --voice-audio-resample) takes a
 // recording at any of those rates and brings it to 24 kHz with bark_hip_resample on the encoder's clone; without the switch another rate stays a 400.
 // Long texts (rules C15s / C15j of bark_mi355x.h): "long": true in a /bark request (default: --long) takes a text of any length - it is split into chunks
@@ -30,12 +30,14 @@
 // Speaking rate (rule C16t of bark_mi355x.h): "speed": a number in 0.5 .. 2.0 in a /bark request (default: --speed, 1.0), sent to the collector as
 // lround(1000 speed) per mille - the answer is time-scaled on the device before "sample_rate" / "format" apply (with "long": every chunk, before the join),
 // and the WAV header follows the actual sample count.  Anything else is a 400.
+// FLAC (rule C18f of bark_mi355x.h): "format": "flac" (or --format flac) - the answer is a complete FLAC stream over the s16 samples, encoded on the device, with
+// Content-Type: audio/flac instead of a WAV; it combines with "sample_rate", "speed", "loudness" and "long" (one stream over the joined audio).
 // Loudness (rule C17l of bark_mi355x.h): "loudness": a number in -40 .. -5 (LUFS) in a /bark request (default: --loudness; off without it), sent to the
 // collector as lround(100 v) hundredths with a peak ceiling of 1.0 and a gain cap of 10 (+20 dB) - the answer is levelled on the device in front of "speed",
 // "sample_rate" and "format" (with "long": every chunk on its own, before the join).  Anything else is a 400 and draws no seed.
 // Plain POSIX sockets, one thread per connection, Connection: close; no third-party code.
 //
-//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw] [--long] [--max-tokens n] [--gap-ms n] [--speed x] [--loudness lufs]
+//   bark_batch_server -m model.bin [-a 127.0.0.1] [-p 1337] [-s seed] [--max-batch 32] [--max-wait-ms 5] [--streams 1] [--devices 0,1,...] [--temp t] [--fine-temp t] [--top-k k] [--top-p p] [--voice name=file ...] [--semantic-encoder file] [--voice-audio name=file.wav ...] [--voice-audio-resample] [--sample-rate hz] [--format f32|s16|mulaw|flac] [--long] [--max-tokens n] [--gap-ms n] [--speed x] [--loudness lufs]
 #include "bark.h"
 #include "bark_mi355x.h"
 #include "http_util.h"
@@ -115,7 +117,13 @@ bool loudness_default_on = false;
 double loudness_default = 0.0;
 bool loudness_valid(double v) { return v >= -40.0 && v <= -5.0; }
 bark_hip_loudness_params loudness_request(double v) { return bark_hip_loudness_params{(int32_t) lround(100.0 * v), 1.0f, 10.0f}; }
-bool format_valid(const bark_hip_audio_format & f) { return f.sample_format >= 0 && f.sample_format <= 2 && bark_hip_resample_out_len(1, 24000, f.sample_rate) >= 1; }
+// the body of an answer of nb bytes in the request's format: the stream itself for FLAC (rule C18f), else a WAV around the nb / width samples
+std::string answer_body(const std::vector<char> & bytes, int nb, const bark_hip_audio_format & af) {
+    if (af.sample_format == BARK_HIP_SAMPLE_FLAC) return std::string(bytes.data(), (size_t) nb);
+    const int width = af.sample_format == BARK_HIP_SAMPLE_F32 ? 4 : af.sample_format == BARK_HIP_SAMPLE_S16 ? 2 : 1;
+    return barkhttp::wav_samples(bytes.data(), nb / width, af.sample_rate, af.sample_format);
+}
+bool format_valid(const bark_hip_audio_format & f) { return f.sample_format >= 0 && f.sample_format <= 3 && bark_hip_resample_out_len(1, 24000, f.sample_rate) >= 1; }
 // the voices by name: read by every /bark request, written by POST /voices.  An entry is never changed, only replaced: a request that has looked its
 // voice up keeps it alive through its shared_ptr while a later POST puts another one under the same name
 std::shared_mutex voice_mutex;
@@ -246,12 +254,8 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
             }
             // "sample_rate" / "format": what the answer comes in; checked here as well, for the same reason
             bark_hip_audio_format af = format_defaults;
-            std::string fname;
-            const int hr = json_int(body, "sample_rate", af.sample_rate);
-            const bool hf = body.find("\"format\"") != std::string::npos;
-            if (hf) af.sample_format = json_string(body, "format", fname) ? barkhttp::sample_format_of(fname) : -1;
-            if (hr < 0 || !format_valid(af)) {
-                respond(fd, 400, "Bad Request", "text/plain", "\"sample_rate\" must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and \"format\" \"f32\", \"s16\" or \"mulaw\"");
+            if (!barkhttp::request_format(body, af.sample_rate, af.sample_format) || !format_valid(af)) {
+                respond(fd, 400, "Bad Request", "text/plain", "\"sample_rate\" must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and \"format\" \"f32\", \"s16\", \"mulaw\" or \"flac\"");
                 ::shutdown(fd, SHUT_RDWR);
                 ::close(fd);
                 return;
@@ -323,8 +327,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                     if (nb <= -2) {
                         std::vector<char> bytes((size_t) std::max(-nb - 2, 1));
                         nb = bark_hip_batcher_wait_bytes(batcher, ticket, bytes.data(), -nb - 2);
-                        const int width = af.sample_format == BARK_HIP_SAMPLE_F32 ? 4 : af.sample_format == BARK_HIP_SAMPLE_S16 ? 2 : 1;
-                        if (nb >= 0) respond(fd, 200, "OK", "audio/wav", barkhttp::wav_samples(bytes.data(), nb / width, af.sample_rate, af.sample_format), extra);
+                        if (nb >= 0) respond(fd, 200, "OK", barkhttp::answer_type(af.sample_format), answer_body(bytes, nb, af), extra);
                     }
                     if (nb < 0) respond(fd, 500, "Internal Server Error", "text/plain", "Internal Server Error");
                 }
@@ -344,8 +347,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
                 if (nb <= -2) {
                     std::vector<char> bytes((size_t) (-nb - 2));
                     nb = bark_hip_batcher_wait_bytes(batcher, ticket, bytes.data(), (int) bytes.size());
-                    const int width = af.sample_format == BARK_HIP_SAMPLE_F32 ? 4 : af.sample_format == BARK_HIP_SAMPLE_S16 ? 2 : 1;
-                    if (nb >= 0) respond(fd, 200, "OK", "audio/wav", barkhttp::wav_samples(bytes.data(), nb / width, af.sample_rate, af.sample_format));
+                    if (nb >= 0) respond(fd, 200, "OK", barkhttp::answer_type(af.sample_format), answer_body(bytes, nb, af));
                 }
                 if (nb < 0) respond(fd, 500, "Internal Server Error", "text/plain", "Internal Server Error");
                 ::shutdown(fd, SHUT_RDWR);
@@ -379,7 +381,7 @@ void serve(int fd, bark_hip_batcher * batcher, int sample_rate) {
 }
 
 void usage(const char * argv0) {
-    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")] [--speed x (speaking rate 0.5 .. 2.0, default 1; a request's \"speed\")] [--loudness lufs (target -40 .. -5, default: no levelling; a request's \"loudness\")]\n", argv0);
+    fprintf(stderr, "usage: %s -m model.bin [-a host] [-p port] [-s seed] [--max-batch n (<= 256; the context serves up to 64 at a time)] [--max-wait-ms n] [--streams n (1 .. 4 jobs in flight)] [--devices 0,1,... (one context and one worker per GPU, one queue)] [--temp t] [--fine-temp t] [--top-k k (0: off)] [--top-p p (1: off)] [--voice name=file (repeatable; a request selects one with \"voice\": \"name\")] [--semantic-encoder file (HuBERT + token head: voices from recordings)] [--voice-audio name=file.wav (repeatable; mono 24 kHz)] [--voice-audio-resample (recordings at 8000 .. 48000 Hz)] [--sample-rate hz (8000 .. 48000; a request's \"sample_rate\")] [--format f32|s16|mulaw|flac (a request's \"format\")] [--long (every request takes the long-form route; a request's \"long\")] [--max-tokens n (0: one sentence per chunk, 1 .. 255: merge up to n word pieces; a request's \"max_tokens\")] [--gap-ms n (silence between chunks, default 250; a request's \"gap_ms\")] [--speed x (speaking rate 0.5 .. 2.0, default 1; a request's \"speed\")] [--loudness lufs (target -40 .. -5, default: no levelling; a request's \"loudness\")]\n", argv0);
 }
 
 }  // namespace
@@ -416,7 +418,7 @@ int main(int argc, char ** argv) {
     }
     if (o.model.empty()) { usage(argv[0]); return 1; }
     format_defaults = bark_hip_audio_format{o.sample_rate, barkhttp::sample_format_of(o.format)};
-    if (!format_valid(format_defaults)) { fprintf(stderr, "%s: --sample-rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and --format f32, s16 or mulaw\n", argv[0]); return 1; }
+    if (!format_valid(format_defaults)) { fprintf(stderr, "%s: --sample-rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000 and --format f32, s16, mulaw or flac\n", argv[0]); return 1; }
     long_defaults.on = o.long_form; long_defaults.max_tokens = o.max_tokens; long_defaults.gap_ms = o.gap_ms;
     if (!long_valid(o.max_tokens, o.gap_ms)) { fprintf(stderr, "%s: --max-tokens must be 0 .. 255 and --gap-ms 0 .. 60000\n", argv[0]); return 1; }
     speed_default = o.speed;

@@ -273,8 +273,20 @@ inline std::string wav_f32(const float * pcm, int n, int rate) {
     return s;
 }
 
-// the request field / option value "f32" | "s16" | "mulaw" -> 0 | 1 | 2 (enum bark_hip_sample_format), -1: anything else
-inline int sample_format_of(const std::string & name) { return name == "f32" ? 0 : name == "s16" ? 1 : name == "mulaw" ? 2 : -1; }
+// the request field / option value "f32" | "s16" | "mulaw" | "flac" -> 0 | 1 | 2 | 3 (enum bark_hip_sample_format and BARK_HIP_SAMPLE_FLAC), -1: anything else
+inline int sample_format_of(const std::string & name) { return name == "f32" ? 0 : name == "s16" ? 1 : name == "mulaw" ? 2 : name == "flac" ? 3 : -1; }
+// A /bark request's "sample_rate" / "format" over the server's defaults in (rate, format): false for a field of the wrong type or a format name that is none
+// of the four (whether the engine serves the rate is the caller's check)
+inline bool request_format(const std::string & js, int32_t & rate, int32_t & format) {
+    if (json_int(js, "sample_rate", rate) < 0) return false;
+    if (js.find("\"format\"") != std::string::npos) {
+        std::string name;
+        format = json_string(js, "format", name) ? sample_format_of(name) : -1;
+    }
+    return format >= 0 && format <= 3;
+}
+// what an answer in `format` is served as: FLAC (3, rule C18f) is a complete stream and goes out as it is, everything else inside a WAV
+inline const char * answer_type(int format) { return format == 3 ? "audio/flac" : "audio/wav"; }
 
 // A mono WAV around n samples in one of the three sample formats: 0 IEEE float (tag 3, 32 bit; the bytes of wav_f32), 1 PCM (tag 1, 16 bit), 2 G.711 mu-law
 // (tag 7, 8 bit: a non-PCM format, so the fmt chunk carries cbSize = 0 and a `fact` chunk states the sample count; an odd data chunk is followed by a pad byte)

@@ -168,6 +168,8 @@ BARK_API double bark_hip_time_resample(struct bark_context * bctx, int n, int it
  * clamp is a real case; mu-law from that s16 value s: sign = s < 0 ? 0x80 : 0, mag = min(|s|, 32635) + 132, e = floor(log2 mag) - 7,
  * man = (mag >> (e + 3)) & 15, byte = ~(sign | e << 4 | man) & 0xFF (0 -> 0xFF, -1 -> 0x7F, 32767 -> 0x80, -32768 -> 0x00). */
 enum bark_hip_sample_format { BARK_HIP_SAMPLE_F32 = 0, BARK_HIP_SAMPLE_S16 = 1, BARK_HIP_SAMPLE_MULAW = 2 };
+/* a container over the s16 samples, not a sample format of its own: a further value of bark_hip_audio_format.sample_format (rule C18f, below) */
+enum bark_hip_container_format { BARK_HIP_SAMPLE_FLAC = 3 };
 struct bark_hip_audio_format { int32_t sample_rate; int32_t sample_format; };
 /* n_out for n samples (n itself for the identity), or -1: an unsupported pair, n < 0.  Needs no context. */
 BARK_API int bark_hip_resample_out_len(int n, int rate_in, int rate_out);
@@ -324,6 +326,36 @@ BARK_API int bark_hip_long_audio_with(struct bark_context * bctx, const struct b
 /* Device time (us) of ONE loudness_hops launch (level == 0) or ONE loudness_level launch with its scaled copy (level != 0) over `count` segments of n_each
  * samples, averaged over `iters` launches (hipEvents on the context's stream).  Returns < 0 on error. */
 BARK_API double bark_hip_time_loudness(struct bark_context * bctx, int count, int n_each, int level, int iters);
+
+/* FLAC (rule C18f): BARK_HIP_SAMPLE_FLAC is a lossless container over the mono s16 samples the format epilogue writes - behind loudness,
+ * speaking rate and output rate - encoded on the device in two launches whatever the number of results.  Blocks of 4096 samples (the last frame holds the
+ * rest, its size in the header's 16-bit field); fixed block size strategy; per frame one subframe: CONSTANT if all samples are equal, else the FIXED predictor
+ * of order 0 .. min(4, n - 1) with the smallest sum of |residual| (ties: the lower order), VERBATIM if that would not be smaller; no wasted-bits detection.
+ * Residuals: 4-bit Rice parameters, partition order 0 .. 4 (only orders that divide the block size and leave the first partition longer than the predictor
+ * order), per partition the parameter 0 .. 14 with the fewest bits (ties: the lower), the escape code where strictly smaller (raw width: the minimum signed
+ * width of the partition's residuals, 0 if all are zero), per frame the partition order with the fewest bits (ties: the lower).  The stream is "fLaC", one
+ * STREAMINFO block marked last (block sizes 4096 / 4096, smallest and largest frame, rate, 1 channel, 16 bits, the sample count, MD5 all zeros: not computed),
+ * then the frames.  Decoding returns the s16 samples bit for bit.
+ * Routes: bark_hip_get_audio_as / _at / _with, bark_hip_batch_audio_as / _at / _with, bark_hip_long_audio_as / _at / _with (one stream over the joined
+ * audio) and the collector's submit calls take the format and return a complete stream.  Its length is known only once it is made: these calls render first,
+ * then return the byte count, or -(2 + bytes) if capacity_bytes is too small (out may then be NULL).  The calls on caller audio (bark_hip_resample_many,
+ * bark_hip_tempo_many, bark_hip_level_many, bark_hip_join_many) keep refusing it: bark_hip_flac_encode_many is the call for caller audio.
+ * bark_hip_flac_max_bytes: 42 + 14 ceil(n / 4096) + 2 n, the size no stream of n samples exceeds, or -1 (n outside 1 .. 2^26); needs no context.
+ * bark_hip_flac_encode_many: count <= 64 recordings of n[i] s16 samples at `rate` (one of the eight rates) -> their streams back to back in `out`,
+ *   lengths[i] (optional) bytes each; returns the bytes written, -(2 + bytes) if capacity_bytes is too small (out may then be NULL; lengths is filled),
+ *   or -1 with the context still usable (a null argument, count outside 1 .. 64, n[i] outside 1 .. 2^26, an unsupported rate) before any launch.
+ * bark_hip_flac_frames (tests): out_Nx4[4 f ..] = subframe code (0 CONSTANT, 1 VERBATIM, 8 + o FIXED of order o), partition order, byte length and CRC-16 of
+ *   frame f of one recording; returns the frame count, or -1 (capacity_frames too small, or what bark_hip_flac_encode_many refuses).
+ * bark_hip_time_flac: device time (us) of ONE pair of launches (frames, pack) over `count` recordings of n_each samples (1 .. 1 310 720) of a synthetic
+ *   voiced signal at 24 kHz, averaged over `iters` pairs (hipEvents on the context's stream); bark_hip_time_flac_launch: of the frames launch (which == 1)
+ *   or the pack launch (which == 2) alone.  < 0 on error.
+ * Out of scope: LPC subframes, stereo, 24 bits, seek tables, Vorbis comments, the MD5 signature, streaming delivery. */
+BARK_API int bark_hip_flac_max_bytes(int n);
+BARK_API int bark_hip_flac_encode_many(struct bark_context * bctx, const int16_t * const * pcm, const int * n, int count, int rate, void * out, int capacity_bytes,
+                                       int32_t * lengths);
+BARK_API int bark_hip_flac_frames(struct bark_context * bctx, const int16_t * pcm, int n, int rate, int32_t * out_Nx4, int capacity_frames);
+BARK_API double bark_hip_time_flac(struct bark_context * bctx, int count, int n_each, int iters);
+BARK_API double bark_hip_time_flac_launch(struct bark_context * bctx, int count, int n_each, int which, int iters);
 
 /* Replicas on one GPU: a clone shares the (immutable) device weights of `src` and owns its stream, KV caches and
  * scratch, so several utterances can be in flight on one device.  Free clones and the original in any order. */
